@@ -304,10 +304,33 @@ class _HostStream:
         pass
 
 
-def run_workload(name, opt, env, steps, warmup, sites=None, samples=None, with_cpu=False, gather="index", early=None, strict=True):
+DUMP_MAX_SITES = 256
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(out, path, seed=20240611):
+    """What the last timed step left in the output arrays, on a fixed seeded sample of the sites (the same for the same
+    arguments): `path`/<field>.npy, integer fields as float64 (exact), float32 fields as they are, plus `sites.npy` = the site
+    indices sampled.  At most DUMP_MAX_SITES sites, and fewer when their rows would pass DUMP_BUDGET_BYTES."""
+    import numpy as np
+    import torch
+    S = out["site_status"].shape[0]
+    per_site = sum(v[0].numel() * (4 if v.dtype == torch.float32 else 8) for v in out.values())
+    n = max(1, min(S, DUMP_MAX_SITES, DUMP_BUDGET_BYTES // per_site))
+    idx = np.sort(np.random.default_rng(seed).choice(S, size=n, replace=False))
+    sel = torch.from_numpy(idx).to(out["site_status"].device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "sites.npy"), idx.astype(np.float64))
+    for k, v in out.items():
+        a = v.index_select(0, sel).cpu().numpy()
+        np.save(os.path.join(path, k + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+    log(f"outputs of the last timed step: {len(out)} fields on {n} of {S} sites -> {path}")
+
+
+def run_workload(name, opt, env, steps, warmup, sites=None, samples=None, with_cpu=False, gather="index", early=None, strict=True, dump=None):
     """K timed passes of the hot path over one workload; returns the result dictionary (rank 0) or None.
     `early(res)`: called on rank 0 as soon as the timed value exists, BEFORE anything that is allowed to fail or stall afterwards
-    (the sampled record gather over RCCL): the line is on stdout by then."""
+    (the sampled record gather over RCCL): the line is on stdout by then.  `dump`: directory for dump_outputs() (rank 0)."""
     import contextlib
     import ctypes as C
     import threading
@@ -469,6 +492,8 @@ def run_workload(name, opt, env, steps, warmup, sites=None, samples=None, with_c
     sim.check(stream.cuda_stream)
     kms, klaunch = sim.kernel_ms(reset=True)
     sim.timing(False)
+    if dump and rank == 0:
+        dump_outputs(out, dump)
     per_rank = None
     if dist is not None:
         # every rank's own clock and kernel buckets to rank 0 (the first multi-GPU run must show a load imbalance at once), then the max
@@ -562,14 +587,14 @@ def run_workload(name, opt, env, steps, warmup, sites=None, samples=None, with_c
             res["comm"] = {"backend": env.get("data_backend", opt.backend), "world": dist.get_world_size(), "gather": gather,
                            "gather_ms": comm["gather_s"] / steps * 1e3,
                            "gather_note": "per step on the writer: gather of the per-site record index (status, allele count) + all-reduce of the site counters"}
-            if gather == "sample":
+            if gather == "sample" and opt.full:
                 res["comm"]["records_sample"] = "pending"          # replaced below; stays if the sampled gather stalls and the watchdog ends the run
         if dist is not None and gather == "records":
             res["records_gather"] = {"bytes_per_step_at_writer": gathered_bytes[0] / steps, "GBps_into_writer": gathered_bytes[0] / dt / 1e9}
         if early is not None:
             early(res)
 
-    if dist is not None and gather == "sample":
+    if dist is not None and gather == "sample" and opt.full:
         # AFTER the timed steps and after rank 0 has printed the line: a failure is reported in `comm`, a stall ends the run with the
         # line already on stdout (the first 8-GPU run is the first time these point-to-point transfers execute over xGMI)
         def stalled():
@@ -609,7 +634,7 @@ def run_workload(name, opt, env, steps, warmup, sites=None, samples=None, with_c
                                                  "to rank 0, measured once AFTER the timed steps (not part of `value`; --gather records puts every tile's "
                                                  "records inside the timed steps)"})
     if res is not None:
-        if name == opt.workload and not opt.no_pack_rate and on_gpu:
+        if name == opt.workload and opt.full and not opt.no_pack_rate and on_gpu:
             # device-side packing of one tile's records (what precedes the gather): an HBM-bound gather
             s0, n, _ = structs[0]
             tile = {k: v[s0:s0 + n] for k, v in out.items()}
@@ -833,18 +858,19 @@ def emit(main_res, extra, opt, world, metric, dist_info=None, final=True):
             text = dumps_strict(line)
             if len(text) < LINE_LIMIT:
                 break
-    try:
-        path = detail_path(opt)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        full = dict(line, roofline=main_res["roofline"])
-        for k in ("cpu_baseline", "comm", "ranks", "record_packing", "records_gather"):
-            if k in main_res:
-                full[k] = main_res[k]
-        full["extra"] = extra
-        with open(path, "w") as f:
-            json.dump(full, f)
-    except Exception as e:
-        log(f"detail file not written: {e!r}")
+    if opt.detail_file or opt.full:
+        try:
+            path = detail_path(opt)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            full = dict(line, roofline=main_res["roofline"])
+            for k in ("cpu_baseline", "comm", "ranks", "record_packing", "records_gather"):
+                if k in main_res:
+                    full[k] = main_res[k]
+            full["extra"] = extra
+            with open(path, "w") as f:
+                json.dump(full, f)
+        except Exception as e:
+            log(f"detail file not written: {e!r}")
     if extra and final:
         print(dumps_strict(compact_extra(extra)), flush=True)
     print(text, flush=True)
@@ -934,6 +960,11 @@ def main():
     ap.add_argument("--no-records-leg", action="store_true", help="N > 1 with --gather sample: skip the short second leg that gathers every tile's records inside the timed step")
     ap.add_argument("--records-leg-tiles", type=int, default=4, help="tiles per rank of that leg (a budget the writer's memory and a few seconds hold)")
     ap.add_argument("--detail-file", default=None, help="where the full (unabridged) result goes; default gpurun_out/bench_detail.json")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the other workloads as `extra`, the host path, record packing, "
+                         "the copy bandwidth and, at N > 1, the sampled record gather and the record-gather leg; writes the detail file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (a fixed, seeded sample of its sites) as DIR/<field>.npy")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)     # internal: one shard of the all-cores CPU leg
     ap.add_argument("--cpu-single-worker", action="store_true", help=argparse.SUPPRESS)   # internal: the one-core CPU leg in a process of its own
     ap.add_argument("--host-path-worker", default=None, help=argparse.SUPPRESS)   # internal: the PCIe-inclusive host path in a fresh process
@@ -949,6 +980,8 @@ def main():
         return
     if opt.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if opt.steps < 1 or opt.warmup < 0:
+        sys.exit("--steps must be >= 1 and --warmup >= 0")
     if "RANK" not in os.environ and opt.gpus > 1:
         spawn_ranks(opt)                                       # does not return
 
@@ -989,7 +1022,7 @@ def main():
     args = workload_args(opt.workload)
     metric = METRIC if opt.workload in ("c3", "fixedq") else f"site-sample GL evals/s at depth {args.depth:g}"
     solo = world == 1 and dist is None and not stub
-    want_extra = solo and not opt.no_extra and opt.sites is None and opt.samples is None
+    want_extra = opt.full and solo and not opt.no_extra and opt.sites is None and opt.samples is None
 
     host_first = None
     if want_extra:
@@ -1006,8 +1039,9 @@ def main():
     def early(res):                                            # N > 1: the line is on stdout before the sampled record gather is attempted
         emit(res, {}, opt, world, metric, dist_info, final=False)
     main_res = run_workload(opt.workload, opt, env, opt.steps, opt.warmup, sites=opt.sites, samples=opt.samples,
-                            with_cpu=(not opt.no_cpu_baseline and solo), gather=opt.gather, early=(early if dist is not None else None))
-    if dist is not None and opt.gather == "sample" and not opt.no_records_leg:
+                            with_cpu=(opt.full and not opt.no_cpu_baseline and solo), gather=opt.gather,
+                            early=(early if dist is not None and opt.full else None), dump=opt.dump_outputs)
+    if opt.full and dist is not None and opt.gather == "sample" and not opt.no_records_leg:
         # north_star's record gather INSIDE the timed region, on a tile budget that fits the writer: `value` above moves no records (sites shard with
         # nothing exchanged; a full record gather is bound by the writer's links) -- this leg puts the figure WITH the gather beside it.
         # One warm-up and one timed pass over --records-leg-tiles tiles per rank, every tile's packed records point to point into rank 0.
@@ -1040,7 +1074,7 @@ def main():
                 main_res["record_gather_leg"] = {"status": "error", "error": repr(e)[:200], "sites_per_rank": leg_sites}
         dog.cancel()
     cpu_proc = None
-    if rank == 0 and solo and not opt.no_cpu_baseline:
+    if opt.full and rank == 0 and solo and not opt.no_cpu_baseline:
         # the one-core CPU leg runs in its own process BESIDE the extra GPU workloads (this thread only enqueues launches and waits);
         # the all-cores leg afterwards, with the GPU idle
         log("cpu baseline (one core) started ...")

@@ -25,7 +25,7 @@ def _lines(stdout):
 
 
 def test_world8_line_schema_with_rccl_fallback(tmp_path):
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--detail-file", str(tmp_path / "d.json")] + COMMON, env=_env(), capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--full", "--detail-file", str(tmp_path / "d.json")] + COMMON, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _lines(r.stdout)
     assert len(lines) == 2                                   # the early line (before the sampled gather) and the final one
@@ -54,7 +54,7 @@ def test_world8_line_schema_with_rccl_fallback(tmp_path):
 
 def test_a_rank_that_never_arrives_in_the_record_gather_does_not_cost_the_line():
     t0 = time.time()
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--comm-timeout", "8", "--backend", "gloo"] + COMMON, env=_env(BENCH_TEST_STALL_RANK="2"),
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--full", "--comm-timeout", "8", "--backend", "gloo"] + COMMON, env=_env(BENCH_TEST_STALL_RANK="2"),
                        capture_output=True, text=True, timeout=600)
     assert time.time() - t0 < 120
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])       # `value` is complete: the run is not failed by a transfer reported beside it ...

@@ -95,7 +95,7 @@ def test_bench_two_ranks_on_one_gpu_prints_a_self_describing_line(tmp_path):
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo", "--sites", "8192", "--tile-sites", "4096",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--share-gpu", "--backend", "gloo", "--sites", "8192", "--tile-sites", "4096",
                         "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-pack-rate", "--detail-file", str(tmp_path / "d.json")],
                        env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-1500:]

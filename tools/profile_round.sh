@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): tools/profile_round.sh <tag> [workload ...]      (default: every bench workload)
 # Collects what DESIGN.md section 5 and profiles/ quote for one round:
-#   gpurun_out/<tag>/bench.json                   default bench.py run (C3 + the other configurations as `extra`)  [skipped with NOBENCH=1]
+#   $out/bench.json                               bench.py --full run (C3 + the other configurations as `extra`)  [skipped with NOBENCH=1]
 #   gpurun_out/<tag>/<wl>/kt/.../kernel_stats     rocprofv3 --kernel-trace --stats of the workload's bench command (1 warm-up + 3 timed steps)
 #   gpurun_out/<tag>/<wl>/kernel_timed_stats.csv  the same trace, timed steps only (tools/trace_timed.py)      [KTONLY=1: stop here, no PMC passes]
 #   gpurun_out/<tag>/<wl>/pmc/<GROUP>/            one rocprofv3 --pmc pass per counter group (never mixed with a trace)
@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 out=gpurun_out/$tag
 mkdir -p "$out"
 if [ -z "${NOBENCH:-}" ]; then
-    python3 bench.py > "$out/bench.json" 2> "$out/bench.err"
+    python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err"
     tail -1 "$out/bench.json" | cut -c1-300
 fi
 Q="--no-cpu-baseline --no-extra --no-pack-rate"
