@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VGL_ABI_VERSION 6
+#define VGL_ABI_VERSION 7
 /* the library is built with -fvisibility=hidden: these entry points are its whole dynamic symbol table */
 #define VGL_API __attribute__((visibility("default")))
 
@@ -357,6 +357,39 @@ VGL_API int vgl_pack_plan_device(int32_t device, int32_t n_sites, const int32_t*
                                  vgl_pack_plan* totals, void* hip_stream);
 VGL_API int vgl_pack_records_device(int32_t device, int32_t n_sites, const int32_t* site_status, const int32_t* n_alleles, const int32_t* offsets,
                                     int32_t* index_out, const vgl_pack_field* fields, int32_t n_fields, void* hip_stream);
+
+/* ---- BGZF compression on the device (ABI 7) ------------------------------------------------------------------------------
+ * BGZF (SAMv1 section 4.1): independent gzip members of at most 64 KiB with their size in a 'BC' extra field -- what the reference
+ * writes through htslib for -O b / -O z (vcfgl.cpp:1790-1803) and its pileup.  The input is cut into members of exactly 0xff00 bytes
+ * (the last one shorter), the boundaries of the host program's zlib path, so the member count is ceil(n / 0xff00) and each member's
+ * ISIZE is the same as there; the compressed bytes differ from zlib's, what they decompress to does not.  Each member is LZ77 +
+ * Huffman coded by one workgroup and written as the smallest of a dynamic, a fixed and a stored deflate block (stored bounds every
+ * member by 0xff00 + 31 bytes).  The output depends on the input bytes only: not on the device, and not on how a caller splits its
+ * input at member boundaries (compressing a + b equals compressing a, then b, when a's length is a multiple of 0xff00).
+ *   vgl_bgzf_bound(n)            largest output for n input bytes: n + 31 * ceil(n / 0xff00) (-1 for n < 0).  Pure host arithmetic.
+ *   vgl_bgzf_workspace_bytes(n)  device workspace a call on n bytes needs (0 for n = 0, -1 for n < 0).  Pure host arithmetic.
+ *   vgl_bgzf_compress_device     src [n], dst [dst_cap >= vgl_bgzf_bound(n)], out_n (int64, may be NULL) and the workspace are device
+ *                                memory of `device`; work is enqueued on `hip_stream` and the call returns without synchronising.  dst
+ *                                receives the members back to back WITHOUT the 28-byte end-of-file member (a file ends with it once:
+ *                                1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00), *out_n their
+ *                                length.  Calls on one workspace must be ordered (one stream).  n = 0 writes *out_n = 0 and nothing else. */
+VGL_API int64_t vgl_bgzf_bound(int64_t n);
+VGL_API int64_t vgl_bgzf_workspace_bytes(int64_t n);
+VGL_API int vgl_bgzf_compress_device(int32_t device, const uint8_t* src, int64_t n, uint8_t* dst, int64_t dst_cap, int64_t* out_n,
+                                     void* workspace, int64_t workspace_bytes, void* hip_stream);
+/* Host batches, for a program that writes BGZF from host memory (the host program's --device-bgzf 1): a handle owns the device
+ * buffers, workspace and streams for batches of up to max_batch bytes, two of which may be in flight.
+ *   vgl_bgzf_host_submit  enqueues the copy of src [n <= max_batch] to the device and its compression; returns at once with a ticket.
+ *                         src must stay unchanged until the ticket is waited for (page-locked memory from vgl_host_alloc_on copies
+ *                         at the link's rate).  A third submit before a wait fails with VGL_E_ARG.
+ *   vgl_bgzf_host_wait    blocks until the ticket's members are back in host memory: *out (owned by the handle, valid until the
+ *                         ticket's slot is submitted again) holds *out_n bytes of members, without the EOF member.
+ * Tickets are waited for in submit order to keep a file's members in order.  No HIP device: VGL_E_NODEVICE from create. */
+typedef struct vgl_bgzf_host vgl_bgzf_host;
+VGL_API int vgl_bgzf_host_create(int32_t device, int64_t max_batch, vgl_bgzf_host** out);
+VGL_API int vgl_bgzf_host_submit(vgl_bgzf_host* h, const uint8_t* src, int64_t n, int32_t* ticket);
+VGL_API int vgl_bgzf_host_wait(vgl_bgzf_host* h, int32_t ticket, const uint8_t** out, int64_t* out_n);
+VGL_API int vgl_bgzf_host_destroy(vgl_bgzf_host* h);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,140 @@
+"""BGZF compression on the device (vgl_bgzf_compress_device, vcfgl_amd.bgzf) against Python's own zlib / gzip: every member's header
+fields, its raw deflate data, CRC32 and ISIZE, the member boundaries of the host writer (0xff00 input bytes), the stored fallback on
+incompressible data, determinism across calls and across a split at a member boundary, and the ratio on real program output."""
+import gzip
+import os
+import struct
+import subprocess
+import zlib
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+M = 0xff00
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "vcfgl_amd", "bin", "vcfgl_hip")
+
+
+def _compress(data):
+    import torch
+    from vcfgl_amd import bgzf
+    t = torch.from_numpy(np.frombuffer(bytes(data), dtype=np.uint8).copy()).to("cuda")
+    out = bgzf.compress(t)
+    assert out.device == t.device and out.dtype == torch.uint8
+    return out.cpu().numpy().tobytes()
+
+
+def members(raw, data):
+    """check every member of raw (no EOF member) against the input; returns the member sizes"""
+    off, k, sizes = 0, 0, []
+    while off < len(raw):
+        h = raw[off:off + 18]
+        assert h[:4] == b"\x1f\x8b\x08\x04" and h[10:12] == b"\x06\x00" and h[12:14] == b"BC" and h[14:16] == b"\x02\x00", h
+        bsize = struct.unpack_from("<H", h, 16)[0] + 1
+        assert bsize <= 65536
+        piece = data[k * M:(k + 1) * M]
+        d = zlib.decompress(raw[off + 18:off + bsize - 8], -15)
+        assert d == piece, (k, len(d), len(piece))
+        crc, isize = struct.unpack_from("<II", raw, off + bsize - 8)
+        assert crc == zlib.crc32(piece) and isize == len(piece)
+        sizes.append(bsize)
+        off += bsize
+        k += 1
+    assert off == len(raw) and k == -(-len(data) // M)
+    return sizes
+
+
+def roundtrip(data):
+    from vcfgl_amd import bgzf
+    raw = _compress(data)
+    sizes = members(raw, data)
+    assert gzip.decompress(raw + bgzf.EOF) == bytes(data)
+    return raw, sizes
+
+
+@pytest.mark.parametrize("n", [0, 1, M - 1, M, M + 1, 3 * M + 17])
+def test_sizes_at_member_boundaries(n):
+    rng = np.random.default_rng(n)
+    text = b"".join(b"chr1\t%d\t.\tA\tC\t.\tPASS\t.\tGT:DP\t0/1:%d\n" % (i, x) for i, x in enumerate(rng.integers(0, 40, n // 20 + 2)))
+    raw, _ = roundtrip(text[:n])
+    if n > 1000:
+        assert len(raw) < n                                # text compresses
+
+
+def test_random_bytes_take_the_stored_form():
+    data = np.random.default_rng(1).integers(0, 256, 16 << 20, dtype=np.uint8).tobytes()
+    raw, sizes = roundtrip(data)
+    assert max(sizes) <= 65535 and all(s == M + 31 for s in sizes[:-1])
+    assert len(raw) == len(data) + 31 * len(sizes)
+
+
+def test_zeros_compress_100x():
+    data = bytes(4 << 20)
+    raw, _ = roundtrip(data)
+    print(f"4 MB of zeros -> {len(raw)} bytes ({len(data) / len(raw):.0f}x)")
+    assert len(raw) * 100 <= len(data)
+
+
+def test_matches_at_distance_32768_and_32769():
+    rng = np.random.default_rng(7)
+    a = rng.integers(0, 256, 32768, dtype=np.uint8).tobytes()
+    b = rng.integers(0, 256, 32769, dtype=np.uint8).tobytes()
+    data = (a + a[:20000]) + (b + b[:12000])          # repeats at exactly 32768 (usable) and 32769 (too far for deflate)
+    data = data + data[:3 * M]
+    roundtrip(data)
+
+
+def test_short_periods_and_runs():
+    parts = [bytes([i % 7]) * (i * 37 % 600 + 1) + bytes(range(i % 256)) for i in range(400)]
+    data = b"".join(parts) * 3
+    raw, _ = roundtrip(data)
+    assert len(raw) < len(data) // 5
+
+
+def test_deterministic_and_split_at_member_boundary():
+    rng = np.random.default_rng(3)
+    words = [b"0/0", b"0/1", b"1/1", b"-0.30103", b"-1.2", b"\t", b"\n", b"PASS"]
+    data = b"".join(words[i] for i in rng.integers(0, len(words), 200000))[:5 * M + 999]
+    one = _compress(data)
+    assert _compress(data) == one
+    two = _compress(data[:2 * M]) + _compress(data[2 * M:])
+    assert two == one
+    members(one, data)
+
+
+@pytest.fixture(scope="module")
+def program_output(tmp_path_factory):
+    """the -O u BCF bytes and -O v text of a C3-flag run (depth 20, --error-qs 2, GL model 2)"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import synth
+    d = tmp_path_factory.mktemp("c3")
+    S, N = 512, 200
+    gt = synth.binary_sites(0, S, N)
+    tok = np.array(["0|0", "1|0", "0|1", "1|1"])
+    vcf = str(d / "in.vcf")
+    with open(vcf, "w") as f:
+        f.write("##fileformat=VCFv4.2\n##contig=<ID=chr1,length=%d>\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n" % (S + 1))
+        f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join("ind%d" % i for i in range(N)) + "\n")
+        for i in range(S):
+            idx = (gt[i] & 0xF).astype(np.int64) + 2 * (gt[i] >> 4).astype(np.int64)
+            f.write("chr1\t%d\t.\t0\t1\t.\tPASS\t.\tGT\t" % (i + 1) + "\t".join(tok[idx]) + "\n")
+    out = {}
+    for mode, ext in (("u", ".bcf"), ("v", ".vcf")):
+        r = subprocess.run([BIN, "-i", vcf, "-o", str(d / mode), "-O", mode, "--seed", "42", "--depth", "20", "-e", "0.01", "--error-qs", "2",
+                            "--beta-variance", "1e-5", "-GL", "2"], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-1500:]
+        out[mode] = open(str(d / mode) + ext, "rb").read()
+    return out
+
+
+@pytest.mark.parametrize("mode", ["u", "v"])
+def test_program_output_and_ratio(program_output, mode):
+    data = program_output[mode]
+    raw, _ = roundtrip(data)
+    z1 = sum(len(zlib.compress(data[i:i + M], 1)) for i in range(0, len(data), M))
+    z6 = sum(len(zlib.compress(data[i:i + M], 6)) for i in range(0, len(data), M))
+    print(f"-O {mode}: {len(data)} bytes -> device {len(raw)}, zlib level 1 {z1}, level 6 {z6} (device / level 1 = {len(raw) / z1:.3f})")
+    assert len(raw) <= 1.25 * z1

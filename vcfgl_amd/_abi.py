@@ -6,7 +6,7 @@ not been built -- the product path never falls back to a CPU implementation.
 import ctypes as C
 import os
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 VGL_OK = 0
 VGL_E_ARG, VGL_E_NODEVICE, VGL_E_NOMEM, VGL_E_CAPACITY, VGL_E_UNSUPPORTED, VGL_E_QSBIN, VGL_E_ADJQ = -1, -2, -3, -4, -5, -6, -7
@@ -90,6 +90,8 @@ EXPORTS = [
     "vgl_simulate_tile_device", "vgl_ctx_check", "vgl_ctx_timing", "vgl_ctx_kernel_ms", "vgl_rng_tile_max_sites", "vgl_rng_tile_site_hash",
     "vgl_simulate_tile_async", "vgl_tile_wait", "vgl_host_alloc", "vgl_host_alloc_on", "vgl_host_free", "vgl_ctx_info",
     "vgl_pack_plan_device", "vgl_pack_records_device",
+    "vgl_bgzf_bound", "vgl_bgzf_workspace_bytes", "vgl_bgzf_compress_device",
+    "vgl_bgzf_host_create", "vgl_bgzf_host_submit", "vgl_bgzf_host_wait", "vgl_bgzf_host_destroy",
 ]
 VGL_PACK_ROW, VGL_PACK_ROWS_G, VGL_PACK_ROWS_A = 0, 1, 2
 
@@ -157,6 +159,15 @@ def load_library(hooks=False):
     lib.vgl_ctx_info.argtypes = [C.c_void_p, C.POINTER(CtxInfo)]
     lib.vgl_pack_plan_device.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PackPlan), C.c_void_p]
     lib.vgl_pack_records_device.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PackField), C.c_int32, C.c_void_p]
+    lib.vgl_bgzf_bound.restype = C.c_int64
+    lib.vgl_bgzf_bound.argtypes = [C.c_int64]
+    lib.vgl_bgzf_workspace_bytes.restype = C.c_int64
+    lib.vgl_bgzf_workspace_bytes.argtypes = [C.c_int64]
+    lib.vgl_bgzf_compress_device.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vgl_bgzf_host_create.argtypes = [C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]
+    lib.vgl_bgzf_host_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+    lib.vgl_bgzf_host_wait.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    lib.vgl_bgzf_host_destroy.argtypes = [C.c_void_p]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

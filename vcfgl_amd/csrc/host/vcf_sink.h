@@ -23,6 +23,8 @@
 #include <thread>
 #include <vector>
 
+#include "../../../include/vcfgl_hip.h"
+
 namespace vsink {
 
 [[noreturn]] void fail(const char* fmt, ...);          // provided by the host program (prints, exits 1)
@@ -43,11 +45,27 @@ static void parallel_for(int n, int threads, F fn) {
 // BGZF: a series of gzip members of at most 64 KiB, each carrying its compressed size in a 'BC'
 // extra field, ended by an empty member.  Members are independent, so --threads N compresses N
 // at a time (the role of htslib's thread pool, vcfgl.cpp:1790-1803); the file does not depend on N.
+// Device mode (--device-bgzf 1): batches of 512 whole members go to a GPU in page-locked memory
+// and are compressed there (vgl_bgzf_host_*, over vgl_bgzf_compress_device); two batches alternate, so the device
+// compresses batch k while the program encodes batch k+1.  Member boundaries are the same in both
+// modes; the device's bytes depend only on the input, so the file does not depend on --threads there either.
 class Bgzf {
   public:
-    void open(FILE* f, int threads_) { fp = f; threads = std::max(1, threads_); buf.reserve(BLOCK * (size_t)batch()); }
+    void open(FILE* f, int threads_, int device_ = -1) {
+        fp = f; threads = std::max(1, threads_); device = device_;
+        if (device >= 0) { dev_open(); return; }
+        buf.reserve(BLOCK * (size_t)batch());
+    }
     void write(const void* p, size_t n) {
         const uint8_t* b = (const uint8_t*)p;
+        if (device >= 0) {
+            while (n) {
+                const size_t k = std::min(n, DEV_BATCH - fill);
+                memcpy(h_in[cur] + fill, b, k); fill += k; b += k; n -= k;
+                if (fill == DEV_BATCH) dev_submit();
+            }
+            return;
+        }
         const size_t cap = BLOCK * (size_t)batch();
         while (n) {
             const size_t k = std::min(n, cap - buf.size());
@@ -56,6 +74,7 @@ class Bgzf {
         }
     }
     void flush() {
+        if (device >= 0) { if (fill) dev_submit(); return; }
         if (buf.empty()) return;
         const int nb = (int)((buf.size() + BLOCK - 1) / BLOCK);
         std::vector<std::vector<uint8_t>> out(nb);
@@ -68,15 +87,43 @@ class Bgzf {
     }
     void close() {
         flush();
+        if (device >= 0) { dev_retrieve(); vgl_bgzf_host_destroy(dev); dev = nullptr; for (auto& p : h_in) { vgl_host_free(p); p = nullptr; } }
         static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         if (fwrite(eof, 1, 28, fp) != 28) fail("write error");
     }
   private:
     static constexpr size_t BLOCK = 0xff00;
+    static constexpr size_t DEV_BATCH = BLOCK * 512;             // 33.4 MB of input per device batch
     FILE* fp = nullptr;
     int threads = 1;
+    int device = -1;                                             // >= 0: device mode on this GPU
     std::vector<uint8_t> buf;
+    vgl_bgzf_host* dev = nullptr;
+    uint8_t* h_in[2] = {nullptr, nullptr};                       // page-locked batches: one filling, one in flight
+    size_t fill = 0;
+    int cur = 0, in_flight = -1;                                 // in_flight: ticket of the submitted batch not yet written
     int batch() const { return threads == 1 ? 1 : threads * 4; }
+    void dev_open() {
+        if (vgl_bgzf_host_create(device, (int64_t)DEV_BATCH, &dev) != VGL_OK)
+            fail("--device-bgzf 1 needs a GPU: %s (device %d; --device-bgzf 0 compresses with zlib on the host)", vgl_last_error(), device);
+        for (auto& p : h_in)
+            if (!(p = (uint8_t*)vgl_host_alloc_on(device, DEV_BATCH))) fail("--device-bgzf 1: page-locked host memory could not be allocated: %s", vgl_last_error());
+    }
+    // the filled batch to the device; the one before it (compressed meanwhile) to the file, then its buffer is filled next
+    void dev_submit() {
+        int32_t ticket;
+        if (vgl_bgzf_host_submit(dev, h_in[cur], (int64_t)fill, &ticket) != VGL_OK) fail("--device-bgzf 1: %s", vgl_last_error());
+        dev_retrieve();
+        in_flight = ticket;
+        cur ^= 1; fill = 0;
+    }
+    void dev_retrieve() {
+        if (in_flight < 0) return;
+        const uint8_t* o; int64_t m;
+        if (vgl_bgzf_host_wait(dev, in_flight, &o, &m) != VGL_OK) fail("--device-bgzf 1: %s", vgl_last_error());
+        if (fwrite(o, 1, (size_t)m, fp) != (size_t)m) fail("write error");
+        in_flight = -1;
+    }
     static void compress_block(const uint8_t* in, size_t len, std::vector<uint8_t>& o) {
         o.resize(65536);
         uint8_t* out = o.data();
@@ -124,11 +171,13 @@ class Sink {
 
     // header = the '##' lines in output order; records may only use contigs / keys these lines define
     // (define_missing() adds the definitions htslib would add with a warning)
-    void open(const std::string& path, char mode_, std::vector<std::string> header, const std::vector<std::string>& samples, int threads = 1) {
+    // bgzf_device >= 0: BGZF members (-O z / -O b) are compressed on that GPU (--device-bgzf 1)
+    void open(const std::string& path, char mode_, std::vector<std::string> header, const std::vector<std::string>& samples, int threads = 1,
+              int bgzf_device = -1) {
         mode = mode_; N = (int)samples.size();
         fp = fopen(path.c_str(), "wb");
         if (!fp) fail("Could not open file: %s", path.c_str());
-        if (mode == 'z' || mode == 'b') bg.open(fp, threads);
+        if (mode == 'z' || mode == 'b') bg.open(fp, threads, bgzf_device);
         if (binary()) build_dictionaries(header);
         std::string text;
         for (const std::string& h : header) { text += h; text += '\n'; }

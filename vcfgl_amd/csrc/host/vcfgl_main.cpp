@@ -59,6 +59,7 @@ struct Args {
     int add_fmt_ad = 0, add_info_ad = 0, add_fmt_adf = 0, add_info_adf = 0, add_fmt_adr = 0, add_info_adr = 0;
     int rng_mode = VGL_RNG_TILE, beta_sampler = -1, tile_sites = 4096, device = 0, verbose = 0, threads = 1, enc_threads = 0;
     bool threads_given = false;
+    int device_bgzf = 0;               // --device-bgzf 1: BGZF streams compressed on the first device of the run
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -89,6 +90,10 @@ static const char USAGE[] =
     "                   --beta-sampler 0|1 [0: the rand48 sampler, 1: std::mt19937 (default with --rng-mode 1)]\n"
     "                   --tile-sites INT [4096]    --device INT [0]    --devices INT,INT,... (several GPUs of the node: sites shard by\n"
     "                   absolute index, the output does not depend on the device count; --rng-mode 0 only)    --encode-threads INT\n"
+    "                   --device-bgzf 0|1 [0: BGZF members compressed by zlib on the host; 1: on the first GPU of --device / --devices,\n"
+    "                   for every BGZF stream the run writes (-O b / -O z output, truth file, -printPileup's .pileup.gz; with -O u / -O v\n"
+    "                   the output and truth files are not BGZF and the flag changes nothing there).  Same decompressed bytes either way;\n"
+    "                   a run without a GPU fails instead of falling back, --depth inf included]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 static Args parse_args(int argc, char** argv) {
@@ -165,6 +170,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--beta-sampler") a.beta_sampler = I(v);
         else if (f == "--tile-sites") a.tile_sites = I(v);
         else if (f == "--device") a.device = I(v);
+        else if (f == "--device-bgzf") a.device_bgzf = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -190,6 +196,7 @@ static Args parse_args(int argc, char** argv) {
     if ((a.adjust_qs & 4) && !a.print_pileup) die("--adjust-qs 4 requires --printPileup 1. Please set --printPileup 1 and rerun.");   // io.cpp:891-898
     if ((a.adjust_qs & 8) && !a.print_qscores) die("--adjust-qs 8 requires --printQScores 1. Please set --printQScores and rerun.");
     if ((a.adjust_qs & 16) && !a.print_gl_err) die("--adjust-qs 16 requires --printGlError 1. Please set --printGlError 1 and rerun.");
+    range(a.device_bgzf, 0, 1, "--device-bgzf");
     range(a.print_pileup, 0, 1, "-printPileup"); range(a.print_truth, 0, 1, "-printTruth"); range(a.print_bpe, 0, 1, "-printBasePickError");
     range(a.print_qs_err, 0, 1, "-printQsError"); range(a.print_gl_err, 0, 1, "-printGlError"); range(a.print_qscores, 0, 1, "-printQScores");
     if (a.print_gl_err && a.gl_model == 1)                                                                                              // io.cpp:993
@@ -794,6 +801,7 @@ int main(int argc, char** argv) {
     // (on the first device the run selected: a primary context on GPU 0 would otherwise be created for a run that never uses it;
     //  a failure here is not swallowed for good -- vgl_ctx_create on the same device reports it below)
     const int warm_dev = a.devices.empty() ? a.device : a.devices[0];
+    const int bgzf_dev = a.device_bgzf ? warm_dev : -1;         // --device-bgzf 1: the run's first device compresses every BGZF stream
     if (!a.depth_inf) hip_warm = std::thread([warm_dev] { vgl_host_free(vgl_host_alloc_on(warm_dev, 4096)); });
     Vcf vcf = read_vcf(a.in_fn, a.print_truth != 0, enc_threads);
     if (hip_warm.joinable()) hip_warm.join();
@@ -822,7 +830,7 @@ int main(int argc, char** argv) {
         std::vector<std::string> hdr = vcf.header;
         hdr.push_back("##source=vcfgl_hip"); hdr.push_back("##source=" + a.command);
         complete_header(hdr);
-        truth_sink.open(a.out_prefix + ".truth" + ext, mode, hdr, vcf.samples);
+        truth_sink.open(a.out_prefix + ".truth" + ext, mode, hdr, vcf.samples, 1, bgzf_dev);
         stream.truth = &truth_sink;
     }
     size_t n_sites_total = 0;
@@ -836,7 +844,7 @@ int main(int argc, char** argv) {
         if (a.add_gp) hdr.push_back("##FORMAT=<ID=GP,Number=G,Type=Float,Description=\"Genotype probabilities\">");
         if (a.add_pl) hdr.push_back("##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods\">");
         complete_header(hdr);
-        out.open(a.out_prefix + ext, mode, hdr, vcf.samples);
+        out.open(a.out_prefix + ext, mode, hdr, vcf.samples, 1, bgzf_dev);
         const bool explode_acgt = a.do_unobserved >= 3;
         const bool add_unobs = (a.do_unobserved == 1 || a.do_unobserved == 2 || a.do_unobserved == 4 || a.do_unobserved == 5);
         const char* nonref = (a.do_unobserved == 1 || a.do_unobserved == 4) ? "<*>" : "<NON_REF>";
@@ -944,12 +952,12 @@ int main(int argc, char** argv) {
         if (a.add_info_adr) hdr.push_back("##INFO=<ID=ADR,Number=R,Type=Integer,Description=\"Total allelic depths, reverse strand\">");
         complete_header(hdr);
         // BGZF compression threads: --threads as in the reference; when it is not given, up to 8 (same bytes either way)
-        out.open(a.out_prefix + ext, mode, hdr, vcf.samples, a.threads_given ? a.threads : (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
+        out.open(a.out_prefix + ext, mode, hdr, vcf.samples, a.threads_given ? a.threads : (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())), bgzf_dev);
     }
     FILE* pile_fp = nullptr; vsink::Bgzf pile;            // the reference writes the pileup through htslib's BGZF (vcfgl.cpp:1776-1783)
     if (a.print_pileup) {
         pile_fp = fopen((a.out_prefix + ".pileup.gz").c_str(), "wb"); if (!pile_fp) die("Could not open pileup output");
-        pile.open(pile_fp, 1);
+        pile.open(pile_fp, 1, bgzf_dev);
     }
     // ---- TSV lines on stdout (vcfgl.cpp:430-435, 533-554, 1745-1755)
     int pre_q = -1, pre_adjq = -1;                                              // preCalc->qScore / adj_qScore
