@@ -10,6 +10,8 @@ import zlib
 import numpy as np
 import pytest
 
+import bgzf_model
+
 pytestmark = pytest.mark.gpu
 
 M = 0xff00
@@ -37,6 +39,7 @@ def members(raw, data):
         piece = data[k * M:(k + 1) * M]
         d = zlib.decompress(raw[off + 18:off + bsize - 8], -15)
         assert d == piece, (k, len(d), len(piece))
+        assert bgzf_model.inflate_member(raw[off:off + bsize])["out"] == piece, k
         crc, isize = struct.unpack_from("<II", raw, off + bsize - 8)
         assert crc == zlib.crc32(piece) and isize == len(piece)
         sizes.append(bsize)
