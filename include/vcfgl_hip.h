@@ -391,6 +391,55 @@ VGL_API int vgl_bgzf_host_submit(vgl_bgzf_host* h, const uint8_t* src, int64_t n
 VGL_API int vgl_bgzf_host_wait(vgl_bgzf_host* h, int32_t ticket, const uint8_t** out, int64_t* out_n);
 VGL_API int vgl_bgzf_host_destroy(vgl_bgzf_host* h);
 
+/* ---- VCF text of the sample columns on the device (ABI 7, additive) --------------------------------------------------------
+ * The N-wide part of a VCF text record -- what the host writer appends behind the eight fixed columns -- formatted from the tile's
+ * FORMAT arrays where they are computed.  For every site i with site_status[i] >= 0 the text is
+ *     "\t" KEYS ( "\t" sample_0 ) ... ( "\t" sample_{N-1} ) "\n"
+ * KEYS = the fields' keys joined by ':' ("." without fields); a sample column = its fields joined by ':', a field's values by ','.
+ * A skipped site (site_status < 0) has no text.  Numbers are written as the host program writes them (htslib's kputd): int32 %d with
+ * VGL_INT32_MISSING as "."; float32 VGL_FLOAT_MISSING_BITS as ".", other NaN "nan", [1e-4, 999999] in kputd's 6-digit integer
+ * form, everything else (infinity included) as glibc's %g, correctly rounded.  The bytes are identical to the host writer's.
+ *   vgl_text_field            one FORMAT field: value k of sample s of site i at ((T*)base)[i * site_stride + s * n(i) + k] -- the
+ *                             VGL_LAYOUT_SAMPLE_MAJOR slabs -- with n(i) = 1 (VGL_TEXT_ONE), nA (nA + 1) / 2 (VGL_TEXT_PER_G) or nA
+ *                             (VGL_TEXT_PER_A), nA = n_alleles[i].  Fields are written in the order given.
+ *   vgl_text_bound            largest text of n_sites sites with at most max_alleles alleles (pure host arithmetic; -1 on bad input).
+ *   vgl_text_workspace_bytes  device workspace of a call (pure host arithmetic).
+ *   vgl_text_format_device    site_status, n_alleles, the fields' values, dst [dst_cap], offsets (int64 [n_sites + 1]) and the workspace
+ *                             are device memory of `device`; work is enqueued on `hip_stream` without synchronising.  offsets[i] = where
+ *                             site i's text starts in dst, offsets[n_sites] = the total.  When the total exceeds dst_cap NOTHING is
+ *                             written to dst; offsets still receives the sizes, so the caller reads offsets[n_sites] to learn what
+ *                             the text needs.
+ *   vgl_ctx_text_bound        vgl_text_bound of the fields vgl_simulate_tile_text_async formats for this context.
+ *   vgl_simulate_tile_text_async
+ *                             vgl_simulate_tile_async whose FORMAT tags come back as text (a context with out_layout =
+ *                             VGL_LAYOUT_SAMPLE_MAJOR; VGL_E_ARG otherwise): the tags the context's add_* flags enable
+ *                             (DP, GL, PL, GP, AD, ADF, ADR: add_tags()'s order) are formatted on the device and the tile's text is
+ *                             copied to `text` [text_cap] (host memory; page-locked copies at the link's rate), its site offsets to
+ *                             `offsets` (host, int64 [n_sites + 1]).  The per-site arrays of `out` are copied as by
+ *                             vgl_simulate_tile_async; its per-sample FORMAT pointers may be NULL (those planes are then not copied back:
+ *                             the text replaces them).  Completed by vgl_tile_wait: a tile that drew deeper than the staging capacity is
+ *                             run again and formatted again; a text larger than text_cap gives VGL_E_CAPACITY, offsets[n_sites] = the
+ *                             size it needs, and nothing is written to `text`.  Only the bytes the tile produced cross the link. */
+#define VGL_TEXT_ONE        0
+#define VGL_TEXT_PER_G      1
+#define VGL_TEXT_PER_A      2
+#define VGL_TEXT_MAX_FIELDS 8
+typedef struct vgl_text_field {
+    const char* key;          /* FORMAT key (host string)                          */
+    int32_t     is_float;     /* 1: float32 values, 0: int32                       */
+    int32_t     count;        /* VGL_TEXT_*                                        */
+    const void* base;         /* device memory                                     */
+    int64_t     site_stride;  /* elements from one site's slab to the next         */
+} vgl_text_field;
+VGL_API int64_t vgl_text_bound(int32_t n_samples, int32_t n_sites, const vgl_text_field* fields, int32_t n_fields, int32_t max_alleles);
+VGL_API int64_t vgl_text_workspace_bytes(int32_t n_samples, int32_t n_sites);
+VGL_API int vgl_text_format_device(int32_t device, const vgl_text_field* fields, int32_t n_fields, int32_t n_samples, int32_t n_sites,
+                                   const int32_t* site_status, const int32_t* n_alleles, uint8_t* dst, int64_t dst_cap, int64_t* offsets,
+                                   void* workspace, int64_t workspace_bytes, void* hip_stream);
+VGL_API int64_t vgl_ctx_text_bound(const vgl_ctx* ctx, int32_t n_sites);
+VGL_API int vgl_simulate_tile_text_async(vgl_ctx* ctx, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* out,
+                                         uint8_t* text, int64_t text_cap, int64_t* offsets, int32_t* ticket);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,12 +92,21 @@ EXPORTS = [
     "vgl_pack_plan_device", "vgl_pack_records_device",
     "vgl_bgzf_bound", "vgl_bgzf_workspace_bytes", "vgl_bgzf_compress_device",
     "vgl_bgzf_host_create", "vgl_bgzf_host_submit", "vgl_bgzf_host_wait", "vgl_bgzf_host_destroy",
+    "vgl_text_bound", "vgl_text_workspace_bytes", "vgl_text_format_device", "vgl_ctx_text_bound", "vgl_simulate_tile_text_async",
 ]
 VGL_PACK_ROW, VGL_PACK_ROWS_G, VGL_PACK_ROWS_A = 0, 1, 2
 
 
 class PackField(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("kind", C.c_int32), ("planes", C.c_int32), ("row_bytes", C.c_int64)]
+
+
+VGL_TEXT_ONE, VGL_TEXT_PER_G, VGL_TEXT_PER_A = 0, 1, 2
+VGL_TEXT_MAX_FIELDS = 8
+
+
+class TextField(C.Structure):
+    _fields_ = [("key", C.c_char_p), ("is_float", C.c_int32), ("count", C.c_int32), ("base", C.c_void_p), ("site_stride", C.c_int64)]
 
 
 class PackPlan(C.Structure):
@@ -168,6 +177,16 @@ def load_library(hooks=False):
     lib.vgl_bgzf_host_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
     lib.vgl_bgzf_host_wait.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     lib.vgl_bgzf_host_destroy.argtypes = [C.c_void_p]
+    lib.vgl_text_bound.restype = C.c_int64
+    lib.vgl_text_bound.argtypes = [C.c_int32, C.c_int32, C.POINTER(TextField), C.c_int32, C.c_int32]
+    lib.vgl_text_workspace_bytes.restype = C.c_int64
+    lib.vgl_text_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.vgl_text_format_device.argtypes = [C.c_int32, C.POINTER(TextField), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vgl_ctx_text_bound.restype = C.c_int64
+    lib.vgl_ctx_text_bound.argtypes = [C.c_void_p, C.c_int32]
+    lib.vgl_simulate_tile_text_async.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(TileOut), C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.POINTER(C.c_int32)]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

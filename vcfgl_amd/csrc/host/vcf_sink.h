@@ -208,6 +208,7 @@ class Sink {
     // Records are encoded into byte strings by encode_line() / encode_rec() (const: several threads may
     // encode different records at once) and appended to the file in order by put().
     void put(const std::string& bytes) { emit(bytes.data(), bytes.size()); }
+    void put(const void* bytes, size_t n) { emit(bytes, n); }          // bytes encoded elsewhere (--device-text 1: a record's sample columns)
     void write_line(const std::string& line) { std::string b; encode_line(line, b); put(b); }
     void write_rec(const std::string& shared8, const std::vector<FmtDesc>& fmt) { std::string b; encode_rec(shared8, fmt, b); put(b); }
 

@@ -60,6 +60,7 @@ struct Args {
     int rng_mode = VGL_RNG_TILE, beta_sampler = -1, tile_sites = 4096, device = 0, verbose = 0, threads = 1, enc_threads = 0;
     bool threads_given = false;
     int device_bgzf = 0;               // --device-bgzf 1: BGZF streams compressed on the first device of the run
+    int device_text = 0;               // --device-text 1: the sample columns of VCF text records formatted on the device
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -94,6 +95,9 @@ static const char USAGE[] =
     "                   for every BGZF stream the run writes (-O b / -O z output, truth file, -printPileup's .pileup.gz; with -O u / -O v\n"
     "                   the output and truth files are not BGZF and the flag changes nothing there).  Same decompressed bytes either way;\n"
     "                   a run without a GPU fails instead of falling back, --depth inf included]\n"
+    "                   --device-text 0|1 [0: the sample columns of -O v / -O z records formatted on the host; 1: on the device that\n"
+    "                   simulated the tile, and the text crosses the link instead of the FORMAT arrays.  Same bytes either way; needs -O v\n"
+    "                   or -O z, refused with -doGVCF 1 and --depth inf; a run without a GPU fails instead of falling back]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 static Args parse_args(int argc, char** argv) {
@@ -171,6 +175,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--tile-sites") a.tile_sites = I(v);
         else if (f == "--device") a.device = I(v);
         else if (f == "--device-bgzf") a.device_bgzf = I(v);
+        else if (f == "--device-text") a.device_text = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -221,6 +226,12 @@ static Args parse_args(int argc, char** argv) {
         die("[Bad argument value: '--output-mode %s'] Allowed values are b, u, z, v", a.output_mode.c_str());
     if ((a.output_mode == "v" || a.output_mode == "z") && a.threads > 1)                      // io.cpp:1206-1210
         die("Multithreading is not supported for VCF output. Please set --threads 1 and rerun.");
+    range(a.device_text, 0, 1, "--device-text");
+    if (a.device_text) {                                        // (checked before any GPU work: nothing is written)
+        if (a.output_mode != "v" && a.output_mode != "z") die("--device-text 1 formats VCF text: it needs -O v or -O z (found -O %s).", a.output_mode.c_str());
+        if (a.do_gvcf) die("--device-text 1 is not supported with -doGVCF 1 (the gVCF blocker reads the FORMAT arrays of every site on the host).");
+        if (a.depth_inf) die("--device-text 1 is not supported with --depth inf (no tile is simulated).");
+    }
     if (a.seed == -1) { a.seed = (int)time(NULL); fprintf(stderr, "\n-> No seed was given. Setting the random seed to the randomly chosen value: %d\n", a.seed); }
     if (a.beta_sampler < 0) a.beta_sampler = (a.rng_mode == VGL_RNG_SERIAL) ? VGL_BETA_STD : VGL_BETA_RAND48;
     if (!a.depths_fn.empty()) {
@@ -977,7 +988,9 @@ int main(int argc, char** argv) {
     const char* nonref = (a.do_unobserved == 1 || a.do_unobserved == 4) ? "<*>" : "<NON_REF>";
 
     // ---- tile buffers (host side of vgl_tile_out): only what this run prints is requested from the device
-    const bool want_dp = a.add_fmt_dp || a.do_gvcf || pile_fp || dump_reads;
+    // --device-text 1: the FORMAT arrays stay on the device (formatted there), DP comes back only for the pileup / per-read listings
+    const bool dtext = a.device_text != 0;
+    const bool want_dp = (a.add_fmt_dp && !dtext) || a.do_gvcf || pile_fp || dump_reads;
     struct TileBufs {
         int ns = 0; int64_t t0 = 0; int dev = 0;
         std::vector<SiteMeta> meta; std::vector<uint8_t> gt;
@@ -985,6 +998,7 @@ int main(int argc, char** argv) {
         PBuf<uint8_t> reads;
         PBuf<int32_t> st, na, nobs, idp, iad, iadf, iadr, dp, pl, ad, adf, adr;
         PBuf<int8_t> a2b; PBuf<float> qs, i16, gl, gp; PBuf<double> errp, pick;
+        PBuf<uint8_t> text; PBuf<int64_t> toff; int64_t text_cap = 0;      // --device-text 1: the tile's sample columns and site offsets
         vgl_tile_out o;
         std::mutex m; std::condition_variable cv; bool done = false;
     };
@@ -1002,7 +1016,7 @@ int main(int argc, char** argv) {
         // buffers are placed next to that device
         const int dev_of_entry = devices[ri % (size_t)D];
         PBuf<uint8_t>::device() = dev_of_entry; PBuf<int32_t>::device() = dev_of_entry; PBuf<int8_t>::device() = dev_of_entry;
-        PBuf<float>::device() = dev_of_entry; PBuf<double>::device() = dev_of_entry;
+        PBuf<float>::device() = dev_of_entry; PBuf<double>::device() = dev_of_entry; PBuf<int64_t>::device() = dev_of_entry;
         B.meta.resize(TS); B.gt.resize(E);
         B.st.resize(TS); B.na.resize(TS); B.nobs.resize(TS); B.a2b.resize((size_t)TS * 5);
         memset(&B.o, 0, sizeof B.o);
@@ -1014,6 +1028,12 @@ int main(int argc, char** argv) {
         if (a.add_qs) { B.qs.resize((size_t)TS * A); B.o.qs = B.qs.data(); }
         if (a.add_i16) { B.i16.resize((size_t)TS * 16); B.o.i16 = B.i16.data(); }
         if (want_dp) { B.dp.resize(E); B.o.fmt_dp = B.dp.data(); }
+        if (dtext) {
+            B.text_cap = vgl_ctx_text_bound(ctxs[ri % (size_t)D], TS);
+            if (B.text_cap < 0) die("--device-text 1: %s", vgl_last_error());
+            B.text.resize((size_t)std::max<int64_t>(B.text_cap, 1)); B.toff.resize((size_t)TS + 1);
+            return;
+        }
         if (a.add_gl) { B.gl.resize(E * G); B.o.gl = B.gl.data(); }
         if (a.add_pl) { B.pl.resize(E * G); B.o.pl = B.pl.data(); }
         if (a.add_gp) { B.gp.resize(E * G); B.o.gp = B.gp.data(); }
@@ -1024,16 +1044,17 @@ int main(int argc, char** argv) {
     alloc_entry(0);
     // one worker per device: simulates the tiles handed to it, in order
     struct Worker { std::thread th; std::mutex m; std::condition_variable cv; std::vector<TileBufs*> q; size_t head = 0; bool stop = false;
-                    long tiles = 0, sites = 0; double t_first = -1.0, t_last = 0.0; };          // --verbose 1: what this device did (written by its own thread, read after the join)
+                    long tiles = 0, sites = 0; double t_first = -1.0, t_last = 0.0; double text_bytes = 0.0; };          // --verbose 1: what this device did (written by its own thread, read after the join)
     // bytes a finished tile brings back over the link, per site (the FORMAT arrays dominate: sample-major slabs, copied whole)
-    const double bytes_per_site = (double)N * ((want_dp ? 4.0 : 0.0) + 4.0 * G * ((a.add_gl ? 1 : 0) + (a.add_pl ? 1 : 0) + (a.add_gp ? 1 : 0)) +
-                                               4.0 * A * ((a.add_fmt_ad ? 1 : 0) + (a.add_fmt_adf ? 1 : 0) + (a.add_fmt_adr ? 1 : 0))) + 64.0;
+    // (--device-text 1: the text instead of the FORMAT arrays, counted as it comes back)
+    const double bytes_per_site = (double)N * ((want_dp ? 4.0 : 0.0) + (dtext ? 0.0 : 4.0 * G * ((a.add_gl ? 1 : 0) + (a.add_pl ? 1 : 0) + (a.add_gp ? 1 : 0)) +
+                                               4.0 * A * ((a.add_fmt_ad ? 1 : 0) + (a.add_fmt_adf ? 1 : 0) + (a.add_fmt_adr ? 1 : 0)))) + 64.0;
     std::vector<std::unique_ptr<Worker>> workers(D);
     for (int d = 0; d < D; d++) {
         workers[d].reset(new Worker());
         Worker* W = workers[d].get();
         vgl_ctx* ctx = ctxs[d];
-        W->th = std::thread([W, ctx, &now]() {
+        W->th = std::thread([W, ctx, &now, dtext]() {
             // a tile is submitted (vgl_simulate_tile_async) before the previous one is waited for: its kernels run while the
             // previous tile's tags are still on their way to the host
             TileBufs* prev = nullptr; int32_t prev_ticket = 0;
@@ -1047,9 +1068,12 @@ int main(int argc, char** argv) {
                 }
                 int32_t ticket = 0;
                 if (B && W->t_first < 0.0) W->t_first = now();
-                if (B && vgl_simulate_tile_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, &ticket) != VGL_OK) die("%s", vgl_last_error());
+                if (B && !dtext && vgl_simulate_tile_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, &ticket) != VGL_OK) die("%s", vgl_last_error());
+                if (B && dtext && vgl_simulate_tile_text_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, B->text.data(), B->text_cap, B->toff.data(), &ticket) != VGL_OK)
+                    die("%s", vgl_last_error());
                 if (prev) {
                     if (vgl_tile_wait(ctx, prev_ticket) != VGL_OK) die("%s", vgl_last_error());
+                    if (dtext) W->text_bytes += (double)prev->toff[prev->ns];
                     W->tiles += 1; W->sites += prev->ns; W->t_last = now();
                     { std::lock_guard<std::mutex> lk(prev->m); prev->done = true; }
                     prev->cv.notify_all();
@@ -1094,6 +1118,7 @@ int main(int argc, char** argv) {
         // the slab of site i holds the record's array as the reference keeps it for bcf_update_format_*(), element k of sample s
         // at slab[s * n + k] with the site's own n -- the encoders below read (and for BCF copy) it front to back
         fmt.clear();
+        if (dtext) return;                                       // the sample columns come from the device
         const size_t sN = (size_t)N, sG = (size_t)nG, sA = (size_t)nA;
         if (a.add_fmt_dp) fmt.push_back({"DP", false, 1, &B.dp[(size_t)i * N], 1, sN});
         if (a.add_gl) fmt.push_back({"GL", true, nG, &B.gl[(size_t)i * G * N], sG, 1});
@@ -1168,10 +1193,15 @@ int main(int argc, char** argv) {
                 if (B.st[i] < 0) return;
                 std::string sh; std::vector<std::string> al; std::vector<vsink::FmtDesc> fmt;
                 build_record(B, i, sh, al, fmt);
+                if (dtext) { enc[i] = std::move(sh); return; }
                 out.encode_rec(sh, fmt, enc[i]);
             });
             lap(4);
-            for (int i = 0; i < ns; i++) if (B.st[i] >= 0) { out.put(enc[i]); n_out++; }
+            for (int i = 0; i < ns; i++) if (B.st[i] >= 0) {
+                out.put(enc[i]);
+                if (dtext) out.put(B.text.data() + B.toff[i], (size_t)(B.toff[i + 1] - B.toff[i]));     // tab, FORMAT, the sample columns, newline
+                n_out++;
+            }
             lap(5);
         }
     };
@@ -1224,7 +1254,7 @@ int main(int argc, char** argv) {
             const Worker& W = *workers[d];
             vgl_ctx_info_t ci; memset(&ci, 0, sizeof ci); ci.size = (int32_t)sizeof ci;
             (void)vgl_ctx_info(ctxs[d], &ci);
-            const double dt = W.t_last - W.t_first, gb = bytes_per_site * (double)W.sites / 1e9;
+            const double dt = W.t_last - W.t_first, gb = (bytes_per_site * (double)W.sites + W.text_bytes) / 1e9;
             fprintf(stderr, "[device %d] %ld tiles, %ld sites, %.3f GB of tags copied back in %.3f s = %.1f GB/s, %.3g evaluations/s; context: %.2f GB workspace, k_sample build %d, fused %d (split %d)\n",
                     devices[d], W.tiles, W.sites, gb, dt > 0 ? dt : 0.0, dt > 0 ? gb / dt : 0.0, dt > 0 ? (double)W.sites * N / dt : 0.0,
                     (double)ci.workspace_bytes / 1e9, ci.sample_lean, ci.fused, ci.fused_split);

@@ -217,7 +217,13 @@ struct vgl_ctx {
         hipEvent_t ev_kernels = nullptr, ev_copied = nullptr;
         bool busy = false; int rc = VGL_OK;
         int64_t site0 = 0; int32_t n_sites = 0; vgl_tile_out o;     // the tile in flight (vgl_tile_wait may run it again through `deep`)
+        // vgl_simulate_tile_text_async: the FORMAT tags formatted on the device (vgl_text.hip); the text is copied back by vgl_tile_wait,
+        // which knows its size
+        bool text = false; uint8_t* h_text = nullptr; int64_t text_cap = 0; int64_t* h_toff = nullptr;
+        uint32_t dev_fields = 0;                                    // fields of d_out the tile's kernels wrote (bit f: FIELDS[f])
+        uint8_t* d_text = nullptr; int64_t d_text_bytes = 0; int64_t* d_toff = nullptr; void* d_tws = nullptr; int64_t d_tws_bytes = 0;
     } slot[2];
+    hipStream_t s_text = nullptr;                                   // text copies of vgl_tile_wait (never behind the next tile's copies)
     // a draw deeper than the staging capacity (vcfgl grows its read buffers, bcf_utils.cpp:618-648): the host entry points run such a tile again on
     // this sibling context, created on first need with the staging layout's largest capacity (VGL_READ_CAP_MAX reads) and tiles of at most
     // VGL_DEEP_TILE_SITES sites.  VGL_RNG_TILE only (a value depends on (seed, site, sample) alone, so the second run is the same tile)
@@ -344,7 +350,7 @@ extern "C" int vgl_ctx_destroy(vgl_ctx* c) {
     for (auto& S : c->slot) {
         if (S.busy && S.ev_copied) (void)hipEventSynchronize(S.ev_copied);
         for (void* q : S.d_out) if (q) (void)hipFree(q);
-        void* dq[] = {S.d_gt, S.d_reads_out, S.d_errp_out, S.d_pick_out};
+        void* dq[] = {S.d_gt, S.d_reads_out, S.d_errp_out, S.d_pick_out, S.d_text, S.d_toff, S.d_tws};
         for (void* q : dq) if (q) (void)hipFree(q);
         if (S.h_gt) (void)hipHostFree(S.h_gt);
         if (S.h_flag) (void)hipHostFree(S.h_flag);
@@ -353,6 +359,7 @@ extern "C" int vgl_ctx_destroy(vgl_ctx* c) {
     }
     if (c->s_compute) (void)hipStreamDestroy(c->s_compute);
     if (c->s_copy) (void)hipStreamDestroy(c->s_copy);
+    if (c->s_text) (void)hipStreamDestroy(c->s_text);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     delete c;
     return VGL_OK;
@@ -1090,6 +1097,39 @@ extern "C" void* vgl_host_alloc_on(int32_t device, size_t bytes) {
 }
 extern "C" void vgl_host_free(void* p) { if (p) (void)hipHostFree(p); }
 
+// The FORMAT tags vgl_simulate_tile_text_async formats, in add_tags()'s order (bcf_utils.cpp:426-507): DP, GL, PL, GP, AD, ADF, ADR.
+// Returns their count; fid[k] = index into FIELDS.
+static int text_fields(const vgl_ctx* c, vgl_text_field* tf, int* fid) {
+    struct T { int on; const char* key; int is_float; int count; int f; };
+    const T all[] = {{c->p.add_fmt_dp, "DP", 0, VGL_TEXT_ONE, 10}, {c->p.add_gl, "GL", 1, VGL_TEXT_PER_G, 11}, {c->p.add_pl, "PL", 0, VGL_TEXT_PER_G, 12},
+                     {c->p.add_gp, "GP", 1, VGL_TEXT_PER_G, 13}, {c->p.add_fmt_ad, "AD", 0, VGL_TEXT_PER_A, 14},
+                     {c->p.add_fmt_adf, "ADF", 0, VGL_TEXT_PER_A, 15}, {c->p.add_fmt_adr, "ADR", 0, VGL_TEXT_PER_A, 16}};
+    int n = 0;
+    for (const T& t : all) {
+        if (!t.on) continue;
+        tf[n].key = t.key; tf[n].is_float = t.is_float; tf[n].count = t.count; tf[n].base = nullptr;
+        tf[n].site_stride = (int64_t)field_count(c, FIELDS[t.f].kind, 1);
+        fid[n++] = t.f;
+    }
+    return n;
+}
+
+extern "C" int64_t vgl_ctx_text_bound(const vgl_ctx* c, int32_t n_sites) {
+    if (!c || n_sites < 0) return -1;
+    vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
+    const int nf = text_fields(c, tf, fid);
+    return vgl_text_bound(c->dp.n_samples, n_sites, tf, nf, (int32_t)c->dp.A);
+}
+
+// the formatter on the slot's device planes (compute stream): text into d_text, site offsets into d_toff
+static int enqueue_text(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites) {
+    vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
+    const int nf = text_fields(c, tf, fid);
+    for (int k = 0; k < nf; k++) tf[k].base = S.d_out[fid[k]];
+    return vgl_text_format_device(c->device, tf, nf, c->dp.n_samples, n_sites, (const int32_t*)S.d_out[0], (const int32_t*)S.d_out[1],
+                                  S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
+}
+
 // Host buffers in, host buffers out, asynchronously: the tile's kernels are enqueued on the context's compute stream, the copies of
 // its tags back to the host on its copy stream behind them; with two tiles in flight the copies of tile t overlap the kernels of
 // tile t + 1.  Destination buffers from vgl_host_alloc() (pinned) are written by DMA directly; pageable ones work, more slowly.
@@ -1100,9 +1140,18 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     HIPCHK(hipMemcpyAsync(S.d_gt, S.h_gt, (size_t)n_sites * N, hipMemcpyHostToDevice, c->s_compute));
     vgl_tile_out d;
     memset(&d, 0, sizeof d);
+    // text: the planes of the formatted tags are computed on the device whether or not the caller also wants them back
+    uint32_t text_mask = 0;
+    if (S.text) {
+        vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
+        const int nf = text_fields(c, tf, fid);
+        for (int k = 0; k < nf; k++) text_mask |= 1u << fid[k];
+    }
+    S.dev_fields = 0;
     for (int f = 0; f < N_FIELDS; f++) {
         void* host = *(void**)((char*)o + FIELDS[f].off);
-        if (!host) continue;
+        if (!host && !(text_mask >> f & 1u)) continue;
+        S.dev_fields |= 1u << f;
         const size_t need = field_count(c, FIELDS[f].kind, (size_t)c->max_sites) * FIELDS[f].esz;
         if (S.d_out_bytes[f] < need) {
             if (S.d_out[f]) (void)hipFree(S.d_out[f]);
@@ -1142,11 +1191,28 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
         HIPCHK(hipMemsetAsync(S.d_pick_out, 0xFF, (size_t)n_sites * sizeof(double), c->s_compute));
         d.site_pick_err = S.d_pick_out;
     }
+    if (S.text) {
+        const int64_t ws = vgl_text_workspace_bytes((int32_t)N, c->max_sites);
+        if (S.d_tws_bytes < ws) {
+            if (S.d_tws) (void)hipFree(S.d_tws);
+            S.d_tws = nullptr; S.d_tws_bytes = 0;
+            HIPCHK(hipMalloc(&S.d_tws, (size_t)ws));
+            S.d_tws_bytes = ws;
+        }
+        if (!S.d_toff) HIPCHK(hipMalloc((void**)&S.d_toff, sizeof(int64_t) * ((size_t)c->max_sites + 1)));
+        if (S.d_text_bytes < S.text_cap) {
+            if (S.d_text) (void)hipFree(S.d_text);
+            S.d_text = nullptr; S.d_text_bytes = 0;
+            HIPCHK(hipMalloc((void**)&S.d_text, (size_t)S.text_cap));
+            S.d_text_bytes = S.text_cap;
+        }
+    }
     int rc = vgl_simulate_tile_device(c, site0, n_sites, S.d_gt, &d, c->s_compute);
     if (rc) return rc;
     // this tile's device error flags, then a clean word for the next tile
     HIPCHK(hipMemcpyAsync(S.h_flag, c->d_errflag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute));
     HIPCHK(hipMemsetAsync(c->d_errflag, 0, sizeof(uint32_t), c->s_compute));
+    if (S.text && (rc = enqueue_text(c, S, n_sites)) != VGL_OK) return rc;
     HIPCHK(hipEventRecord(S.ev_kernels, c->s_compute));
     HIPCHK(hipStreamWaitEvent(c->s_copy, S.ev_kernels, 0));
     for (int f = 0; f < N_FIELDS; f++) {
@@ -1157,6 +1223,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     if (d.reads) HIPCHK(hipMemcpyAsync(o->reads, d.reads, (size_t)o->read_capacity * n_sites * N, hipMemcpyDeviceToHost, c->s_copy));
     if (d.read_errp && c->dp.error_qs == 2) HIPCHK(hipMemcpyAsync(o->read_errp, d.read_errp, (size_t)o->read_capacity * n_sites * N * sizeof(double), hipMemcpyDeviceToHost, c->s_copy));
     if (d.site_pick_err) HIPCHK(hipMemcpyAsync(o->site_pick_err, d.site_pick_err, (size_t)n_sites * sizeof(double), hipMemcpyDeviceToHost, c->s_copy));
+    if (S.text) HIPCHK(hipMemcpyAsync(S.h_toff, S.d_toff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, c->s_copy));
     HIPCHK(hipEventRecord(S.ev_copied, c->s_copy));
     return VGL_OK;
 }
@@ -1167,8 +1234,11 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
 // The ticket and the slot are committed only when everything is enqueued: after a failure part-way the streams are drained, the
 // sticky device error word is cleared and the slot is free again -- no later tile inherits this one's flags or shares its buffers
 // with work still in flight.
-extern "C" int vgl_simulate_tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o, int32_t* ticket) {
+static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o, int32_t* ticket,
+                      uint8_t* text, int64_t text_cap, int64_t* toff, bool want_text) {
     if (!c || !o || !ticket) return fail(VGL_E_ARG, "null argument");
+    if (want_text && (!toff || text_cap < 0 || (text_cap > 0 && !text))) return fail(VGL_E_ARG, "vgl_simulate_tile_text_async: null text or offsets");
+    if (want_text && c->p.out_layout != VGL_LAYOUT_SAMPLE_MAJOR) return fail(VGL_E_ARG, "vgl_simulate_tile_text_async: the context needs out_layout = VGL_LAYOUT_SAMPLE_MAJOR");
     if (n_sites < 0 || n_sites > c->max_sites) return fail(VGL_E_ARG, "n_sites %d exceeds max_sites_per_tile %d", n_sites, c->max_sites);
     if (n_sites > 0 && !gt) return fail(VGL_E_ARG, "null gt");
     HIPCHK(hipSetDevice(c->device));
@@ -1183,7 +1253,9 @@ extern "C" int vgl_simulate_tile_async(vgl_ctx* c, int64_t site0, int32_t n_site
     if (!S.h_flag) HIPCHK(hipHostMalloc((void**)&S.h_flag, sizeof(uint32_t), hipHostMallocDefault));
     S.rc = VGL_OK; *S.h_flag = 0;
     S.site0 = site0; S.n_sites = n_sites; S.o = *o;
-    if (n_sites == 0) HIPCHK(hipEventRecord(S.ev_copied, c->s_copy));
+    S.text = want_text; S.h_text = text; S.text_cap = text_cap; S.h_toff = toff;
+    if (want_text && !c->s_text) HIPCHK(hipStreamCreateWithFlags(&c->s_text, hipStreamNonBlocking));
+    if (n_sites == 0) { if (want_text) toff[0] = 0; HIPCHK(hipEventRecord(S.ev_copied, c->s_copy)); }
     else {
         const int rc = enqueue_host_tile(c, S, site0, n_sites, gt, o);
         if (rc != VGL_OK) {
@@ -1201,11 +1273,20 @@ extern "C" int vgl_simulate_tile_async(vgl_ctx* c, int64_t site0, int32_t n_site
     return VGL_OK;
 }
 
+extern "C" int vgl_simulate_tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o, int32_t* ticket) {
+    return tile_async(c, site0, n_sites, gt, o, ticket, nullptr, 0, nullptr, false);
+}
+
+extern "C" int vgl_simulate_tile_text_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o,
+                                            uint8_t* text, int64_t text_cap, int64_t* offsets, int32_t* ticket) {
+    return tile_async(c, site0, n_sites, gt, o, ticket, text, text_cap, offsets, true);
+}
+
 // A tile whose device flags report a draw deeper than the staging capacity, run again through the sibling context (host buffers: the slot's own copy of
 // the genotypes, the caller's output arrays), VGL_DEEP_TILE_SITES sites at a time -- every tag array of a tile is site-major, so a sub-tile is a slice of
 // it.  Returns VGL_E_CAPACITY (quietly) where that cannot be done: serial mode (the streams have moved on), a per-read dump (read-major planes of the
 // caller's own capacity), a capacity already at the layout's maximum, or no memory for the sibling.
-static int deep_rerun(vgl_ctx* c, vgl_ctx::HostSlot& S) {
+static int deep_ctx(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     const VglDevParams& D = c->dp;
     if (D.serial || D.read_cap >= VGL_READ_CAP_MAX || (S.o.read_capacity > 0 && (S.o.reads || S.o.read_errp))) return VGL_E_CAPACITY;
     if (!c->deep) {
@@ -1218,7 +1299,11 @@ static int deep_rerun(vgl_ctx* c, vgl_ctx::HostSlot& S) {
         const int rc = ctx_create_cap(&p, c->device, c->max_sites < VGL_DEEP_TILE_SITES ? c->max_sites : VGL_DEEP_TILE_SITES, &c->deep, VGL_READ_CAP_MAX);
         if (rc != VGL_OK) { c->deep = nullptr; memcpy(g_err, keep, sizeof keep); return VGL_E_CAPACITY; }
     }
-    const size_t N = (size_t)D.n_samples;
+    return VGL_OK;
+}
+static int deep_rerun(vgl_ctx* c, vgl_ctx::HostSlot& S) {
+    if (deep_ctx(c, S) != VGL_OK) return VGL_E_CAPACITY;
+    const size_t N = (size_t)c->dp.n_samples;
     for (int32_t k = 0; k < S.n_sites; k += c->deep->max_sites) {
         const int32_t n = (S.n_sites - k < c->deep->max_sites) ? (S.n_sites - k) : c->deep->max_sites;
         vgl_tile_out o = S.o;
@@ -1233,6 +1318,34 @@ static int deep_rerun(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     c->deep_runs++;
     return VGL_OK;
 }
+// The same for a text tile: the sibling runs the sub-tiles into the slot's own device planes (the genotypes are still in S.d_gt), then
+// the whole tile is formatted again and its per-site arrays and offsets copied again (compute stream, synchronously: a rare path).
+static int deep_rerun_text(vgl_ctx* c, vgl_ctx::HostSlot& S) {
+    if (deep_ctx(c, S) != VGL_OK) return VGL_E_CAPACITY;
+    const size_t N = (size_t)c->dp.n_samples;
+    for (int32_t k = 0; k < S.n_sites; k += c->deep->max_sites) {
+        const int32_t n = (S.n_sites - k < c->deep->max_sites) ? (S.n_sites - k) : c->deep->max_sites;
+        vgl_tile_out d;
+        memset(&d, 0, sizeof d);
+        for (int f = 0; f < N_FIELDS; f++)
+            if (S.dev_fields >> f & 1u) *(char**)((char*)&d + FIELDS[f].off) = (char*)S.d_out[f] + field_count(c, FIELDS[f].kind, (size_t)k) * FIELDS[f].esz;
+        if (S.o.site_pick_err && S.d_pick_out) d.site_pick_err = S.d_pick_out + k;
+        int rc = vgl_simulate_tile_device(c->deep, S.site0 + k, n, S.d_gt + (size_t)k * N, &d, c->s_compute);
+        if (rc == VGL_OK) rc = vgl_ctx_check(c->deep, c->s_compute);
+        if (rc != VGL_OK) return rc;                                 // (a draw beyond VGL_READ_CAP_MAX reads: VGL_E_CAPACITY after all)
+    }
+    const int rc = enqueue_text(c, S, S.n_sites);
+    if (rc != VGL_OK) return rc;
+    for (int f = 0; f < N_FIELDS; f++) {
+        void* host = *(void**)((char*)&S.o + FIELDS[f].off);
+        if (host) HIPCHK(hipMemcpyAsync(host, S.d_out[f], field_count(c, FIELDS[f].kind, (size_t)S.n_sites) * FIELDS[f].esz, hipMemcpyDeviceToHost, c->s_compute));
+    }
+    if (S.o.site_pick_err && S.d_pick_out) HIPCHK(hipMemcpyAsync(S.o.site_pick_err, S.d_pick_out, (size_t)S.n_sites * sizeof(double), hipMemcpyDeviceToHost, c->s_compute));
+    HIPCHK(hipMemcpyAsync(S.h_toff, S.d_toff, sizeof(int64_t) * ((size_t)S.n_sites + 1), hipMemcpyDeviceToHost, c->s_compute));
+    HIPCHK(hipStreamSynchronize(c->s_compute));
+    c->deep_runs++;
+    return VGL_OK;
+}
 
 extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
     if (!c || ticket < 0 || ticket > 1) return fail(VGL_E_ARG, "bad ticket");
@@ -1242,10 +1355,23 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
     HIPCHK(hipEventSynchronize(S.ev_copied));
     S.busy = false;
     if ((*S.h_flag & VGL_DEVERR_CAPACITY) && S.n_sites > 0) {
-        const int rc = deep_rerun(c, S);
-        if (rc != VGL_E_CAPACITY) return rc;                         // done (or failed for another reason, reported as such)
+        const int rc = S.text ? deep_rerun_text(c, S) : deep_rerun(c, S);
+        if (rc != VGL_E_CAPACITY && (rc != VGL_OK || !S.text)) return rc;      // done (or failed for another reason, reported as such)
+        if (rc == VGL_E_CAPACITY) return flags_to_rc(c, *S.h_flag);
+    } else {
+        const int rc = flags_to_rc(c, *S.h_flag);
+        if (rc != VGL_OK || !S.text) return rc;
     }
-    return flags_to_rc(c, *S.h_flag);
+    // text: only the bytes the tile produced cross the link
+    const int64_t total = S.h_toff[S.n_sites];
+    if (total < 0 || total > S.text_cap)
+        return fail(VGL_E_CAPACITY, "the tile's text needs %lld bytes, text_cap is %lld (offsets[n_sites] holds the size; vgl_ctx_text_bound bounds it)",
+                    (long long)total, (long long)S.text_cap);
+    if (total > 0) {
+        HIPCHK(hipMemcpyAsync(S.h_text, S.d_text, (size_t)total, hipMemcpyDeviceToHost, c->s_text));
+        HIPCHK(hipStreamSynchronize(c->s_text));
+    }
+    return VGL_OK;
 }
 
 extern "C" int vgl_simulate_tile(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o) {
