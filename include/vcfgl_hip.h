@@ -440,6 +440,91 @@ VGL_API int64_t vgl_ctx_text_bound(const vgl_ctx* ctx, int32_t n_sites);
 VGL_API int vgl_simulate_tile_text_async(vgl_ctx* ctx, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* out,
                                          uint8_t* text, int64_t text_cap, int64_t* offsets, int32_t* ticket);
 
+/* ---- gVCF blocks on the device (ABI 7, additive) ------------------------------------------------------------------------------
+ * The block machine of the host writer (prepare_gvcf_block) over one tile, as rules on neighbouring kept sites (site_status >= 0;
+ * skipped sites are passed over).  r(i) = the index of the first --gvcf-dps threshold above the site's smallest per-sample DP (the
+ * number of thresholds when none is).  A kept site is BLOCKABLE when n_alleles_obs == 1 and r > 0; it CONTINUES the block of the
+ * previous kept site when that site is blockable, on the same contig, pos0 <= its pos0 + 1, with the same r; a blockable site that
+ * does not continue FOUNDS a block; any other kept site is a RECORD.  A block's aggregates: per sample the minimum DP and the
+ * lexicographically smallest (PL[1], PL[2]) compared as signed int32; PL[0] (and, for the caller, alleles and QS) of the founder;
+ * MIN_DP = the smallest DP of all members.  A site that joins a block while it or the founder has n_alleles != 2 is the host's fatal
+ * "Unexpected number of PL values": the first such site is reported.  A one-site block whose founder has n_alleles != 2 keeps the
+ * founder's nG PL values per sample.
+ *   vgl_gvcf_item             one item of the tile's ordered output: a record (first = last = founder = the site, block = -1) or a
+ *                             block (first / last member, founder = first, dpr = r, min_dp = MIN_DP, block = index of its aggregates)
+ *   vgl_gvcf_workspace_bytes  device workspace of a call (pure host arithmetic).
+ *   vgl_gvcf_blocks_device    `in` and `out` arrays and the workspace are device memory of `device`; work is enqueued on `hip_stream`
+ *                             without synchronising.  dp[i * dp_site_stride + s], pl[i * pl_site_stride + s * nG(i) + g]: the
+ *                             VGL_LAYOUT_SAMPLE_MAJOR slabs (pl_site_stride >= n_samples * nG of every founder).  Out: items[0 ..
+ *                             n_items), counts = {n_items, n_blocks, first error site or -1, 0}; block b's DP slab at block_dp[b *
+ *                             n_samples], its PL slab at block_pl[b * pl_site_stride] (founder's nG values per sample), its founder's
+ *                             n_alleles in block_n_alleles[b]; block_status[b] = 0 for b < n_blocks, -1 up to n_sites;
+ *                             record_status[i] = site_status[i] for records, -1 for block members and skipped sites.  With the
+ *                             fields {"PL", VGL_TEXT_PER_G, block_pl, pl_site_stride}, {"DP", VGL_TEXT_ONE, block_dp, n_samples},
+ *                             block_status and block_n_alleles, vgl_text_format_device writes each block's sample columns
+ *                             ("\tPL:DP" ("\t" PL ":" DP)* "\n"); with record_status, the records' columns.
+ *   vgl_ctx_gvcf_text_bound   the text_cap that always suffices for vgl_simulate_tile_gvcf_async on n_sites sites (host arithmetic).
+ *   vgl_simulate_tile_gvcf_async
+ *                             vgl_simulate_tile_async of a -doGVCF 1 record loop (a context with out_layout = VGL_LAYOUT_SAMPLE_MAJOR,
+ *                             add_fmt_dp and add_pl; VGL_E_ARG otherwise): contig (int32) and pos0 (int64) per site and the thresholds
+ *                             dps[n_dps] are host arrays; the tile is blocked and its record and block columns formatted on the device.
+ *                             The per-site arrays of `out` are copied as by vgl_simulate_tile_async (its per-sample FORMAT pointers
+ *                             may be NULL: PL and GL then stay on the device).  vgl_tile_wait completes it, filling `g`: n_items,
+ *                             n_blocks, error_site (tile index or -1), items [n_items]; record site i's text at text[record_offsets[i]
+ *                             .. record_offsets[i + 1]) (empty for members and skipped sites), block b's at text[block_offsets[b] ..
+ *                             block_offsets[b + 1]) (behind the record text, block_offsets[0] = record_offsets[n_sites]); first_dp [N],
+ *                             first_pl [n_samples * max genotypes] and last_dp / last_pl: the aggregates of block 0 and block
+ *                             n_blocks - 1 (to stitch blocks across tiles).  A tile that drew deeper than the staging capacity is run,
+ *                             blocked and formatted again; a text larger than text_cap gives VGL_E_CAPACITY and text_needed = its
+ *                             size, nothing is written to `text`.  `g` and its arrays must live until vgl_tile_wait returns. */
+#define VGL_GVCF_RECORD 0
+#define VGL_GVCF_BLOCK  1
+typedef struct vgl_gvcf_item {
+    int32_t kind;             /* VGL_GVCF_RECORD / VGL_GVCF_BLOCK                */
+    int32_t first, last;      /* tile indices of the first and last member       */
+    int32_t founder;          /* tile index of the founding site (= first)       */
+    int32_t dpr;              /* the block's r (0 for a record)                  */
+    int32_t min_dp;           /* MIN_DP (a record: its smallest per-sample DP)   */
+    int32_t block;            /* index of the block's aggregates, -1: a record   */
+    int32_t reserved;
+} vgl_gvcf_item;
+typedef struct vgl_gvcf_in {
+    const int32_t* site_status;
+    const int32_t* n_alleles_obs;
+    const int32_t* n_alleles;
+    const int32_t* contig;        /* any int32 id, equal for sites of one contig    */
+    const int64_t* pos0;
+    const int32_t* dp;   int64_t dp_site_stride;
+    const int32_t* pl;   int64_t pl_site_stride;
+    const int32_t* dps;  int32_t n_dps;   /* the --gvcf-dps thresholds (device memory) */
+    int32_t reserved;
+} vgl_gvcf_in;
+typedef struct vgl_gvcf_out {
+    vgl_gvcf_item* items;         /* [n_sites]                                        */
+    int32_t* counts;              /* [4]                                              */
+    int32_t* block_dp;            /* [n_sites * n_samples]                            */
+    int32_t* block_pl;            /* [n_sites * pl_site_stride]                       */
+    int32_t* block_n_alleles;     /* [n_sites]                                        */
+    int32_t* block_status;        /* [n_sites]                                        */
+    int32_t* record_status;       /* [n_sites]                                        */
+} vgl_gvcf_out;
+typedef struct vgl_gvcf_tile {     /* host memory */
+    vgl_gvcf_item* items;         /* [n_sites]                                        */
+    uint8_t* text; int64_t text_cap;
+    int64_t* record_offsets;      /* [n_sites + 1]                                    */
+    int64_t* block_offsets;       /* [n_sites + 1]                                    */
+    int32_t* first_dp; int32_t* first_pl; int32_t* last_dp; int32_t* last_pl;
+    int32_t n_items, n_blocks, error_site, reserved;    /* written by vgl_tile_wait   */
+    int64_t text_needed;                                /* written by vgl_tile_wait   */
+} vgl_gvcf_tile;
+VGL_API int64_t vgl_gvcf_workspace_bytes(int32_t n_samples, int32_t n_sites);
+VGL_API int vgl_gvcf_blocks_device(int32_t device, int32_t n_samples, int32_t n_sites, const vgl_gvcf_in* in, const vgl_gvcf_out* out,
+                                   void* workspace, int64_t workspace_bytes, void* hip_stream);
+VGL_API int64_t vgl_ctx_gvcf_text_bound(const vgl_ctx* ctx, int32_t n_sites);
+VGL_API int vgl_simulate_tile_gvcf_async(vgl_ctx* ctx, int64_t site0, int32_t n_sites, const uint8_t* gt, const int32_t* contig,
+                                         const int64_t* pos0, const int32_t* dps, int32_t n_dps, vgl_tile_out* out, vgl_gvcf_tile* g,
+                                         int32_t* ticket);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,7 @@ EXPORTS = [
     "vgl_bgzf_bound", "vgl_bgzf_workspace_bytes", "vgl_bgzf_compress_device",
     "vgl_bgzf_host_create", "vgl_bgzf_host_submit", "vgl_bgzf_host_wait", "vgl_bgzf_host_destroy",
     "vgl_text_bound", "vgl_text_workspace_bytes", "vgl_text_format_device", "vgl_ctx_text_bound", "vgl_simulate_tile_text_async",
+    "vgl_gvcf_workspace_bytes", "vgl_gvcf_blocks_device", "vgl_ctx_gvcf_text_bound", "vgl_simulate_tile_gvcf_async",
 ]
 VGL_PACK_ROW, VGL_PACK_ROWS_G, VGL_PACK_ROWS_A = 0, 1, 2
 
@@ -107,6 +108,32 @@ VGL_TEXT_MAX_FIELDS = 8
 
 class TextField(C.Structure):
     _fields_ = [("key", C.c_char_p), ("is_float", C.c_int32), ("count", C.c_int32), ("base", C.c_void_p), ("site_stride", C.c_int64)]
+
+
+VGL_GVCF_RECORD, VGL_GVCF_BLOCK = 0, 1
+
+
+class GvcfItem(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("first", C.c_int32), ("last", C.c_int32), ("founder", C.c_int32), ("dpr", C.c_int32),
+                ("min_dp", C.c_int32), ("block", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GvcfIn(C.Structure):
+    _fields_ = [("site_status", C.c_void_p), ("n_alleles_obs", C.c_void_p), ("n_alleles", C.c_void_p), ("contig", C.c_void_p),
+                ("pos0", C.c_void_p), ("dp", C.c_void_p), ("dp_site_stride", C.c_int64), ("pl", C.c_void_p), ("pl_site_stride", C.c_int64),
+                ("dps", C.c_void_p), ("n_dps", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GvcfOut(C.Structure):
+    _fields_ = [("items", C.c_void_p), ("counts", C.c_void_p), ("block_dp", C.c_void_p), ("block_pl", C.c_void_p),
+                ("block_n_alleles", C.c_void_p), ("block_status", C.c_void_p), ("record_status", C.c_void_p)]
+
+
+class GvcfTile(C.Structure):
+    _fields_ = [("items", C.c_void_p), ("text", C.c_void_p), ("text_cap", C.c_int64), ("record_offsets", C.c_void_p),
+                ("block_offsets", C.c_void_p), ("first_dp", C.c_void_p), ("first_pl", C.c_void_p), ("last_dp", C.c_void_p),
+                ("last_pl", C.c_void_p), ("n_items", C.c_int32), ("n_blocks", C.c_int32), ("error_site", C.c_int32),
+                ("reserved", C.c_int32), ("text_needed", C.c_int64)]
 
 
 class PackPlan(C.Structure):
@@ -187,6 +214,14 @@ def load_library(hooks=False):
     lib.vgl_ctx_text_bound.argtypes = [C.c_void_p, C.c_int32]
     lib.vgl_simulate_tile_text_async.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(TileOut), C.c_void_p, C.c_int64,
                                                  C.c_void_p, C.POINTER(C.c_int32)]
+    lib.vgl_gvcf_workspace_bytes.restype = C.c_int64
+    lib.vgl_gvcf_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.vgl_gvcf_blocks_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(GvcfIn), C.POINTER(GvcfOut), C.c_void_p, C.c_int64,
+                                           C.c_void_p]
+    lib.vgl_ctx_gvcf_text_bound.restype = C.c_int64
+    lib.vgl_ctx_gvcf_text_bound.argtypes = [C.c_void_p, C.c_int32]
+    lib.vgl_simulate_tile_gvcf_async.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                 C.POINTER(TileOut), C.POINTER(GvcfTile), C.POINTER(C.c_int32)]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

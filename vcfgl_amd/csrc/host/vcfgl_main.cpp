@@ -61,6 +61,7 @@ struct Args {
     bool threads_given = false;
     int device_bgzf = 0;               // --device-bgzf 1: BGZF streams compressed on the first device of the run
     int device_text = 0;               // --device-text 1: the sample columns of VCF text records formatted on the device
+    int device_gvcf = 0;               // --device-gvcf 1: -doGVCF 1 blocks built and their / the records' sample columns formatted on the device
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -98,6 +99,9 @@ static const char USAGE[] =
     "                   --device-text 0|1 [0: the sample columns of -O v / -O z records formatted on the host; 1: on the device that\n"
     "                   simulated the tile, and the text crosses the link instead of the FORMAT arrays.  Same bytes either way; needs -O v\n"
     "                   or -O z, refused with -doGVCF 1 and --depth inf; a run without a GPU fails instead of falling back]\n"
+    "                   --device-gvcf 0|1 [0: -doGVCF 1 blocks built on the host, site by site; 1: on the device that simulated the tile,\n"
+    "                   with the sample columns of records and blocks formatted there (blocks that cross a tile are merged on the host).\n"
+    "                   Same bytes either way; needs -doGVCF 1 and -O v or -O z, refused with --depth inf; a run without a GPU fails]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 static Args parse_args(int argc, char** argv) {
@@ -176,6 +180,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--device") a.device = I(v);
         else if (f == "--device-bgzf") a.device_bgzf = I(v);
         else if (f == "--device-text") a.device_text = I(v);
+        else if (f == "--device-gvcf") a.device_gvcf = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -184,6 +189,7 @@ static Args parse_args(int argc, char** argv) {
     if (a.in_fn.empty()) die("Input file is not specified. Please use -i/--input option to specify the input file.");
     if (!a.have_depth && a.depths_fn.empty()) die("Average per-site read depth value is required. Please set it using --depth or --depths-file and re-run.");
     if (a.depths_fn.empty()) range(a.depth, 0.0, 500.0, "--depth");
+    if (a.device_gvcf == 1 && a.depth_inf) die("--device-gvcf 1 is not supported with --depth inf (no tile is simulated).");
     if (a.depth_inf) {                                                          // io.cpp:781-850, 1011-1018
         if (a.rm_invar & 4) die("[--rm-invar-sites %d] Cannot skip invariable sites when --depth inf is set.", a.rm_invar);
         if (a.do_gvcf) die("[-doGVCF 1] Cannot output gVCF when --depth inf is set.");
@@ -229,8 +235,13 @@ static Args parse_args(int argc, char** argv) {
     range(a.device_text, 0, 1, "--device-text");
     if (a.device_text) {                                        // (checked before any GPU work: nothing is written)
         if (a.output_mode != "v" && a.output_mode != "z") die("--device-text 1 formats VCF text: it needs -O v or -O z (found -O %s).", a.output_mode.c_str());
-        if (a.do_gvcf) die("--device-text 1 is not supported with -doGVCF 1 (the gVCF blocker reads the FORMAT arrays of every site on the host).");
+        if (a.do_gvcf) die("--device-text 1 is not supported with -doGVCF 1 (the gVCF blocker reads the FORMAT arrays of every site on the host); use --device-gvcf 1.");
         if (a.depth_inf) die("--device-text 1 is not supported with --depth inf (no tile is simulated).");
+    }
+    range(a.device_gvcf, 0, 1, "--device-gvcf");
+    if (a.device_gvcf) {                                        // (checked before any GPU work: nothing is written)
+        if (!a.do_gvcf) die("--device-gvcf 1 builds gVCF blocks: it needs -doGVCF 1.");
+        if (a.output_mode != "v" && a.output_mode != "z") die("--device-gvcf 1 writes gVCF text: it needs -O v or -O z (found -O %s).", a.output_mode.c_str());
     }
     if (a.seed == -1) { a.seed = (int)time(NULL); fprintf(stderr, "\n-> No seed was given. Setting the random seed to the randomly chosen value: %d\n", a.seed); }
     if (a.beta_sampler < 0) a.beta_sampler = (a.rng_mode == VGL_RNG_SERIAL) ? VGL_BETA_STD : VGL_BETA_RAND48;
@@ -726,16 +737,23 @@ struct GvcfBlocker {
         return NO_WRITE;
     }
 
-    void emit(vsink::Sink& out, int N) {
+    // the eight fixed columns of a block record (also --device-gvcf 1, whose blocks carry their sample columns from the device)
+    static void fixed_columns(std::string& line, const vsink::Sink& out, const std::string& chrom, long start_pos, long end_pos,
+                              const std::string& alleles, int32_t min_dp, const float* qs, size_t n_qs) {
         const long end1 = end_pos + 1;                                    // 0-based -> 1-based
-        std::string line = chrom;
+        line += chrom;
         char hb[64]; snprintf(hb, sizeof hb, "\t%ld\t.\t", start_pos + 1); line += hb;
         const size_t c = alleles.find(',');
         line += alleles.substr(0, c); line += '\t'; line += (c == std::string::npos) ? "." : alleles.substr(c + 1);
         line += "\t.\t.\t";
         if (end1 - start_pos >= 2) { snprintf(hb, sizeof hb, "END=%ld;", end1); line += hb; }
         snprintf(hb, sizeof hb, "MIN_DP=%d", min_dp); line += hb;
-        if (!qsum.empty()) { line += ";QS="; for (size_t k = 0; k < qsum.size(); k++) { if (k) line += ','; out.put_float(line, qsum[k]); } }
+        if (n_qs) { line += ";QS="; for (size_t k = 0; k < n_qs; k++) { if (k) line += ','; out.put_float(line, qs[k]); } }
+    }
+
+    void emit(vsink::Sink& out, int N) {
+        std::string line;
+        fixed_columns(line, out, chrom, start_pos, end_pos, alleles, min_dp, qsum.data(), qsum.size());
         line += "\tPL:DP";
         const size_t nG = pl.size() / (size_t)N;
         for (int s = 0; s < N; ++s) {
@@ -990,7 +1008,9 @@ int main(int argc, char** argv) {
     // ---- tile buffers (host side of vgl_tile_out): only what this run prints is requested from the device
     // --device-text 1: the FORMAT arrays stay on the device (formatted there), DP comes back only for the pileup / per-read listings
     const bool dtext = a.device_text != 0;
-    const bool want_dp = (a.add_fmt_dp && !dtext) || a.do_gvcf || pile_fp || dump_reads;
+    // --device-gvcf 1: the same for -doGVCF 1; the blocks are built on the device, the FORMAT arrays stay there
+    const bool dgvcf = a.device_gvcf != 0;
+    const bool want_dp = (a.add_fmt_dp && !dtext && !dgvcf) || (a.do_gvcf && !dgvcf) || pile_fp || dump_reads;
     struct TileBufs {
         int ns = 0; int64_t t0 = 0; int dev = 0;
         std::vector<SiteMeta> meta; std::vector<uint8_t> gt;
@@ -999,6 +1019,9 @@ int main(int argc, char** argv) {
         PBuf<int32_t> st, na, nobs, idp, iad, iadf, iadr, dp, pl, ad, adf, adr;
         PBuf<int8_t> a2b; PBuf<float> qs, i16, gl, gp; PBuf<double> errp, pick;
         PBuf<uint8_t> text; PBuf<int64_t> toff; int64_t text_cap = 0;      // --device-text 1: the tile's sample columns and site offsets
+        // --device-gvcf 1: contig id and position per site (in), the items, block offsets and the first / last block's aggregates (out)
+        std::vector<int32_t> contig; std::vector<int64_t> pos0;
+        PBuf<int32_t> gitems, fdp, fpl, ldp, lpl; PBuf<int64_t> boff; vgl_gvcf_tile g;
         vgl_tile_out o;
         std::mutex m; std::condition_variable cv; bool done = false;
     };
@@ -1034,6 +1057,19 @@ int main(int argc, char** argv) {
             B.text.resize((size_t)std::max<int64_t>(B.text_cap, 1)); B.toff.resize((size_t)TS + 1);
             return;
         }
+        if (dgvcf) {
+            B.text_cap = vgl_ctx_gvcf_text_bound(ctxs[ri % (size_t)D], TS);
+            if (B.text_cap < 0) die("--device-gvcf 1: %s", vgl_last_error());
+            B.text.resize((size_t)std::max<int64_t>(B.text_cap, 1)); B.toff.resize((size_t)TS + 1); B.boff.resize((size_t)TS + 1);
+            B.gitems.resize((size_t)TS * (sizeof(vgl_gvcf_item) / sizeof(int32_t)));
+            B.fdp.resize(N); B.ldp.resize(N); B.fpl.resize((size_t)G * N); B.lpl.resize((size_t)G * N);
+            B.contig.resize(TS); B.pos0.resize(TS);
+            memset(&B.g, 0, sizeof B.g);
+            B.g.items = (vgl_gvcf_item*)B.gitems.data(); B.g.text = B.text.data(); B.g.text_cap = B.text_cap;
+            B.g.record_offsets = B.toff.data(); B.g.block_offsets = B.boff.data();
+            B.g.first_dp = B.fdp.data(); B.g.first_pl = B.fpl.data(); B.g.last_dp = B.ldp.data(); B.g.last_pl = B.lpl.data();
+            return;
+        }
         if (a.add_gl) { B.gl.resize(E * G); B.o.gl = B.gl.data(); }
         if (a.add_pl) { B.pl.resize(E * G); B.o.pl = B.pl.data(); }
         if (a.add_gp) { B.gp.resize(E * G); B.o.gp = B.gp.data(); }
@@ -1047,14 +1083,15 @@ int main(int argc, char** argv) {
                     long tiles = 0, sites = 0; double t_first = -1.0, t_last = 0.0; double text_bytes = 0.0; };          // --verbose 1: what this device did (written by its own thread, read after the join)
     // bytes a finished tile brings back over the link, per site (the FORMAT arrays dominate: sample-major slabs, copied whole)
     // (--device-text 1: the text instead of the FORMAT arrays, counted as it comes back)
-    const double bytes_per_site = (double)N * ((want_dp ? 4.0 : 0.0) + (dtext ? 0.0 : 4.0 * G * ((a.add_gl ? 1 : 0) + (a.add_pl ? 1 : 0) + (a.add_gp ? 1 : 0)) +
+    const double bytes_per_site = (double)N * ((want_dp ? 4.0 : 0.0) + (dtext || dgvcf ? 0.0 : 4.0 * G * ((a.add_gl ? 1 : 0) + (a.add_pl ? 1 : 0) + (a.add_gp ? 1 : 0)) +
                                                4.0 * A * ((a.add_fmt_ad ? 1 : 0) + (a.add_fmt_adf ? 1 : 0) + (a.add_fmt_adr ? 1 : 0)))) + 64.0;
     std::vector<std::unique_ptr<Worker>> workers(D);
     for (int d = 0; d < D; d++) {
         workers[d].reset(new Worker());
         Worker* W = workers[d].get();
         vgl_ctx* ctx = ctxs[d];
-        W->th = std::thread([W, ctx, &now, dtext]() {
+        const int32_t* dps = a.gvcf_dps.data(); const int32_t n_dps = (int32_t)a.gvcf_dps.size();
+        W->th = std::thread([W, ctx, &now, dtext, dgvcf, dps, n_dps]() {
             // a tile is submitted (vgl_simulate_tile_async) before the previous one is waited for: its kernels run while the
             // previous tile's tags are still on their way to the host
             TileBufs* prev = nullptr; int32_t prev_ticket = 0;
@@ -1068,12 +1105,16 @@ int main(int argc, char** argv) {
                 }
                 int32_t ticket = 0;
                 if (B && W->t_first < 0.0) W->t_first = now();
-                if (B && !dtext && vgl_simulate_tile_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, &ticket) != VGL_OK) die("%s", vgl_last_error());
+                if (B && !dtext && !dgvcf && vgl_simulate_tile_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, &ticket) != VGL_OK) die("%s", vgl_last_error());
+                if (B && dgvcf && vgl_simulate_tile_gvcf_async(ctx, B->t0, B->ns, B->gt.data(), B->contig.data(), B->pos0.data(), dps, n_dps, &B->o, &B->g,
+                                                               &ticket) != VGL_OK)
+                    die("%s", vgl_last_error());
                 if (B && dtext && vgl_simulate_tile_text_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, B->text.data(), B->text_cap, B->toff.data(), &ticket) != VGL_OK)
                     die("%s", vgl_last_error());
                 if (prev) {
                     if (vgl_tile_wait(ctx, prev_ticket) != VGL_OK) die("%s", vgl_last_error());
                     if (dtext) W->text_bytes += (double)prev->toff[prev->ns];
+                    if (dgvcf) W->text_bytes += (double)prev->g.text_needed;
                     W->tiles += 1; W->sites += prev->ns; W->t_last = now();
                     { std::lock_guard<std::mutex> lk(prev->m); prev->done = true; }
                     prev->cv.notify_all();
@@ -1118,7 +1159,7 @@ int main(int argc, char** argv) {
         // the slab of site i holds the record's array as the reference keeps it for bcf_update_format_*(), element k of sample s
         // at slab[s * n + k] with the site's own n -- the encoders below read (and for BCF copy) it front to back
         fmt.clear();
-        if (dtext) return;                                       // the sample columns come from the device
+        if (dtext || dgvcf) return;                              // the sample columns come from the device
         const size_t sN = (size_t)N, sG = (size_t)nG, sA = (size_t)nA;
         if (a.add_fmt_dp) fmt.push_back({"DP", false, 1, &B.dp[(size_t)i * N], 1, sN});
         if (a.add_gl) fmt.push_back({"GL", true, nG, &B.gl[(size_t)i * G * N], sG, 1});
@@ -1127,6 +1168,69 @@ int main(int argc, char** argv) {
         if (a.add_fmt_ad) fmt.push_back({"AD", false, nA, &B.ad[(size_t)i * A * N], sA, 1});
         if (a.add_fmt_adf) fmt.push_back({"ADF", false, nA, &B.adf[(size_t)i * A * N], sA, 1});
         if (a.add_fmt_adr) fmt.push_back({"ADR", false, nA, &B.adr[(size_t)i * A * N], sA, 1});
+    };
+    // --device-gvcf 1: a tile's items in order.  Records and blocks get their fixed columns here (in parallel) and their sample
+    // columns from the device; the tile's last block stays open on the host (GvcfBlocker's state) and takes in the first block of a
+    // later tile that continues it (same contig, pos0 <= END + 1, same range): min / lexicographic-min aggregates, founder from the left
+    auto site_alleles = [&](const TileBufs& B, int i) {
+        std::string s;
+        for (int k = 0; k < B.na[i]; k++) { const int b = B.a2b[(size_t)i * 5 + k]; if (k) s += ','; s += b == 4 ? std::string(nonref) : (b >= 0 ? std::string(1, "ACGT"[b]) : std::string(".")); }
+        return s.empty() ? std::string(".") : s;
+    };
+    auto pl_count_die = [&](int nA) { die("Unexpected number of PL values: %d", N * nA * (nA + 1) / 2); };
+    auto write_gvcf_tile = [&](TileBufs& B) {
+        const vgl_gvcf_tile& g = B.g;
+        const int ni = g.n_items;
+        const vgl_gvcf_item* it = g.items;
+        bool merge = false;
+        if (ni > 0 && it[0].kind == VGL_GVCF_BLOCK && gv.current_dpr != 0) {
+            const int f = it[0].first;
+            merge = B.meta[f].rec->chrom == gv.chrom && B.meta[f].pos0 <= gv.end_pos + 1 && it[0].dpr == gv.current_dpr;
+            if (merge && (B.na[f] != 2 || gv.pl.size() != (size_t)N * 3)) pl_count_die(B.na[f]);
+        }
+        if (g.error_site >= 0) pl_count_die(B.na[g.error_site]);
+        enc.resize(std::max(ni, 1));
+        vsink::parallel_for(ni, enc_threads, [&](int k) {
+            enc[k].clear();
+            const vgl_gvcf_item& t = it[k];
+            if (t.kind == VGL_GVCF_RECORD) { std::vector<std::string> al; std::vector<vsink::FmtDesc> fmt; build_record(B, t.first, enc[k], al, fmt); return; }
+            if ((k == 0 && merge) || k == ni - 1) return;            // carried on the host
+            const int f = t.founder;
+            GvcfBlocker::fixed_columns(enc[k], out, B.meta[f].rec->chrom, B.meta[f].pos0, B.meta[t.last].pos0, site_alleles(B, f), t.min_dp,
+                                       a.add_qs ? &B.qs[(size_t)f * A] : nullptr, a.add_qs ? (size_t)B.na[f] : 0);
+        });
+        lap(4);
+        for (int k = 0; k < ni; k++) {
+            const vgl_gvcf_item& t = it[k];
+            if (t.kind == VGL_GVCF_BLOCK && k == 0 && merge) {
+                if (gv.min_dp > t.min_dp) gv.min_dp = t.min_dp;
+                for (int s = 0; s < N; ++s) {
+                    if (gv.dp[s] > B.fdp[s]) gv.dp[s] = B.fdp[s];
+                    const int32_t p1 = B.fpl[(size_t)3 * s + 1], p2 = B.fpl[(size_t)3 * s + 2];
+                    if (gv.pl[3 * s + 1] > p1) { gv.pl[3 * s + 1] = p1; gv.pl[3 * s + 2] = p2; }
+                    else if (gv.pl[3 * s + 1] == p1 && gv.pl[3 * s + 2] > p2) gv.pl[3 * s + 2] = p2;
+                }
+                gv.end_pos = B.meta[t.last].pos0;
+                if (k < ni - 1) { gv.emit(out, N); n_out++; }
+                continue;
+            }
+            if (gv.current_dpr != 0) { gv.emit(out, N); n_out++; }
+            if (t.kind == VGL_GVCF_BLOCK && k == ni - 1) {               // the tile's last block: open until a later tile decides
+                const int f = t.founder, nA = B.na[f], nG = nA * (nA + 1) / 2;
+                const int32_t* dp = (ni == 1) ? B.fdp.data() : B.ldp.data();
+                const int32_t* pl = (ni == 1) ? B.fpl.data() : B.lpl.data();
+                gv.dp.assign(dp, dp + N); gv.pl.assign(pl, pl + (size_t)N * nG);
+                gv.qsum.clear(); if (a.add_qs) gv.qsum.assign(&B.qs[(size_t)f * A], &B.qs[(size_t)f * A] + nA);
+                gv.chrom = B.meta[f].rec->chrom; gv.start_pos = B.meta[f].pos0; gv.end_pos = B.meta[t.last].pos0;
+                gv.alleles = site_alleles(B, f); gv.min_dp = t.min_dp; gv.current_dpr = t.dpr;
+                continue;
+            }
+            out.put(enc[k]);
+            if (t.kind == VGL_GVCF_BLOCK) out.put(B.text.data() + B.boff[t.block], (size_t)(B.boff[t.block + 1] - B.boff[t.block]));
+            else out.put(B.text.data() + B.toff[t.first], (size_t)(B.toff[t.first + 1] - B.toff[t.first]));
+            n_out++;
+        }
+        lap(5);
     };
     // everything the writer does with one finished tile, in site order (TSV lines, pileup, gVCF blocks, records)
     auto write_tile = [&](TileBufs& B) {
@@ -1171,7 +1275,7 @@ int main(int argc, char** argv) {
                 pile.write(line.data(), line.size());
             }
             if (B.st[i] < 0) { n_skipped++; continue; }
-            if (!a.do_gvcf) continue;                                    // plain records: encoded in parallel below
+            if (!a.do_gvcf || dgvcf) continue;                           // plain records, device gVCF: written below
             // gVCF: write_record_values (vcfgl.cpp:167-206) carries the open block from record to record (and from tile to
             // tile, whichever device simulated it)
             const int nA = B.na[i];
@@ -1186,6 +1290,7 @@ int main(int argc, char** argv) {
             if (ret == GvcfBlocker::FLUSH_BLOCK) { gv.emit(out, N); n_out++; ret = gv.prepare(&sv); }
             if (ret == GvcfBlocker::WRITE_SIMREC) { out.write_rec(line, fmt); n_out++; }
         }
+        if (dgvcf) write_gvcf_tile(B);
         if (!a.do_gvcf) {
             enc.resize(ns);
             vsink::parallel_for(ns, enc_threads, [&](int i) {
@@ -1209,6 +1314,7 @@ int main(int argc, char** argv) {
     // ---- the tile ring: produce (decode sites, hand the tile to its device) up to R tiles ahead, write in order
     size_t produced = 0, consumed = 0;
     bool eof = false;
+    std::map<std::string, int32_t> contig_ids; const std::string* last_chrom = nullptr; int32_t last_id = 0;
     lap(6);
     for (;;) {
         while (!eof && produced - consumed < (size_t)R) {
@@ -1218,6 +1324,14 @@ int main(int argc, char** argv) {
             while (B.ns < TS && stream.next(&B.gt[(size_t)B.ns * N], B.meta[B.ns])) B.ns++;
             if (B.ns < TS) eof = true;
             if (B.ns == 0) break;
+            if (dgvcf) for (int i = 0; i < B.ns; i++) {                 // contig ids: equal for equal names (the device compares ids)
+                const std::string& c = B.meta[i].rec->chrom;
+                if (last_chrom == nullptr || *last_chrom != c) {
+                    auto ins = contig_ids.emplace(c, (int32_t)contig_ids.size());
+                    last_id = ins.first->second; last_chrom = &ins.first->first;
+                }
+                B.contig[i] = last_id; B.pos0[i] = B.meta[i].pos0;
+            }
             n_sites_total += (size_t)B.ns;
             PBuf<uint8_t>::device() = devices[B.dev]; PBuf<double>::device() = devices[B.dev];      // dump buffers of this entry: next to its device, like the rest
             if (pile_fp) { B.reads.resize((size_t)pile_cap * TS * N); memset(B.reads.data(), 0xFF, (size_t)pile_cap * B.ns * N); B.o.reads = B.reads.data(); B.o.read_capacity = pile_cap; }   // capacity of the per-read dump: the library stages at most read_cap reads; ask generously

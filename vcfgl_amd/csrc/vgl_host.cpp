@@ -222,6 +222,14 @@ struct vgl_ctx {
         bool text = false; uint8_t* h_text = nullptr; int64_t text_cap = 0; int64_t* h_toff = nullptr;
         uint32_t dev_fields = 0;                                    // fields of d_out the tile's kernels wrote (bit f: FIELDS[f])
         uint8_t* d_text = nullptr; int64_t d_text_bytes = 0; int64_t* d_toff = nullptr; void* d_tws = nullptr; int64_t d_tws_bytes = 0;
+        // vgl_simulate_tile_gvcf_async: the tile blocked on the device (vgl_gvcf.hip), its record and block columns formatted there
+        // (record text in d_text / d_toff, block text in d_btext / d_boff); vgl_tile_wait copies the text back, which knows its size
+        bool gvcf = false; vgl_gvcf_tile* h_gv = nullptr; int32_t* h_counts = nullptr;
+        int32_t* h_contig = nullptr; int64_t* h_pos0 = nullptr; int32_t* d_contig = nullptr; int64_t* d_pos0 = nullptr;
+        std::vector<int32_t> dps; int32_t* d_dps = nullptr; size_t d_dps_n = 0;
+        vgl_gvcf_item* d_items = nullptr; int32_t* d_counts = nullptr; int32_t* d_bdp = nullptr; int32_t* d_bpl = nullptr;
+        int32_t* d_bna = nullptr; int32_t* d_bst = nullptr; int32_t* d_rst = nullptr; int32_t* d_edge = nullptr;
+        void* d_gws = nullptr; int64_t d_gws_bytes = 0; uint8_t* d_btext = nullptr; int64_t d_btext_bytes = 0; int64_t* d_boff = nullptr;
     } slot[2];
     hipStream_t s_text = nullptr;                                   // text copies of vgl_tile_wait (never behind the next tile's copies)
     // a draw deeper than the staging capacity (vcfgl grows its read buffers, bcf_utils.cpp:618-648): the host entry points run such a tile again on
@@ -350,9 +358,12 @@ extern "C" int vgl_ctx_destroy(vgl_ctx* c) {
     for (auto& S : c->slot) {
         if (S.busy && S.ev_copied) (void)hipEventSynchronize(S.ev_copied);
         for (void* q : S.d_out) if (q) (void)hipFree(q);
-        void* dq[] = {S.d_gt, S.d_reads_out, S.d_errp_out, S.d_pick_out, S.d_text, S.d_toff, S.d_tws};
+        void* dq[] = {S.d_gt, S.d_reads_out, S.d_errp_out, S.d_pick_out, S.d_text, S.d_toff, S.d_tws, S.d_contig, S.d_pos0, S.d_dps, S.d_items,
+                      S.d_counts, S.d_bdp, S.d_bpl, S.d_bna, S.d_bst, S.d_rst, S.d_edge, S.d_gws, S.d_btext, S.d_boff};
         for (void* q : dq) if (q) (void)hipFree(q);
         if (S.h_gt) (void)hipHostFree(S.h_gt);
+        void* hq[] = {S.h_counts, S.h_contig, S.h_pos0};
+        for (void* q : hq) if (q) (void)hipHostFree(q);
         if (S.h_flag) (void)hipHostFree(S.h_flag);
         if (S.ev_kernels) (void)hipEventDestroy(S.ev_kernels);
         if (S.ev_copied) (void)hipEventDestroy(S.ev_copied);
@@ -1130,11 +1141,110 @@ static int enqueue_text(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites) {
                                   S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
 }
 
+extern "C" int vgl_gvcf_edges_device(int32_t n_samples, int32_t n_sites, const vgl_gvcf_in* in, const vgl_gvcf_out* out, void* workspace,
+                                     int32_t* edge, void* hip_stream);            // vgl_gvcf.hip (not exported)
+
+// the block columns: PL (the founder's nG values per sample) and DP of each block's aggregates
+static int gvcf_block_fields(const vgl_ctx* c, const vgl_ctx::HostSlot* S, vgl_text_field* bf) {
+    bf[0].key = "PL"; bf[0].is_float = 0; bf[0].count = VGL_TEXT_PER_G; bf[0].base = S ? S->d_bpl : nullptr; bf[0].site_stride = (int64_t)field_count(c, K_PLANEG, 1);
+    bf[1].key = "DP"; bf[1].is_float = 0; bf[1].count = VGL_TEXT_ONE; bf[1].base = S ? S->d_bdp : nullptr; bf[1].site_stride = c->dp.n_samples;
+    return 2;
+}
+
+extern "C" int64_t vgl_ctx_gvcf_text_bound(const vgl_ctx* c, int32_t n_sites) {
+    if (!c || n_sites < 0) return -1;
+    vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
+    const int nf = text_fields(c, tf, fid);
+    vgl_text_field bf[2];
+    gvcf_block_fields(c, nullptr, bf);
+    // a site is a record or a member of at most one block: the larger of the two texts per site
+    const int64_t rec = vgl_text_bound(c->dp.n_samples, 1, tf, nf, (int32_t)c->dp.A), blk = vgl_text_bound(c->dp.n_samples, 1, bf, 2, (int32_t)c->dp.A);
+    if (rec < 0 || blk < 0) return -1;
+    return (int64_t)n_sites * (rec > blk ? rec : blk);
+}
+
+// the blocker, the edges and both formatters on the slot's device planes (compute stream)
+static int enqueue_gvcf(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites) {
+    const int32_t N = c->dp.n_samples;
+    vgl_gvcf_in in; memset(&in, 0, sizeof in);
+    in.site_status = (const int32_t*)S.d_out[0]; in.n_alleles = (const int32_t*)S.d_out[1]; in.n_alleles_obs = (const int32_t*)S.d_out[2];
+    in.contig = S.d_contig; in.pos0 = S.d_pos0;
+    in.dp = (const int32_t*)S.d_out[10]; in.dp_site_stride = N; in.pl = (const int32_t*)S.d_out[12]; in.pl_site_stride = (int64_t)field_count(c, K_PLANEG, 1);
+    in.dps = S.d_dps; in.n_dps = (int32_t)S.dps.size();
+    vgl_gvcf_out out; memset(&out, 0, sizeof out);
+    out.items = S.d_items; out.counts = S.d_counts; out.block_dp = S.d_bdp; out.block_pl = S.d_bpl; out.block_n_alleles = S.d_bna;
+    out.block_status = S.d_bst; out.record_status = S.d_rst;
+    int rc = vgl_gvcf_blocks_device(c->device, N, n_sites, &in, &out, S.d_gws, S.d_gws_bytes, c->s_compute);
+    if (rc == VGL_OK) rc = vgl_gvcf_edges_device(N, n_sites, &in, &out, S.d_gws, S.d_edge, c->s_compute);
+    if (rc != VGL_OK) return rc;
+    vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
+    const int nf = text_fields(c, tf, fid);
+    for (int k = 0; k < nf; k++) tf[k].base = S.d_out[fid[k]];
+    rc = vgl_text_format_device(c->device, tf, nf, N, n_sites, S.d_rst, in.n_alleles, S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
+    if (rc != VGL_OK) return rc;
+    vgl_text_field bf[2];
+    gvcf_block_fields(c, &S, bf);
+    return vgl_text_format_device(c->device, bf, 2, N, n_sites, S.d_bst, S.d_bna, S.d_btext, S.text_cap, S.d_boff, S.d_tws, S.d_tws_bytes, c->s_compute);
+}
+
+// the bounded gVCF outputs of a tile: items, counts, offsets, the first / last block's aggregates
+static int copy_gvcf_small(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites, hipStream_t st) {
+    vgl_gvcf_tile* g = S.h_gv;
+    const size_t N = c->dp.n_samples, GN = field_count(c, K_PLANEG, 1);
+    HIPCHK(hipMemcpyAsync(g->items, S.d_items, sizeof(vgl_gvcf_item) * (size_t)n_sites, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(S.h_counts, S.d_counts, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(g->record_offsets, S.d_toff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(g->block_offsets, S.d_boff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, st));
+    if (g->first_dp) HIPCHK(hipMemcpyAsync(g->first_dp, S.d_edge, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (g->last_dp) HIPCHK(hipMemcpyAsync(g->last_dp, S.d_edge + N, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (g->first_pl) HIPCHK(hipMemcpyAsync(g->first_pl, S.d_edge + 2 * N, sizeof(int32_t) * GN, hipMemcpyDeviceToHost, st));
+    if (g->last_pl) HIPCHK(hipMemcpyAsync(g->last_pl, S.d_edge + 2 * N + GN, sizeof(int32_t) * GN, hipMemcpyDeviceToHost, st));
+    return VGL_OK;
+}
+
+// device buffers of a gVCF tile (sized for max_sites on first use) and its contig / pos0 / thresholds (compute stream)
+static int stage_gvcf(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites, const int32_t* contig, const int64_t* pos0) {
+    const size_t M = (size_t)c->max_sites, N = c->dp.n_samples, GN = field_count(c, K_PLANEG, 1);
+    if (!S.d_items) {
+        HIPCHK(hipMalloc((void**)&S.d_contig, sizeof(int32_t) * M)); HIPCHK(hipMalloc((void**)&S.d_pos0, sizeof(int64_t) * M));
+        HIPCHK(hipHostMalloc((void**)&S.h_contig, sizeof(int32_t) * M, hipHostMallocDefault)); HIPCHK(hipHostMalloc((void**)&S.h_pos0, sizeof(int64_t) * M, hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void**)&S.h_counts, 4 * sizeof(int32_t), hipHostMallocDefault));
+        HIPCHK(hipMalloc((void**)&S.d_counts, 4 * sizeof(int32_t)));
+        HIPCHK(hipMalloc((void**)&S.d_bdp, sizeof(int32_t) * M * N)); HIPCHK(hipMalloc((void**)&S.d_bpl, sizeof(int32_t) * M * GN));
+        HIPCHK(hipMalloc((void**)&S.d_bna, sizeof(int32_t) * M)); HIPCHK(hipMalloc((void**)&S.d_bst, sizeof(int32_t) * M));
+        HIPCHK(hipMalloc((void**)&S.d_rst, sizeof(int32_t) * M)); HIPCHK(hipMalloc((void**)&S.d_edge, sizeof(int32_t) * 2 * (N + GN)));
+        HIPCHK(hipMalloc((void**)&S.d_boff, sizeof(int64_t) * (M + 1)));
+        S.d_gws_bytes = vgl_gvcf_workspace_bytes((int32_t)N, (int32_t)M);
+        HIPCHK(hipMalloc(&S.d_gws, (size_t)S.d_gws_bytes));
+        HIPCHK(hipMalloc((void**)&S.d_items, sizeof(vgl_gvcf_item) * M));
+    }
+    if (S.d_btext_bytes < S.text_cap) {
+        if (S.d_btext) (void)hipFree(S.d_btext);
+        S.d_btext = nullptr; S.d_btext_bytes = 0;
+        HIPCHK(hipMalloc((void**)&S.d_btext, (size_t)S.text_cap));
+        S.d_btext_bytes = S.text_cap;
+    }
+    if (S.d_dps_n < S.dps.size()) {
+        if (S.d_dps) (void)hipFree(S.d_dps);
+        S.d_dps = nullptr; S.d_dps_n = 0;
+        HIPCHK(hipMalloc((void**)&S.d_dps, sizeof(int32_t) * S.dps.size()));
+        S.d_dps_n = S.dps.size();
+    }
+    memcpy(S.h_contig, contig, sizeof(int32_t) * (size_t)n_sites);
+    memcpy(S.h_pos0, pos0, sizeof(int64_t) * (size_t)n_sites);
+    HIPCHK(hipMemcpyAsync(S.d_contig, S.h_contig, sizeof(int32_t) * (size_t)n_sites, hipMemcpyHostToDevice, c->s_compute));
+    HIPCHK(hipMemcpyAsync(S.d_pos0, S.h_pos0, sizeof(int64_t) * (size_t)n_sites, hipMemcpyHostToDevice, c->s_compute));
+    // (S.dps lives in the slot until its next tile, which waits for this one)
+    if (!S.dps.empty()) HIPCHK(hipMemcpyAsync(S.d_dps, S.dps.data(), sizeof(int32_t) * S.dps.size(), hipMemcpyHostToDevice, c->s_compute));
+    return VGL_OK;
+}
+
 // Host buffers in, host buffers out, asynchronously: the tile's kernels are enqueued on the context's compute stream, the copies of
 // its tags back to the host on its copy stream behind them; with two tiles in flight the copies of tile t overlap the kernels of
 // tile t + 1.  Destination buffers from vgl_host_alloc() (pinned) are written by DMA directly; pageable ones work, more slowly.
 // the fallible part of vgl_simulate_tile_async, from the first enqueue on (its caller cleans up after a failure)
-static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o) {
+static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o,
+                             const int32_t* contig, const int64_t* pos0) {
     const size_t N = c->dp.n_samples;
     memcpy(S.h_gt, gt, (size_t)n_sites * N);
     HIPCHK(hipMemcpyAsync(S.d_gt, S.h_gt, (size_t)n_sites * N, hipMemcpyHostToDevice, c->s_compute));
@@ -1142,10 +1252,11 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     memset(&d, 0, sizeof d);
     // text: the planes of the formatted tags are computed on the device whether or not the caller also wants them back
     uint32_t text_mask = 0;
-    if (S.text) {
+    if (S.text || S.gvcf) {
         vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
         const int nf = text_fields(c, tf, fid);
         for (int k = 0; k < nf; k++) text_mask |= 1u << fid[k];
+        if (S.gvcf) text_mask |= 1u << 10 | 1u << 12;                  // (the blocker reads FORMAT/DP and PL)
     }
     S.dev_fields = 0;
     for (int f = 0; f < N_FIELDS; f++) {
@@ -1191,7 +1302,8 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
         HIPCHK(hipMemsetAsync(S.d_pick_out, 0xFF, (size_t)n_sites * sizeof(double), c->s_compute));
         d.site_pick_err = S.d_pick_out;
     }
-    if (S.text) {
+    if (S.gvcf) { const int rc = stage_gvcf(c, S, n_sites, contig, pos0); if (rc != VGL_OK) return rc; }
+    if (S.text || S.gvcf) {
         const int64_t ws = vgl_text_workspace_bytes((int32_t)N, c->max_sites);
         if (S.d_tws_bytes < ws) {
             if (S.d_tws) (void)hipFree(S.d_tws);
@@ -1213,6 +1325,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     HIPCHK(hipMemcpyAsync(S.h_flag, c->d_errflag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute));
     HIPCHK(hipMemsetAsync(c->d_errflag, 0, sizeof(uint32_t), c->s_compute));
     if (S.text && (rc = enqueue_text(c, S, n_sites)) != VGL_OK) return rc;
+    if (S.gvcf && (rc = enqueue_gvcf(c, S, n_sites)) != VGL_OK) return rc;
     HIPCHK(hipEventRecord(S.ev_kernels, c->s_compute));
     HIPCHK(hipStreamWaitEvent(c->s_copy, S.ev_kernels, 0));
     for (int f = 0; f < N_FIELDS; f++) {
@@ -1224,6 +1337,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     if (d.read_errp && c->dp.error_qs == 2) HIPCHK(hipMemcpyAsync(o->read_errp, d.read_errp, (size_t)o->read_capacity * n_sites * N * sizeof(double), hipMemcpyDeviceToHost, c->s_copy));
     if (d.site_pick_err) HIPCHK(hipMemcpyAsync(o->site_pick_err, d.site_pick_err, (size_t)n_sites * sizeof(double), hipMemcpyDeviceToHost, c->s_copy));
     if (S.text) HIPCHK(hipMemcpyAsync(S.h_toff, S.d_toff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, c->s_copy));
+    if (S.gvcf && (rc = copy_gvcf_small(c, S, n_sites, c->s_copy)) != VGL_OK) return rc;
     HIPCHK(hipEventRecord(S.ev_copied, c->s_copy));
     return VGL_OK;
 }
@@ -1234,9 +1348,19 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
 // The ticket and the slot are committed only when everything is enqueued: after a failure part-way the streams are drained, the
 // sticky device error word is cleared and the slot is free again -- no later tile inherits this one's flags or shares its buffers
 // with work still in flight.
+struct GvcfReq { const int32_t* contig; const int64_t* pos0; const int32_t* dps; int32_t n_dps; vgl_gvcf_tile* g; };
 static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o, int32_t* ticket,
-                      uint8_t* text, int64_t text_cap, int64_t* toff, bool want_text) {
+                      uint8_t* text, int64_t text_cap, int64_t* toff, bool want_text, const GvcfReq* gq = nullptr) {
     if (!c || !o || !ticket) return fail(VGL_E_ARG, "null argument");
+    if (gq) {
+        const vgl_gvcf_tile* g = gq->g;
+        if (!g || !g->items || !g->record_offsets || !g->block_offsets || g->text_cap < 0 || (g->text_cap > 0 && !g->text) || gq->n_dps < 0 ||
+            (gq->n_dps > 0 && !gq->dps) || (n_sites > 0 && (!gq->contig || !gq->pos0)))
+            return fail(VGL_E_ARG, "vgl_simulate_tile_gvcf_async: null or bad argument");
+        if (c->p.out_layout != VGL_LAYOUT_SAMPLE_MAJOR || !c->p.add_fmt_dp || !c->p.add_pl)
+            return fail(VGL_E_ARG, "vgl_simulate_tile_gvcf_async: the context needs out_layout = VGL_LAYOUT_SAMPLE_MAJOR, add_fmt_dp and add_pl");
+        text = g->text; text_cap = g->text_cap;
+    }
     if (want_text && (!toff || text_cap < 0 || (text_cap > 0 && !text))) return fail(VGL_E_ARG, "vgl_simulate_tile_text_async: null text or offsets");
     if (want_text && c->p.out_layout != VGL_LAYOUT_SAMPLE_MAJOR) return fail(VGL_E_ARG, "vgl_simulate_tile_text_async: the context needs out_layout = VGL_LAYOUT_SAMPLE_MAJOR");
     if (n_sites < 0 || n_sites > c->max_sites) return fail(VGL_E_ARG, "n_sites %d exceeds max_sites_per_tile %d", n_sites, c->max_sites);
@@ -1254,10 +1378,15 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     S.rc = VGL_OK; *S.h_flag = 0;
     S.site0 = site0; S.n_sites = n_sites; S.o = *o;
     S.text = want_text; S.h_text = text; S.text_cap = text_cap; S.h_toff = toff;
-    if (want_text && !c->s_text) HIPCHK(hipStreamCreateWithFlags(&c->s_text, hipStreamNonBlocking));
-    if (n_sites == 0) { if (want_text) toff[0] = 0; HIPCHK(hipEventRecord(S.ev_copied, c->s_copy)); }
-    else {
-        const int rc = enqueue_host_tile(c, S, site0, n_sites, gt, o);
+    S.gvcf = gq != nullptr; S.h_gv = gq ? gq->g : nullptr;
+    if (gq) S.dps.assign(gq->dps, gq->dps + gq->n_dps);
+    if ((want_text || gq) && !c->s_text) HIPCHK(hipStreamCreateWithFlags(&c->s_text, hipStreamNonBlocking));
+    if (n_sites == 0) {
+        if (want_text) toff[0] = 0;
+        if (gq) { gq->g->record_offsets[0] = 0; gq->g->block_offsets[0] = 0; }
+        HIPCHK(hipEventRecord(S.ev_copied, c->s_copy));
+    } else {
+        const int rc = enqueue_host_tile(c, S, site0, n_sites, gt, o, gq ? gq->contig : nullptr, gq ? gq->pos0 : nullptr);
         if (rc != VGL_OK) {
             char keep[sizeof g_err];
             memcpy(keep, g_err, sizeof keep);                        // the first error is the one to report
@@ -1280,6 +1409,12 @@ extern "C" int vgl_simulate_tile_async(vgl_ctx* c, int64_t site0, int32_t n_site
 extern "C" int vgl_simulate_tile_text_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o,
                                             uint8_t* text, int64_t text_cap, int64_t* offsets, int32_t* ticket) {
     return tile_async(c, site0, n_sites, gt, o, ticket, text, text_cap, offsets, true);
+}
+
+extern "C" int vgl_simulate_tile_gvcf_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, const int32_t* contig, const int64_t* pos0,
+                                            const int32_t* dps, int32_t n_dps, vgl_tile_out* o, vgl_gvcf_tile* g, int32_t* ticket) {
+    const GvcfReq q{contig, pos0, dps, n_dps, g};
+    return tile_async(c, site0, n_sites, gt, o, ticket, nullptr, 0, nullptr, false, &q);
 }
 
 // A tile whose device flags report a draw deeper than the staging capacity, run again through the sibling context (host buffers: the slot's own copy of
@@ -1334,16 +1469,35 @@ static int deep_rerun_text(vgl_ctx* c, vgl_ctx::HostSlot& S) {
         if (rc == VGL_OK) rc = vgl_ctx_check(c->deep, c->s_compute);
         if (rc != VGL_OK) return rc;                                 // (a draw beyond VGL_READ_CAP_MAX reads: VGL_E_CAPACITY after all)
     }
-    const int rc = enqueue_text(c, S, S.n_sites);
+    const int rc = S.gvcf ? enqueue_gvcf(c, S, S.n_sites) : enqueue_text(c, S, S.n_sites);
     if (rc != VGL_OK) return rc;
     for (int f = 0; f < N_FIELDS; f++) {
         void* host = *(void**)((char*)&S.o + FIELDS[f].off);
         if (host) HIPCHK(hipMemcpyAsync(host, S.d_out[f], field_count(c, FIELDS[f].kind, (size_t)S.n_sites) * FIELDS[f].esz, hipMemcpyDeviceToHost, c->s_compute));
     }
     if (S.o.site_pick_err && S.d_pick_out) HIPCHK(hipMemcpyAsync(S.o.site_pick_err, S.d_pick_out, (size_t)S.n_sites * sizeof(double), hipMemcpyDeviceToHost, c->s_compute));
-    HIPCHK(hipMemcpyAsync(S.h_toff, S.d_toff, sizeof(int64_t) * ((size_t)S.n_sites + 1), hipMemcpyDeviceToHost, c->s_compute));
+    if (S.text) HIPCHK(hipMemcpyAsync(S.h_toff, S.d_toff, sizeof(int64_t) * ((size_t)S.n_sites + 1), hipMemcpyDeviceToHost, c->s_compute));
+    if (S.gvcf) { const int r2 = copy_gvcf_small(c, S, S.n_sites, c->s_compute); if (r2 != VGL_OK) return r2; }
     HIPCHK(hipStreamSynchronize(c->s_compute));
     c->deep_runs++;
+    return VGL_OK;
+}
+
+// gVCF tile: counts into the caller's struct; the record text, then the block text behind it, cross the link (only the bytes produced)
+static int finish_gvcf(vgl_ctx* c, vgl_ctx::HostSlot& S) {
+    vgl_gvcf_tile* g = S.h_gv;
+    const int32_t n = S.n_sites;
+    if (n == 0) { g->n_items = 0; g->n_blocks = 0; g->error_site = -1; g->text_needed = 0; return VGL_OK; }
+    g->n_items = S.h_counts[0]; g->n_blocks = S.h_counts[1]; g->error_site = S.h_counts[2];
+    const int64_t rt = g->record_offsets[n], bt = g->block_offsets[n];
+    g->text_needed = rt + bt;
+    if (rt < 0 || bt < 0 || rt + bt > g->text_cap)
+        return fail(VGL_E_CAPACITY, "the tile's gVCF text needs %lld bytes, text_cap is %lld (text_needed holds the size; vgl_ctx_gvcf_text_bound bounds it)",
+                    (long long)(rt + bt), (long long)g->text_cap);
+    if (rt > 0) HIPCHK(hipMemcpyAsync(g->text, S.d_text, (size_t)rt, hipMemcpyDeviceToHost, c->s_text));
+    if (bt > 0) HIPCHK(hipMemcpyAsync(g->text + rt, S.d_btext, (size_t)bt, hipMemcpyDeviceToHost, c->s_text));
+    if (rt > 0 || bt > 0) HIPCHK(hipStreamSynchronize(c->s_text));
+    for (int32_t i = 0; i <= n; i++) g->block_offsets[i] += rt;
     return VGL_OK;
 }
 
@@ -1355,13 +1509,15 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
     HIPCHK(hipEventSynchronize(S.ev_copied));
     S.busy = false;
     if ((*S.h_flag & VGL_DEVERR_CAPACITY) && S.n_sites > 0) {
-        const int rc = S.text ? deep_rerun_text(c, S) : deep_rerun(c, S);
-        if (rc != VGL_E_CAPACITY && (rc != VGL_OK || !S.text)) return rc;      // done (or failed for another reason, reported as such)
+        const bool dev_text = S.text || S.gvcf;
+        const int rc = dev_text ? deep_rerun_text(c, S) : deep_rerun(c, S);
+        if (rc != VGL_E_CAPACITY && (rc != VGL_OK || !dev_text)) return rc;      // done (or failed for another reason, reported as such)
         if (rc == VGL_E_CAPACITY) return flags_to_rc(c, *S.h_flag);
     } else {
         const int rc = flags_to_rc(c, *S.h_flag);
-        if (rc != VGL_OK || !S.text) return rc;
+        if (rc != VGL_OK || !(S.text || S.gvcf)) return rc;
     }
+    if (S.gvcf) return finish_gvcf(c, S);
     // text: only the bytes the tile produced cross the link
     const int64_t total = S.h_toff[S.n_sites];
     if (total < 0 || total > S.text_cap)

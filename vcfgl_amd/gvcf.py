@@ -124,3 +124,82 @@ def stitch(parts: Sequence[List[Item]]) -> List[Item]:
                 part = part[1:]
         out.extend(part)
     return out
+
+
+class GvcfError(ValueError):
+    """A site joins a block while it or the block's founder has n_alleles != 2 (the host writer's "Unexpected number of PL values")."""
+
+    def __init__(self, site: int, n_values: int):
+        super().__init__(f"Unexpected number of PL values: {n_values} (site {site})")
+        self.site, self.n_values = site, n_values
+
+
+def blocks_device_raw(block_dps, site_status, n_obs, n_alleles, contig, pos0, dp, pl):
+    """vgl_gvcf_blocks_device on one tile (torch tensors on one HIP device, enqueued on the current stream; waits for it).
+    site_status / n_obs / n_alleles / contig: int32 [S]; pos0: int64 [S]; dp: int32 [S, N]; pl: int32 [S, K] sample-major slabs
+    (pl[i, s * nG(i) + g], K >= N * nG of every founder).  Returns a dict of the device outputs: items (numpy structured
+    vgl_gvcf_item [n_items]), n_items, n_blocks, error_site, block_dp [S, N], block_pl [S, K], block_n_alleles, block_status,
+    record_status (device tensors)."""
+    import ctypes as C
+    import torch
+    from . import _abi
+    S, N = int(dp.shape[0]), int(dp.shape[1])
+    dev = dp.device
+    for t in (site_status, n_obs, n_alleles, contig, dp, pl):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError("gvcf.blocks_device: contiguous int32 tensors on one HIP device are expected (pos0: int64)")
+    if pos0.dtype != torch.int64 or pos0.device != dev or pl.shape[0] != S:
+        raise ValueError("gvcf.blocks_device: pos0 must be int64 [S] and pl [S, K] on the device of dp")
+    lib = _abi.load_library()
+    with torch.cuda.device(dev):
+        dps = torch.tensor(list(block_dps) or [0], dtype=torch.int32, device=dev)
+        K = int(pl.shape[1])
+        items = torch.empty(max(1, S) * 8, dtype=torch.int32, device=dev)
+        counts = torch.empty(4, dtype=torch.int32, device=dev)
+        out_t = dict(block_dp=torch.empty(max(1, S), N, dtype=torch.int32, device=dev), block_pl=torch.empty(max(1, S), K, dtype=torch.int32, device=dev),
+                     block_n_alleles=torch.empty(max(1, S), dtype=torch.int32, device=dev),
+                     block_status=torch.empty(max(1, S), dtype=torch.int32, device=dev), record_status=torch.empty(max(1, S), dtype=torch.int32, device=dev))
+        ws_bytes = int(lib.vgl_gvcf_workspace_bytes(N, S))
+        ws = torch.empty(max(1, ws_bytes), dtype=torch.uint8, device=dev)
+        gin = _abi.GvcfIn(site_status.data_ptr(), n_obs.data_ptr(), n_alleles.data_ptr(), contig.data_ptr(), pos0.data_ptr(), dp.data_ptr(), N,
+                          pl.data_ptr(), K, dps.data_ptr(), len(list(block_dps)), 0)
+        gout = _abi.GvcfOut(items.data_ptr(), counts.data_ptr(), *(out_t[k].data_ptr() for k in ("block_dp", "block_pl", "block_n_alleles",
+                                                                                                  "block_status", "record_status")))
+        stream = torch.cuda.current_stream(dev)
+        rc = lib.vgl_gvcf_blocks_device(dev.index, N, S, C.byref(gin), C.byref(gout), C.c_void_p(ws.data_ptr()), ws_bytes,
+                                        C.c_void_p(stream.cuda_stream))
+        if rc != _abi.VGL_OK:
+            raise RuntimeError(f"vgl_gvcf_blocks_device: {lib.vgl_last_error().decode()} (code {rc})")
+        n_items, n_blocks, err, _ = (int(x) for x in counts.cpu().tolist())
+    names = ["kind", "first", "last", "founder", "dpr", "min_dp", "block", "reserved"]
+    arr = items.cpu().numpy()[: n_items * 8].reshape(n_items, 8)
+    rec = np.rec.fromarrays([arr[:, k] for k in range(8)], names=names) if n_items else np.rec.fromarrays([np.zeros(0, np.int32)] * 8, names=names)
+    out = dict(items=rec, n_items=n_items, n_blocks=n_blocks, error_site=err)
+    out.update(out_t)
+    return out
+
+
+def blocks_device(block_dps, site_status, n_obs, n_alleles, contig, pos0, dp, pl, chroms=None, site0=0) -> List[Item]:
+    """The items gvcf.build() returns for one tile, computed on the device (blocks_device_raw's arguments): ("rec", site0 + i) and
+    ("block", Block) with chrom = chroms[contig id] (default str(id)) and Block.pl [nG, N] (nG = 3 but for a lone founder with
+    n_alleles != 2).  Raises GvcfError where the host writer dies."""
+    r = blocks_device_raw(block_dps, site_status, n_obs, n_alleles, contig, pos0, dp, pl)
+    if r["error_site"] >= 0:
+        e = r["error_site"]
+        na = int(n_alleles[e].item())
+        raise GvcfError(site0 + e, int(dp.shape[1]) * na * (na + 1) // 2)
+    N = int(dp.shape[1])
+    ids = contig.cpu().numpy()
+    p0 = pos0.cpu().numpy()
+    bdp, bpl, bna = r["block_dp"].cpu().numpy(), r["block_pl"].cpu().numpy(), r["block_n_alleles"].cpu().numpy()
+    name = (lambda c: chroms[c]) if chroms is not None else (lambda c: str(c))
+    items: List[Item] = []
+    for t in r["items"]:
+        if t.kind == 0:
+            items.append(("rec", site0 + int(t.first)))
+            continue
+        b, f = int(t.block), int(t.founder)
+        nG = int(bna[b]) * (int(bna[b]) + 1) // 2
+        items.append(("block", Block(name(int(ids[f])), int(p0[f]), int(p0[int(t.last)]), int(t.dpr), int(t.min_dp), site0 + f,
+                                     bdp[b].copy(), bpl[b, : N * nG].reshape(N, nG).T.copy())))
+    return items
