@@ -51,7 +51,8 @@ extern "C" {
 #define VGL_E_CAPACITY     (-4)  /* a per-sample read depth exceeded the staging capacity (mean + 8 sigma + 16 reads) where the tile could not be run
                                     again: the host-buffer entry points (vgl_simulate_tile, vgl_tile_wait) run such a tile once more on an internal
                                     context with the layout's largest capacity, 1020 reads (the reference grows its buffers, bcf_utils.cpp:618-648), so
-                                    this code is left to vgl_ctx_check() (device buffers), VGL_RNG_SERIAL, per-read dumps and draws beyond 1020 reads */
+                                    this code is left to vgl_ctx_check() (device buffers), VGL_RNG_SERIAL, per-read dumps, pileups formatted on the
+                                    device (vgl_ctx_pileup_next) and draws beyond 1020 reads */
 #define VGL_E_UNSUPPORTED  (-5)  /* flag combination not implemented on the device path (the mt19937 beta sampler in VGL_RNG_TILE) */
 #define VGL_E_QSBIN        (-6)  /* "Could not find a range for qs value" (vcfgl.cpp:63)         */
 #define VGL_E_ADJQ         (-7)  /* --adjust-qs 1|2 met a read without a valid adjusted quality score: error probability
@@ -524,6 +525,50 @@ VGL_API int64_t vgl_ctx_gvcf_text_bound(const vgl_ctx* ctx, int32_t n_sites);
 VGL_API int vgl_simulate_tile_gvcf_async(vgl_ctx* ctx, int64_t site0, int32_t n_sites, const uint8_t* gt, const int32_t* contig,
                                          const int64_t* pos0, const int32_t* dps, int32_t n_dps, vgl_tile_out* out, vgl_gvcf_tile* g,
                                          int32_t* ticket);
+
+/* ---- pileup lines on the device (ABI 7, additive) -----------------------------------------------------------------------------
+ * The N-wide part of a -printPileup 1 line -- what the host writer appends behind the prefix chrom "\t" pos "\t" ref -- formatted from
+ * the tile's DP plane and read dump where they are computed.  For every site i with site_status[i] != VGL_SITE_SKIP_EMPTY the text is
+ *     ( "\t" COL(i, s) ) for s = 0 .. N-1, then "\n"
+ *     COL = "0\t*\t*" when dp(i, s) == 0, else dp "\t" B_0 .. B_{dp-1} "\t" Q_0 .. Q_{dp-1}
+ *     B_r = "ACGT"[reads[r][i][s] & 3]; Q_r = (reads[r][i][s] >> 2) + 33, or qual_char for every read when qual_char >= 0
+ * An empty site (VGL_SITE_SKIP_EMPTY) has no text; every other status has its line (VGL_SITE_SKIP_INVAR and VGL_SITE_NO_READS included).
+ *   vgl_pileup_bound          largest text of n_sites sites whose depths are at most read_capacity (pure host arithmetic; -1 on bad
+ *                             input): n_sites (1 + n_samples max(6, 3 + digits(read_capacity) + 2 read_capacity)).
+ *   vgl_pileup_workspace_bytes  device workspace of a call (pure host arithmetic).
+ *   vgl_pileup_format_device  site_status (int32 [n_sites]), fmt_dp (int32 [n_sites][n_samples]), reads (uint8 [read_capacity][n_sites]
+ *                             [n_samples], vgl_tile_out.reads' layout), dst [dst_cap], offsets (int64 [n_sites + 1]) and the workspace are
+ *                             device memory of `device`; work is enqueued on `hip_stream` without synchronising.  No dump row at or
+ *                             beyond read_capacity is read.  offsets[i] = where site i's text starts in dst, offsets[n_sites] = the
+ *                             total.  When the total exceeds dst_cap NOTHING is written to dst and offsets[n_sites] is the size the text
+ *                             needs.  A dp below 0 or above read_capacity is an error reported through the same word: NOTHING is
+ *                             written and offsets[n_sites] = -1 (the call itself returns VGL_OK: it does not synchronise).
+ *   vgl_ctx_pileup_bound      vgl_pileup_bound at the context's staging capacity (vgl_ctx_info_t.read_cap): the text_cap that always
+ *                             suffices for a tile of n_sites sites of this context.
+ *   vgl_ctx_pileup_next       asks for the pileup of the NEXT tile submitted on ctx by vgl_simulate_tile_async, _text_async or
+ *                             _gvcf_async (NULL withdraws a pending request; the next tile call consumes it, whether it succeeds or
+ *                             not).  That tile's read dump and DP plane feed the formatter on the device: they cross the link only if
+ *                             `out` also asks for them (reads / read_capacity, fmt_dp).  --adjust-qs 4 (adjust_qs & 4) is applied from
+ *                             the context's parameters: with error_qs 0 / 1 every read gets the adjusted score of error_rate, with
+ *                             error_qs 2 each read the adjusted score of its staged error probability (the sampler's rule: double
+ *                             log10, adjust_by, the bins or the cap of 63; an error probability of exactly 0 or 1 has no adjusted score
+ *                             and gives the byte 32, as the host writer's).  vgl_tile_wait copies the text into p->text (host memory)
+ *                             and the site offsets into p->offsets (host, int64 [n_sites + 1]), sets p->text_needed, and copies only the
+ *                             bytes produced.  A text larger than text_cap gives VGL_E_CAPACITY (text_needed = its size, nothing is
+ *                             written to text).  A tile that drew deeper than the staging capacity is not run again when it carries a
+ *                             pileup: VGL_E_CAPACITY, as for a per-read dump.  `p` and its arrays must live until vgl_tile_wait returns. */
+typedef struct vgl_pileup_tile {   /* host memory */
+    uint8_t* text; int64_t text_cap;
+    int64_t* offsets;             /* [n_sites + 1]                                    */
+    int64_t text_needed;          /* written by vgl_tile_wait                         */
+} vgl_pileup_tile;
+VGL_API int64_t vgl_pileup_bound(int32_t n_samples, int32_t n_sites, int32_t read_capacity);
+VGL_API int64_t vgl_pileup_workspace_bytes(int32_t n_samples, int32_t n_sites);
+VGL_API int vgl_pileup_format_device(int32_t device, int32_t n_samples, int32_t n_sites, const int32_t* site_status, const int32_t* fmt_dp,
+                                     const uint8_t* reads, int32_t read_capacity, int32_t qual_char, uint8_t* dst, int64_t dst_cap,
+                                     int64_t* offsets, void* workspace, int64_t workspace_bytes, void* hip_stream);
+VGL_API int64_t vgl_ctx_pileup_bound(const vgl_ctx* ctx, int32_t n_sites);
+VGL_API int vgl_ctx_pileup_next(vgl_ctx* ctx, vgl_pileup_tile* p);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,7 @@ EXPORTS = [
     "vgl_bgzf_host_create", "vgl_bgzf_host_submit", "vgl_bgzf_host_wait", "vgl_bgzf_host_destroy",
     "vgl_text_bound", "vgl_text_workspace_bytes", "vgl_text_format_device", "vgl_ctx_text_bound", "vgl_simulate_tile_text_async",
     "vgl_gvcf_workspace_bytes", "vgl_gvcf_blocks_device", "vgl_ctx_gvcf_text_bound", "vgl_simulate_tile_gvcf_async",
+    "vgl_pileup_bound", "vgl_pileup_workspace_bytes", "vgl_pileup_format_device", "vgl_ctx_pileup_bound", "vgl_ctx_pileup_next",
 ]
 VGL_PACK_ROW, VGL_PACK_ROWS_G, VGL_PACK_ROWS_A = 0, 1, 2
 
@@ -134,6 +135,10 @@ class GvcfTile(C.Structure):
                 ("block_offsets", C.c_void_p), ("first_dp", C.c_void_p), ("first_pl", C.c_void_p), ("last_dp", C.c_void_p),
                 ("last_pl", C.c_void_p), ("n_items", C.c_int32), ("n_blocks", C.c_int32), ("error_site", C.c_int32),
                 ("reserved", C.c_int32), ("text_needed", C.c_int64)]
+
+
+class PileupTile(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_cap", C.c_int64), ("offsets", C.c_void_p), ("text_needed", C.c_int64)]
 
 
 class PackPlan(C.Structure):
@@ -222,6 +227,15 @@ def load_library(hooks=False):
     lib.vgl_ctx_gvcf_text_bound.argtypes = [C.c_void_p, C.c_int32]
     lib.vgl_simulate_tile_gvcf_async.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                  C.POINTER(TileOut), C.POINTER(GvcfTile), C.POINTER(C.c_int32)]
+    lib.vgl_pileup_bound.restype = C.c_int64
+    lib.vgl_pileup_bound.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.vgl_pileup_workspace_bytes.restype = C.c_int64
+    lib.vgl_pileup_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.vgl_pileup_format_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vgl_ctx_pileup_bound.restype = C.c_int64
+    lib.vgl_ctx_pileup_bound.argtypes = [C.c_void_p, C.c_int32]
+    lib.vgl_ctx_pileup_next.argtypes = [C.c_void_p, C.POINTER(PileupTile)]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

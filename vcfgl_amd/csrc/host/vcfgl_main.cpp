@@ -62,6 +62,7 @@ struct Args {
     int device_bgzf = 0;               // --device-bgzf 1: BGZF streams compressed on the first device of the run
     int device_text = 0;               // --device-text 1: the sample columns of VCF text records formatted on the device
     int device_gvcf = 0;               // --device-gvcf 1: -doGVCF 1 blocks built and their / the records' sample columns formatted on the device
+    int device_pileup = 0;             // --device-pileup 1: the N-wide part of -printPileup 1's lines formatted on the device
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -102,6 +103,9 @@ static const char USAGE[] =
     "                   --device-gvcf 0|1 [0: -doGVCF 1 blocks built on the host, site by site; 1: on the device that simulated the tile,\n"
     "                   with the sample columns of records and blocks formatted there (blocks that cross a tile are merged on the host).\n"
     "                   Same bytes either way; needs -doGVCF 1 and -O v or -O z, refused with --depth inf; a run without a GPU fails]\n"
+    "                   --device-pileup 0|1 [0: -printPileup 1's lines formatted on the host from the read dump; 1: their sample columns\n"
+    "                   formatted on the device that simulated the tile, and the text crosses the link instead of the read dump.  Same\n"
+    "                   bytes either way; needs -printPileup 1, refused with --depth inf; a run without a GPU fails instead of falling back]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 static Args parse_args(int argc, char** argv) {
@@ -181,6 +185,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--device-bgzf") a.device_bgzf = I(v);
         else if (f == "--device-text") a.device_text = I(v);
         else if (f == "--device-gvcf") a.device_gvcf = I(v);
+        else if (f == "--device-pileup") a.device_pileup = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -242,6 +247,11 @@ static Args parse_args(int argc, char** argv) {
     if (a.device_gvcf) {                                        // (checked before any GPU work: nothing is written)
         if (!a.do_gvcf) die("--device-gvcf 1 builds gVCF blocks: it needs -doGVCF 1.");
         if (a.output_mode != "v" && a.output_mode != "z") die("--device-gvcf 1 writes gVCF text: it needs -O v or -O z (found -O %s).", a.output_mode.c_str());
+    }
+    range(a.device_pileup, 0, 1, "--device-pileup");
+    if (a.device_pileup) {                                      // (checked before any GPU work: nothing is written)
+        if (!a.print_pileup) die("--device-pileup 1 formats the pileup of -printPileup 1: it needs -printPileup 1.");
+        if (a.depth_inf) die("--device-pileup 1 is not supported with --depth inf (no tile is simulated, no pileup is written).");
     }
     if (a.seed == -1) { a.seed = (int)time(NULL); fprintf(stderr, "\n-> No seed was given. Setting the random seed to the randomly chosen value: %d\n", a.seed); }
     if (a.beta_sampler < 0) a.beta_sampler = (a.rng_mode == VGL_RNG_SERIAL) ? VGL_BETA_STD : VGL_BETA_RAND48;
@@ -817,7 +827,7 @@ int main(int argc, char** argv) {
     Args a = parse_args(argc, argv);
     RunLog runlog; runlog.open(a);
     // --verbose 1: wall-clock seconds per stage on stderr at the end
-    double t_stage[8] = {0, 0, 0, 0, 0, 0, 0, 0};             // read, sites, context, waiting for the device, encode, write, tile buffers (page-locked), teardown
+    double t_stage[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};          // read, sites, context, waiting for the device, encode, write, tile buffers (page-locked), teardown, pileup
     auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; };
     double t_mark = now();
     auto lap = [&](int k) { const double t = now(); t_stage[k] += t - t_mark; t_mark = t; };
@@ -940,8 +950,16 @@ int main(int argc, char** argv) {
     p.add_fmt_dp = a.add_fmt_dp; p.add_info_dp = a.add_info_dp; p.add_fmt_ad = a.add_fmt_ad; p.add_info_ad = a.add_info_ad;
     p.add_fmt_adf = a.add_fmt_adf; p.add_info_adf = a.add_info_adf; p.add_fmt_adr = a.add_fmt_adr; p.add_info_adr = a.add_info_adr;
     int TS = a.tile_sites > 0 ? a.tile_sites : 4096;
-    if (a.print_pileup || a.print_qs_err || a.print_gl_err || a.print_qscores)      // per-read dumps: bounded host / device staging
+    const bool dpile = a.device_pileup != 0;                   // --device-pileup 1: the pileup's sample columns come from the device
+    // per-read dump rows: the library's own staging capacity (vgl_host.cpp: depth + 8 sqrt(depth) + 16)
+    double dmax = a.depth; for (double d : a.depths) dmax = std::max(dmax, d); if (!(dmax >= 0)) dmax = 0;
+    const int pile_cap = (((int)ceil(dmax + 8.0 * sqrt(dmax) + 16.0)) + 3) & ~3;
+    if ((a.print_pileup && !dpile) || a.print_qs_err || a.print_gl_err || a.print_qscores)      // per-read dumps: bounded host / device staging
         TS = std::max(1, std::min(TS, (int)((64u << 20) / ((size_t)1024 * (size_t)std::max(N, 1)) + 1)));
+    else if (dpile) {                                           // the pileup text of a tile: at most 256 MiB per ring entry (two per device)
+        const int64_t per_site = vgl_pileup_bound(N, 1, pile_cap);
+        TS = std::max(1, (int)std::min<int64_t>(TS, (int64_t)(256u << 20) / std::max<int64_t>(per_site, 1)));
+    }
     // ---- devices: one context and one host thread per GPU; tiles are dealt to them round robin and come back to the writer
     //      (this thread) in site order.  Every value depends only on the absolute site index (VGL_RNG_TILE), so the file does
     //      not depend on the number of devices.  VGL_RNG_SERIAL consumes its streams in call order: one device.
@@ -998,11 +1016,8 @@ int main(int argc, char** argv) {
         if (a.print_qscores) printf("qs\tNA\tNA\tNA\tNA\t%d\n", a.adjust_qs ? pre_adjq : pre_q);
     }
     const bool dump_reads = a.error_qs == 2 && (a.print_qs_err || a.print_gl_err || a.print_qscores);
-    const bool want_errp = dump_reads || (a.error_qs == 2 && pile_fp && (a.adjust_qs & 4));
+    const bool want_errp = dump_reads || (a.error_qs == 2 && pile_fp && !dpile && (a.adjust_qs & 4));
     const bool dump_pick = a.error_qs == 1 && a.print_bpe;
-    // per-read dump rows: the library's own staging capacity (vgl_host.cpp: depth + 8 sqrt(depth) + 16)
-    double dmax = a.depth; for (double d : a.depths) dmax = std::max(dmax, d); if (!(dmax >= 0)) dmax = 0;
-    const int pile_cap = (((int)ceil(dmax + 8.0 * sqrt(dmax) + 16.0)) + 3) & ~3;
     const char* nonref = (a.do_unobserved == 1 || a.do_unobserved == 4) ? "<*>" : "<NON_REF>";
 
     // ---- tile buffers (host side of vgl_tile_out): only what this run prints is requested from the device
@@ -1010,7 +1025,8 @@ int main(int argc, char** argv) {
     const bool dtext = a.device_text != 0;
     // --device-gvcf 1: the same for -doGVCF 1; the blocks are built on the device, the FORMAT arrays stay there
     const bool dgvcf = a.device_gvcf != 0;
-    const bool want_dp = (a.add_fmt_dp && !dtext && !dgvcf) || (a.do_gvcf && !dgvcf) || pile_fp || dump_reads;
+    // --device-pileup 1: the read dump and DP stay on the device (the pileup's sample columns come back as text)
+    const bool want_dp = (a.add_fmt_dp && !dtext && !dgvcf) || (a.do_gvcf && !dgvcf) || (pile_fp && !dpile) || dump_reads;
     struct TileBufs {
         int ns = 0; int64_t t0 = 0; int dev = 0;
         std::vector<SiteMeta> meta; std::vector<uint8_t> gt;
@@ -1022,6 +1038,7 @@ int main(int argc, char** argv) {
         // --device-gvcf 1: contig id and position per site (in), the items, block offsets and the first / last block's aggregates (out)
         std::vector<int32_t> contig; std::vector<int64_t> pos0;
         PBuf<int32_t> gitems, fdp, fpl, ldp, lpl; PBuf<int64_t> boff; vgl_gvcf_tile g;
+        PBuf<uint8_t> ptext; PBuf<int64_t> poff; vgl_pileup_tile pt;      // --device-pileup 1: the tile's pileup columns and site offsets
         vgl_tile_out o;
         std::mutex m; std::condition_variable cv; bool done = false;
     };
@@ -1051,6 +1068,13 @@ int main(int argc, char** argv) {
         if (a.add_qs) { B.qs.resize((size_t)TS * A); B.o.qs = B.qs.data(); }
         if (a.add_i16) { B.i16.resize((size_t)TS * 16); B.o.i16 = B.i16.data(); }
         if (want_dp) { B.dp.resize(E); B.o.fmt_dp = B.dp.data(); }
+        memset(&B.pt, 0, sizeof B.pt);
+        if (dpile) {
+            const int64_t cap = vgl_ctx_pileup_bound(ctxs[ri % (size_t)D], TS);
+            if (cap < 0) die("--device-pileup 1: %s", vgl_last_error());
+            B.ptext.resize((size_t)std::max<int64_t>(cap, 1)); B.poff.resize((size_t)TS + 1);
+            B.pt.text = B.ptext.data(); B.pt.text_cap = cap; B.pt.offsets = B.poff.data();
+        }
         if (dtext) {
             B.text_cap = vgl_ctx_text_bound(ctxs[ri % (size_t)D], TS);
             if (B.text_cap < 0) die("--device-text 1: %s", vgl_last_error());
@@ -1091,7 +1115,7 @@ int main(int argc, char** argv) {
         Worker* W = workers[d].get();
         vgl_ctx* ctx = ctxs[d];
         const int32_t* dps = a.gvcf_dps.data(); const int32_t n_dps = (int32_t)a.gvcf_dps.size();
-        W->th = std::thread([W, ctx, &now, dtext, dgvcf, dps, n_dps]() {
+        W->th = std::thread([W, ctx, &now, dtext, dgvcf, dpile, dps, n_dps]() {
             // a tile is submitted (vgl_simulate_tile_async) before the previous one is waited for: its kernels run while the
             // previous tile's tags are still on their way to the host
             TileBufs* prev = nullptr; int32_t prev_ticket = 0;
@@ -1105,6 +1129,7 @@ int main(int argc, char** argv) {
                 }
                 int32_t ticket = 0;
                 if (B && W->t_first < 0.0) W->t_first = now();
+                if (B && dpile && vgl_ctx_pileup_next(ctx, &B->pt) != VGL_OK) die("%s", vgl_last_error());   // (a side channel of the tile call below)
                 if (B && !dtext && !dgvcf && vgl_simulate_tile_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, &ticket) != VGL_OK) die("%s", vgl_last_error());
                 if (B && dgvcf && vgl_simulate_tile_gvcf_async(ctx, B->t0, B->ns, B->gt.data(), B->contig.data(), B->pos0.data(), dps, n_dps, &B->o, &B->g,
                                                                &ticket) != VGL_OK)
@@ -1115,6 +1140,7 @@ int main(int argc, char** argv) {
                     if (vgl_tile_wait(ctx, prev_ticket) != VGL_OK) die("%s", vgl_last_error());
                     if (dtext) W->text_bytes += (double)prev->toff[prev->ns];
                     if (dgvcf) W->text_bytes += (double)prev->g.text_needed;
+                    if (dpile) W->text_bytes += (double)prev->pt.text_needed;
                     W->tiles += 1; W->sites += prev->ns; W->t_last = now();
                     { std::lock_guard<std::mutex> lk(prev->m); prev->done = true; }
                     prev->cv.notify_all();
@@ -1258,21 +1284,29 @@ int main(int argc, char** argv) {
                 fwrite(tsv.data(), 1, tsv.size(), stdout);
             }
             if (pile_fp && B.st[i] != VGL_SITE_SKIP_EMPTY) {              // vcfgl.cpp:414-416, 616-634 (printed before skip decisions)
+                const double t_pile = now();
                 line.clear();
                 char hb[64]; snprintf(hb, sizeof hb, "\t%ld\t%c", S.pos0 + 1, S.ref_char);
                 line += S.rec->chrom; line += hb;
-                for (int s = 0; s < N; s++) {
-                    const int n = B.dp[(size_t)i * N + s];
-                    if (n == 0) { line += "\t0\t*\t*"; continue; }
-                    snprintf(hb, sizeof hb, "\t%d\t", n); line += hb;
-                    for (int r = 0; r < n; r++) line += "ACGT"[B.reads[((size_t)r * ns + i) * N + s] & 3];
-                    line += '\t';
-                    if (!(a.adjust_qs & 4)) for (int r = 0; r < n; r++) line += (char)((B.reads[((size_t)r * ns + i) * N + s] >> 2) + 33);
-                    else if (a.error_qs != 2) line.append((size_t)n, (char)(pre_adjq + 33));                  // PROGRAM_WILL_ADJUST_QS_FOR_PILEUP
-                    else for (int r = 0; r < n; r++) { int q, aq; host_errprob_to_qs(a, B.errp[((size_t)r * ns + i) * N + s], q, aq); line += (char)(aq + 33); }
+                if (dpile) {                                                // the prefix here, the sample columns and the newline from the device
+                    pile.write(line.data(), line.size());
+                    pile.write(B.ptext.data() + B.poff[i], (size_t)(B.poff[i + 1] - B.poff[i]));
+                } else {
+                    for (int s = 0; s < N; s++) {
+                        const int n = B.dp[(size_t)i * N + s];
+                        if (n == 0) { line += "\t0\t*\t*"; continue; }
+                        snprintf(hb, sizeof hb, "\t%d\t", n); line += hb;
+                        for (int r = 0; r < n; r++) line += "ACGT"[B.reads[((size_t)r * ns + i) * N + s] & 3];
+                        line += '\t';
+                        if (!(a.adjust_qs & 4)) for (int r = 0; r < n; r++) line += (char)((B.reads[((size_t)r * ns + i) * N + s] >> 2) + 33);
+                        else if (a.error_qs != 2) line.append((size_t)n, (char)(pre_adjq + 33));                  // PROGRAM_WILL_ADJUST_QS_FOR_PILEUP
+                        else for (int r = 0; r < n; r++) { int q, aq; host_errprob_to_qs(a, B.errp[((size_t)r * ns + i) * N + s], q, aq); line += (char)(aq + 33); }
+                    }
+                    line += '\n';
+                    pile.write(line.data(), line.size());
                 }
-                line += '\n';
-                pile.write(line.data(), line.size());
+                const double dt = now() - t_pile;                          // --verbose 1: the pileup's own stage, out of write/compress
+                t_stage[8] += dt; t_mark += dt;
             }
             if (B.st[i] < 0) { n_skipped++; continue; }
             if (!a.do_gvcf || dgvcf) continue;                           // plain records, device gVCF: written below
@@ -1334,7 +1368,7 @@ int main(int argc, char** argv) {
             }
             n_sites_total += (size_t)B.ns;
             PBuf<uint8_t>::device() = devices[B.dev]; PBuf<double>::device() = devices[B.dev];      // dump buffers of this entry: next to its device, like the rest
-            if (pile_fp) { B.reads.resize((size_t)pile_cap * TS * N); memset(B.reads.data(), 0xFF, (size_t)pile_cap * B.ns * N); B.o.reads = B.reads.data(); B.o.read_capacity = pile_cap; }   // capacity of the per-read dump: the library stages at most read_cap reads; ask generously
+            if (pile_fp && !dpile) { B.reads.resize((size_t)pile_cap * TS * N); memset(B.reads.data(), 0xFF, (size_t)pile_cap * B.ns * N); B.o.reads = B.reads.data(); B.o.read_capacity = pile_cap; }   // capacity of the per-read dump: the library stages at most read_cap reads; ask generously
             if (want_errp) { B.errp.resize((size_t)pile_cap * TS * N); B.o.read_errp = B.errp.data(); B.o.read_capacity = pile_cap; }
             if (dump_pick) { B.pick.resize(TS); B.o.site_pick_err = B.pick.data(); }
             Worker* W = workers[B.dev].get();
@@ -1374,8 +1408,8 @@ int main(int argc, char** argv) {
                     (double)ci.workspace_bytes / 1e9, ci.sample_lean, ci.fused, ci.fused_split);
         }
     }
-    if (a.verbose) fprintf(stderr, "\n[timing] read input %.3f s, decode sites %.3f s, device context(s) %.3f s, waiting for the device(s) (simulation incl. PCIe, overlapped with the writer) %.3f s, encode %.3f s, write/compress %.3f s, tile buffers %.3f s, teardown %.3f s\n",
-                           t_stage[0], t_stage[1], t_stage[2], t_stage[3], t_stage[4], t_stage[5], t_stage[6], t_stage[7]);
+    if (a.verbose) fprintf(stderr, "\n[timing] read input %.3f s, decode sites %.3f s, device context(s) %.3f s, waiting for the device(s) (simulation incl. PCIe, overlapped with the writer) %.3f s, encode %.3f s, write/compress %.3f s, tile buffers %.3f s, teardown %.3f s, pileup %.3f s\n",
+                           t_stage[0], t_stage[1], t_stage[2], t_stage[3], t_stage[4], t_stage[5], t_stage[6], t_stage[7], t_stage[8]);
     char sb[512];
     snprintf(sb, sizeof sb, "\n\n-> Simulation finished successfully.\n\nSummary:\n\tNumber of samples: %d\n\tTotal number of sites simulated: %zu\n"
                             "\tNumber of sites included in simulation output file: %ld\n\tNumber of sites skipped: %ld\n", N, n_sites_total, n_out, n_skipped);

@@ -230,7 +230,12 @@ struct vgl_ctx {
         vgl_gvcf_item* d_items = nullptr; int32_t* d_counts = nullptr; int32_t* d_bdp = nullptr; int32_t* d_bpl = nullptr;
         int32_t* d_bna = nullptr; int32_t* d_bst = nullptr; int32_t* d_rst = nullptr; int32_t* d_edge = nullptr;
         void* d_gws = nullptr; int64_t d_gws_bytes = 0; uint8_t* d_btext = nullptr; int64_t d_btext_bytes = 0; int64_t* d_boff = nullptr;
+        // vgl_ctx_pileup_next: the tile's pileup formatted on the device (vgl_pileup.hip) from its read dump and DP plane; vgl_tile_wait
+        // copies the text back, which knows its size
+        vgl_pileup_tile* pile = nullptr; int32_t pile_qc = -1;
+        uint8_t* d_ptext = nullptr; int64_t d_ptext_bytes = 0; int64_t* d_poff = nullptr; void* d_pws = nullptr; int64_t d_pws_bytes = 0;
     } slot[2];
+    vgl_pileup_tile* pile_next = nullptr;                           // vgl_ctx_pileup_next: taken by the next tile call
     hipStream_t s_text = nullptr;                                   // text copies of vgl_tile_wait (never behind the next tile's copies)
     // a draw deeper than the staging capacity (vcfgl grows its read buffers, bcf_utils.cpp:618-648): the host entry points run such a tile again on
     // this sibling context, created on first need with the staging layout's largest capacity (VGL_READ_CAP_MAX reads) and tiles of at most
@@ -359,7 +364,7 @@ extern "C" int vgl_ctx_destroy(vgl_ctx* c) {
         if (S.busy && S.ev_copied) (void)hipEventSynchronize(S.ev_copied);
         for (void* q : S.d_out) if (q) (void)hipFree(q);
         void* dq[] = {S.d_gt, S.d_reads_out, S.d_errp_out, S.d_pick_out, S.d_text, S.d_toff, S.d_tws, S.d_contig, S.d_pos0, S.d_dps, S.d_items,
-                      S.d_counts, S.d_bdp, S.d_bpl, S.d_bna, S.d_bst, S.d_rst, S.d_edge, S.d_gws, S.d_btext, S.d_boff};
+                      S.d_counts, S.d_bdp, S.d_bpl, S.d_bna, S.d_bst, S.d_rst, S.d_edge, S.d_gws, S.d_btext, S.d_boff, S.d_ptext, S.d_poff, S.d_pws};
         for (void* q : dq) if (q) (void)hipFree(q);
         if (S.h_gt) (void)hipHostFree(S.h_gt);
         void* hq[] = {S.h_counts, S.h_contig, S.h_pos0};
@@ -1239,6 +1244,48 @@ static int stage_gvcf(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites, const i
     return VGL_OK;
 }
 
+extern "C" int vgl_pileup_format_impl(int32_t device, int32_t n_samples, int32_t n_sites, const int32_t* site_status, const int32_t* fmt_dp,
+                                      const uint8_t* reads, int32_t read_capacity, int32_t qual_char, const double* errp, const VglDevParams* P,
+                                      uint32_t* errflag, uint8_t* dst, int64_t dst_cap, int64_t* offsets, void* workspace, int64_t workspace_bytes,
+                                      void* hip_stream);          // vgl_pileup.hip (not exported)
+
+extern "C" int64_t vgl_ctx_pileup_bound(const vgl_ctx* c, int32_t n_sites) {
+    if (!c || n_sites < 0) return -1;
+    return vgl_pileup_bound(c->dp.n_samples, n_sites, c->dp.read_cap);
+}
+
+extern "C" int vgl_ctx_pileup_next(vgl_ctx* c, vgl_pileup_tile* p) {
+    if (!c) return fail(VGL_E_ARG, "null ctx");
+    if (p && (!p->offsets || p->text_cap < 0 || (p->text_cap > 0 && !p->text))) return fail(VGL_E_ARG, "vgl_ctx_pileup_next: null text or offsets");
+    c->pile_next = p;
+    return VGL_OK;
+}
+
+// the score byte of every read of a pileup: -1 = each read's own (or, --adjust-qs 4 with --error-qs 2, from its error probability);
+// --adjust-qs 4 with --error-qs 0 / 1: the adjusted score of error_rate (PROGRAM_WILL_ADJUST_QS_FOR_PILEUP, vcfgl.cpp:1664-1693)
+static int pileup_qual_char(const vgl_ctx* c, int32_t* qc) {
+    *qc = -1;
+    if (!(c->p.adjust_qs & 4) || c->p.error_qs == 2) return VGL_OK;
+    vgl_params p = c->p;
+    if (!c->bins_copy.empty()) p.qs_bins = c->bins_copy.data();
+    int q = -1, aq = -1;
+    const int rc = errprob_to_qs_fixed(&p, p.error_rate, &q, &aq);
+    if (rc != VGL_OK) return rc;
+    if (aq + 33 < 0 || aq + 33 > 255) return fail(VGL_E_ADJQ, "--adjust-qs 4: the adjusted score %d of the error rate is not a pileup byte", aq);
+    *qc = aq + 33;
+    return VGL_OK;
+}
+
+// the pileup formatter on the slot's device read dump and DP plane (compute stream): text into d_ptext, site offsets into d_poff;
+// a --qs-bins miss of a score lands in the tile's device flags (this runs before they are copied)
+static int enqueue_pileup(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites, const vgl_tile_out& d) {
+    const int32_t cap = d.read_capacity < c->dp.read_cap ? d.read_capacity : c->dp.read_cap;
+    const bool from_errp = (c->p.adjust_qs & 4) && c->p.error_qs == 2;
+    return vgl_pileup_format_impl(c->device, c->dp.n_samples, n_sites, (const int32_t*)S.d_out[0], (const int32_t*)S.d_out[10], d.reads, cap, S.pile_qc,
+                                  from_errp ? d.read_errp : nullptr, from_errp ? &c->dp : nullptr, from_errp ? c->d_errflag : nullptr,
+                                  S.d_ptext, S.pile->text_cap, S.d_poff, S.d_pws, S.d_pws_bytes, c->s_compute);
+}
+
 // Host buffers in, host buffers out, asynchronously: the tile's kernels are enqueued on the context's compute stream, the copies of
 // its tags back to the host on its copy stream behind them; with two tiles in flight the copies of tile t overlap the kernels of
 // tile t + 1.  Destination buffers from vgl_host_alloc() (pinned) are written by DMA directly; pageable ones work, more slowly.
@@ -1258,6 +1305,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
         for (int k = 0; k < nf; k++) text_mask |= 1u << fid[k];
         if (S.gvcf) text_mask |= 1u << 10 | 1u << 12;                  // (the blocker reads FORMAT/DP and PL)
     }
+    if (S.pile) text_mask |= 1u << 10;                                  // (the pileup formatter reads FORMAT/DP)
     S.dev_fields = 0;
     for (int f = 0; f < N_FIELDS; f++) {
         void* host = *(void**)((char*)o + FIELDS[f].off);
@@ -1277,25 +1325,29 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
         }
         *(void**)((char*)&d + FIELDS[f].off) = S.d_out[f];
     }
-    if (o->reads && o->read_capacity > 0) {
-        const size_t need = (size_t)o->read_capacity * c->max_sites * N;
+    // a pileup: the read dump (and, for --adjust-qs 4 with --error-qs 2, the error probabilities) on the device whether or not the
+    // caller also wants them back -- at the caller's capacity when it asks for a dump, else at the context's staging capacity
+    const bool pile_errp = S.pile && (c->p.adjust_qs & 4) && c->p.error_qs == 2;
+    const int32_t dump_cap = ((o->reads || o->read_errp) && o->read_capacity > 0) ? o->read_capacity : (S.pile ? c->dp.read_cap : 0);
+    if ((o->reads || S.pile) && dump_cap > 0) {
+        const size_t need = (size_t)dump_cap * c->max_sites * N;
         if (S.d_reads_out_bytes < need) {
             if (S.d_reads_out) (void)hipFree(S.d_reads_out);
             S.d_reads_out = nullptr; S.d_reads_out_bytes = 0;
             HIPCHK(hipMalloc((void**)&S.d_reads_out, need));
             S.d_reads_out_bytes = need;
         }
-        d.reads = S.d_reads_out; d.read_capacity = o->read_capacity;
+        d.reads = S.d_reads_out; d.read_capacity = dump_cap;
     }
-    if (o->read_errp && o->read_capacity > 0) {
-        const size_t need = (size_t)o->read_capacity * c->max_sites * N * sizeof(double);
+    if ((o->read_errp || pile_errp) && dump_cap > 0) {
+        const size_t need = (size_t)dump_cap * c->max_sites * N * sizeof(double);
         if (S.d_errp_out_bytes < need) {
             if (S.d_errp_out) (void)hipFree(S.d_errp_out);
             S.d_errp_out = nullptr; S.d_errp_out_bytes = 0;
             HIPCHK(hipMalloc((void**)&S.d_errp_out, need));
             S.d_errp_out_bytes = need;
         }
-        d.read_errp = S.d_errp_out; d.read_capacity = o->read_capacity;
+        d.read_errp = S.d_errp_out; d.read_capacity = dump_cap;
     }
     if (o->site_pick_err) {
         if (!S.d_pick_out) HIPCHK(hipMalloc((void**)&S.d_pick_out, (size_t)c->max_sites * sizeof(double)));
@@ -1319,8 +1371,25 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
             S.d_text_bytes = S.text_cap;
         }
     }
+    if (S.pile) {
+        const int64_t ws = vgl_pileup_workspace_bytes((int32_t)N, c->max_sites);
+        if (S.d_pws_bytes < ws) {
+            if (S.d_pws) (void)hipFree(S.d_pws);
+            S.d_pws = nullptr; S.d_pws_bytes = 0;
+            HIPCHK(hipMalloc(&S.d_pws, (size_t)ws));
+            S.d_pws_bytes = ws;
+        }
+        if (!S.d_poff) HIPCHK(hipMalloc((void**)&S.d_poff, sizeof(int64_t) * ((size_t)c->max_sites + 1)));
+        if (S.d_ptext_bytes < S.pile->text_cap) {
+            if (S.d_ptext) (void)hipFree(S.d_ptext);
+            S.d_ptext = nullptr; S.d_ptext_bytes = 0;
+            HIPCHK(hipMalloc((void**)&S.d_ptext, (size_t)S.pile->text_cap));
+            S.d_ptext_bytes = S.pile->text_cap;
+        }
+    }
     int rc = vgl_simulate_tile_device(c, site0, n_sites, S.d_gt, &d, c->s_compute);
     if (rc) return rc;
+    if (S.pile && (rc = enqueue_pileup(c, S, n_sites, d)) != VGL_OK) return rc;
     // this tile's device error flags, then a clean word for the next tile
     HIPCHK(hipMemcpyAsync(S.h_flag, c->d_errflag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute));
     HIPCHK(hipMemsetAsync(c->d_errflag, 0, sizeof(uint32_t), c->s_compute));
@@ -1333,11 +1402,12 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
         if (!host) continue;
         HIPCHK(hipMemcpyAsync(host, S.d_out[f], field_count(c, FIELDS[f].kind, (size_t)n_sites) * FIELDS[f].esz, hipMemcpyDeviceToHost, c->s_copy));
     }
-    if (d.reads) HIPCHK(hipMemcpyAsync(o->reads, d.reads, (size_t)o->read_capacity * n_sites * N, hipMemcpyDeviceToHost, c->s_copy));
-    if (d.read_errp && c->dp.error_qs == 2) HIPCHK(hipMemcpyAsync(o->read_errp, d.read_errp, (size_t)o->read_capacity * n_sites * N * sizeof(double), hipMemcpyDeviceToHost, c->s_copy));
+    if (d.reads && o->reads && o->read_capacity > 0) HIPCHK(hipMemcpyAsync(o->reads, d.reads, (size_t)o->read_capacity * n_sites * N, hipMemcpyDeviceToHost, c->s_copy));
+    if (d.read_errp && o->read_errp && o->read_capacity > 0 && c->dp.error_qs == 2) HIPCHK(hipMemcpyAsync(o->read_errp, d.read_errp, (size_t)o->read_capacity * n_sites * N * sizeof(double), hipMemcpyDeviceToHost, c->s_copy));
     if (d.site_pick_err) HIPCHK(hipMemcpyAsync(o->site_pick_err, d.site_pick_err, (size_t)n_sites * sizeof(double), hipMemcpyDeviceToHost, c->s_copy));
     if (S.text) HIPCHK(hipMemcpyAsync(S.h_toff, S.d_toff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, c->s_copy));
     if (S.gvcf && (rc = copy_gvcf_small(c, S, n_sites, c->s_copy)) != VGL_OK) return rc;
+    if (S.pile) HIPCHK(hipMemcpyAsync(S.pile->offsets, S.d_poff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, c->s_copy));
     HIPCHK(hipEventRecord(S.ev_copied, c->s_copy));
     return VGL_OK;
 }
@@ -1352,6 +1422,8 @@ struct GvcfReq { const int32_t* contig; const int64_t* pos0; const int32_t* dps;
 static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o, int32_t* ticket,
                       uint8_t* text, int64_t text_cap, int64_t* toff, bool want_text, const GvcfReq* gq = nullptr) {
     if (!c || !o || !ticket) return fail(VGL_E_ARG, "null argument");
+    vgl_pileup_tile* const pile = c->pile_next;                     // (taken by this call, whether it succeeds or not)
+    c->pile_next = nullptr;
     if (gq) {
         const vgl_gvcf_tile* g = gq->g;
         if (!g || !g->items || !g->record_offsets || !g->block_offsets || g->text_cap < 0 || (g->text_cap > 0 && !g->text) || gq->n_dps < 0 ||
@@ -1379,11 +1451,14 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     S.site0 = site0; S.n_sites = n_sites; S.o = *o;
     S.text = want_text; S.h_text = text; S.text_cap = text_cap; S.h_toff = toff;
     S.gvcf = gq != nullptr; S.h_gv = gq ? gq->g : nullptr;
+    S.pile = pile;
+    if (pile) { const int rc = pileup_qual_char(c, &S.pile_qc); if (rc != VGL_OK) { S.pile = nullptr; return rc; } }
     if (gq) S.dps.assign(gq->dps, gq->dps + gq->n_dps);
-    if ((want_text || gq) && !c->s_text) HIPCHK(hipStreamCreateWithFlags(&c->s_text, hipStreamNonBlocking));
+    if ((want_text || gq || pile) && !c->s_text) HIPCHK(hipStreamCreateWithFlags(&c->s_text, hipStreamNonBlocking));
     if (n_sites == 0) {
         if (want_text) toff[0] = 0;
         if (gq) { gq->g->record_offsets[0] = 0; gq->g->block_offsets[0] = 0; }
+        if (pile) pile->offsets[0] = 0;
         HIPCHK(hipEventRecord(S.ev_copied, c->s_copy));
     } else {
         const int rc = enqueue_host_tile(c, S, site0, n_sites, gt, o, gq ? gq->contig : nullptr, gq ? gq->pos0 : nullptr);
@@ -1420,10 +1495,10 @@ extern "C" int vgl_simulate_tile_gvcf_async(vgl_ctx* c, int64_t site0, int32_t n
 // A tile whose device flags report a draw deeper than the staging capacity, run again through the sibling context (host buffers: the slot's own copy of
 // the genotypes, the caller's output arrays), VGL_DEEP_TILE_SITES sites at a time -- every tag array of a tile is site-major, so a sub-tile is a slice of
 // it.  Returns VGL_E_CAPACITY (quietly) where that cannot be done: serial mode (the streams have moved on), a per-read dump (read-major planes of the
-// caller's own capacity), a capacity already at the layout's maximum, or no memory for the sibling.
+// caller's own capacity) or a pileup (formatted from such planes), a capacity already at the layout's maximum, or no memory for the sibling.
 static int deep_ctx(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     const VglDevParams& D = c->dp;
-    if (D.serial || D.read_cap >= VGL_READ_CAP_MAX || (S.o.read_capacity > 0 && (S.o.reads || S.o.read_errp))) return VGL_E_CAPACITY;
+    if (D.serial || D.read_cap >= VGL_READ_CAP_MAX || (S.o.read_capacity > 0 && (S.o.reads || S.o.read_errp)) || S.pile) return VGL_E_CAPACITY;
     if (!c->deep) {
         vgl_params p = c->p;
         std::vector<double> depths; std::vector<int32_t> bins;
@@ -1501,6 +1576,23 @@ static int finish_gvcf(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     return VGL_OK;
 }
 
+// pileup: the text crosses the link (only the bytes produced); offsets[n_sites] = -1: a dp beyond the dump's capacity
+static int finish_pileup(vgl_ctx* c, vgl_ctx::HostSlot& S) {
+    vgl_pileup_tile* p = S.pile;
+    const int64_t total = p->offsets[S.n_sites];
+    p->text_needed = total;
+    if (total < 0)
+        return fail(VGL_E_CAPACITY, "a simulated read depth exceeded the capacity of the tile's read dump (%d reads per sample): no pileup", c->dp.read_cap);
+    if (total > p->text_cap)
+        return fail(VGL_E_CAPACITY, "the tile's pileup needs %lld bytes, text_cap is %lld (text_needed holds the size; vgl_ctx_pileup_bound bounds it)",
+                    (long long)total, (long long)p->text_cap);
+    if (total > 0) {
+        HIPCHK(hipMemcpyAsync(p->text, S.d_ptext, (size_t)total, hipMemcpyDeviceToHost, c->s_text));
+        HIPCHK(hipStreamSynchronize(c->s_text));
+    }
+    return VGL_OK;
+}
+
 extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
     if (!c || ticket < 0 || ticket > 1) return fail(VGL_E_ARG, "bad ticket");
     vgl_ctx::HostSlot& S = c->slot[ticket];
@@ -1508,6 +1600,8 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipEventSynchronize(S.ev_copied));
     S.busy = false;
+    int rc2 = VGL_OK;
+    if (S.pile && S.n_sites == 0) S.pile->text_needed = 0;
     if ((*S.h_flag & VGL_DEVERR_CAPACITY) && S.n_sites > 0) {
         const bool dev_text = S.text || S.gvcf;
         const int rc = dev_text ? deep_rerun_text(c, S) : deep_rerun(c, S);
@@ -1515,7 +1609,9 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
         if (rc == VGL_E_CAPACITY) return flags_to_rc(c, *S.h_flag);
     } else {
         const int rc = flags_to_rc(c, *S.h_flag);
-        if (rc != VGL_OK || !(S.text || S.gvcf)) return rc;
+        if (rc != VGL_OK) return rc;
+        if (S.pile && (rc2 = finish_pileup(c, S)) != VGL_OK) return rc2;
+        if (!(S.text || S.gvcf)) return VGL_OK;
     }
     if (S.gvcf) return finish_gvcf(c, S);
     // text: only the bytes the tile produced cross the link

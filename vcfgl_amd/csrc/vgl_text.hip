@@ -350,6 +350,13 @@ int64_t per_sample_bound(const vgl_text_field* f, int32_t nf, int32_t max_allele
 
 extern "C" int vgl_pack_set_error(int code, const char* msg);       // vgl_host.cpp: records the message for vgl_last_error()
 
+// the site scan alone (k_text_scan: offsets[0 .. n_sites] from the site lengths in offsets[0 .. n_sites)); vgl_pileup.hip places its sites
+// with it (not exported)
+extern "C" int vgl_text_scan_launch(int32_t n_sites, int64_t* offsets, void* hip_stream) {
+    hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(SCAN_NT), 0, (hipStream_t)hip_stream, n_sites, offsets);
+    return hipGetLastError() != hipSuccess ? -1 : 0;
+}
+
 extern "C" int64_t vgl_text_bound(int32_t n_samples, int32_t n_sites, const vgl_text_field* fields, int32_t n_fields, int32_t max_alleles) {
     if (n_samples < 0 || n_sites < 0 || n_fields < 0 || n_fields > VGL_TEXT_MAX_FIELDS || (n_fields > 0 && !fields) || max_alleles < 1 || max_alleles > 5) return -1;
     int64_t hdr = 2;
