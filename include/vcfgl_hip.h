@@ -570,6 +570,44 @@ VGL_API int vgl_pileup_format_device(int32_t device, int32_t n_samples, int32_t 
 VGL_API int64_t vgl_ctx_pileup_bound(const vgl_ctx* ctx, int32_t n_sites);
 VGL_API int vgl_ctx_pileup_next(vgl_ctx* ctx, vgl_pileup_tile* p);
 
+/* ---- the FORMAT part of BCF records on the device (ABI 7, additive) -------------------------------------------------------------
+ * The N-wide part of a BCF record -- the `indiv` block the host writer (BCF 2.2 section 6.3.3) puts behind the shared block -- encoded
+ * from the tile's FORMAT arrays where they are computed.  For every site i with site_status[i] >= 0 and every field, in the order given:
+ *     the typed key           0x11 id (id <= 127), 0x12 id16 (<= 32767), 0x13 id32
+ *     the size/type byte      (n << 4 | bt) for n < 15; (0xF0 | bt) followed by the typed integer n for n >= 15; bt alone for n = 0
+ *     n(i) * n_samples values int32 fields in the narrowest of int8 (max <= 127, min >= -120), int16 (max <= 32767, min >= -32760) and
+ *                             int32 that holds the record's range -- VGL_INT32_MISSING and the vector end INT32_MIN + 1 are left out of
+ *                             the range and become 0x80 / 0x8000 and 0x81 / 0x8001; a vector without an ordinary value is int8 --
+ *                             float32 fields as their bit patterns, untouched; little endian
+ * A skipped site (site_status < 0) has no bytes.  The bytes are identical to the host writer's (htslib's choices).
+ *   vgl_bcf_field             one FORMAT field: value k of sample s of site i at ((T*)base)[i * site_stride + s * n(i) + k] -- the
+ *                             VGL_LAYOUT_SAMPLE_MAJOR slabs -- with n(i) by `count`, as in vgl_text_field: VGL_TEXT_ONE / _PER_G / _PER_A;
+ *                             key_id = the key's index in the output header's string dictionary.
+ *   vgl_bcf_bound             largest encoding of n_sites sites with at most max_alleles alleles (pure host arithmetic; -1 on bad input).
+ *   vgl_bcf_workspace_bytes   device workspace of a call (pure host arithmetic; -1 on bad input).
+ *   vgl_bcf_encode_device     the contract of vgl_text_format_device: every pointer is device memory of `device`, work is enqueued on
+ *                             `hip_stream` without synchronising; offsets[i] = where site i's bytes start in dst, offsets[n_sites] = the
+ *                             total.  When the total exceeds dst_cap NOTHING is written to dst and offsets[n_sites] says what is needed.
+ *   vgl_ctx_bcf_keys          key_ids[7] = the output header's dictionary ids of DP, GL, PL, GP, AD, ADF, ADR (entries of tags the
+ *                             context does not write are ignored; n must be 7).  From then on vgl_simulate_tile_text_async and
+ *                             vgl_simulate_tile_gvcf_async of this context deliver the sample data as these typed vectors instead of
+ *                             text, in the same buffers and through the same offsets arrays (gVCF blocks: the fields PL then DP), and
+ *                             vgl_ctx_text_bound / vgl_ctx_gvcf_text_bound bound this encoding.  NULL switches back to text.  Call it
+ *                             while no tile of the context is in flight. */
+typedef struct vgl_bcf_field {
+    int32_t     key_id;       /* index of the FORMAT key in the header's dictionary */
+    int32_t     is_float;     /* 1: float32 values, 0: int32                       */
+    int32_t     count;        /* VGL_TEXT_*                                        */
+    const void* base;         /* device memory                                     */
+    int64_t     site_stride;  /* elements from one site's slab to the next         */
+} vgl_bcf_field;
+VGL_API int64_t vgl_bcf_bound(int32_t n_samples, int32_t n_sites, const vgl_bcf_field* fields, int32_t n_fields, int32_t max_alleles);
+VGL_API int64_t vgl_bcf_workspace_bytes(int32_t n_samples, int32_t n_sites);
+VGL_API int vgl_bcf_encode_device(int32_t device, const vgl_bcf_field* fields, int32_t n_fields, int32_t n_samples, int32_t n_sites,
+                                  const int32_t* site_status, const int32_t* n_alleles, uint8_t* dst, int64_t dst_cap, int64_t* offsets,
+                                  void* workspace, int64_t workspace_bytes, void* hip_stream);
+VGL_API int vgl_ctx_bcf_keys(vgl_ctx* ctx, const int32_t* key_ids, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

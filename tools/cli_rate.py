@@ -2,8 +2,11 @@
 """End-to-end rate of the host program (VCF text in -> GPU simulation -> file out) per output mode and
 --threads value, on a synthetic input of SITES x SAMPLES phased binary genotypes.  Everything is
 inside the measured wall time: process start, input parsing, PCIe copies, record encoding, compression.
-usage (GPU box): python tools/cli_rate.py [sites] [samples]"""
-import os, subprocess, sys, tempfile, time
+usage (GPU box): python tools/cli_rate.py [sites] [samples]
+CLI_BCF_AB=1: every binary mode of the list is run with --device-bcf 0 and --device-bcf 1, alternating, CLI_REPS times each (default 3);
+both settings must write the same stream (decompressed, the ##source= lines taken out): checked on every pair.  CLI_PARENT_BIN=path
+alternates another build of the program (without the flag) with this one at --device-bcf 0 instead: the run-to-run spread of the two."""
+import gzip, hashlib, os, struct, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
@@ -27,6 +30,52 @@ flags = "--seed 42 --depth 20 -e 0.01 --error-qs 2 --beta-variance 1e-5 -GL 2".s
 runs = (("v", 0), ("v", 1), ("u", 0), ("u", 1), ("u", 16), ("b", 0), ("b", 1), ("b", 64))
 if os.environ.get("CLI_MODES"):                              # e.g. CLI_MODES="u:0,u:16"
     runs = tuple((m.split(":")[0], int(m.split(":")[1])) for m in os.environ["CLI_MODES"].split(","))
+
+
+def bcf_digest(fn):
+    """sha1 of a BCF stream without the ##source= lines of its header"""
+    with open(fn, "rb") as f:
+        raw = f.read()
+    if raw[:2] == b"\x1f\x8b":
+        raw = gzip.decompress(raw)
+    l_text = struct.unpack_from("<I", raw, 5)[0]
+    h = hashlib.sha1(b"\n".join(l for l in raw[9:9 + l_text].split(b"\n") if not l.startswith(b"##source=")))
+    h.update(memoryview(raw)[9 + l_text:])
+    return h.hexdigest()
+
+
+def ab(mode, threads):
+    """alternating runs of two settings of one binary mode: times, [timing] and [device] lines, output size, equal streams"""
+    parent = os.environ.get("CLI_PARENT_BIN")
+    settings = [("parent", parent, []), ("--device-bcf 0", BIN, ["--device-bcf", "0"])] if parent else \
+               [("--device-bcf 0", BIN, ["--device-bcf", "0"]), ("--device-bcf 1", BIN, ["--device-bcf", "1"])]
+    th = ["--threads", str(threads)] if threads else []
+    times, digests = {k: [] for k, _, _ in settings}, {}
+    for rep in range(int(os.environ.get("CLI_REPS", "3"))):
+        for k, (name, prog, extra) in enumerate(settings):
+            out = os.path.join(d, f"ab_{mode}{threads}_{k}")
+            t0 = time.perf_counter()
+            r = subprocess.run([prog, "-i", vcf, "-o", out, "-O", mode, "--verbose", "1"] + th + flags + extra, capture_output=True, text=True)
+            dt = time.perf_counter() - t0
+            assert r.returncode == 0, r.stderr[-800:]
+            times[name].append(dt)
+            print(f"-O {mode} --threads {threads:3d} {name:16s} run {rep}: {dt:7.2f} s  {S * N / dt:10.3e} evals/s  output {os.path.getsize(out + '.bcf') / 1e6:8.1f} MB", flush=True)
+            if rep == 0:
+                for l in r.stderr.splitlines():
+                    if l.startswith("[timing]") or l.startswith("[device"):
+                        print("    " + l, flush=True)
+                digests[name] = bcf_digest(out + ".bcf")
+            os.remove(out + ".bcf")
+    assert len(set(digests.values())) == 1, f"-O {mode}: the two settings wrote different streams"
+    for name, ts in times.items():
+        print(f"  {name:16s} min {min(ts):.2f} s  median {sorted(ts)[len(ts) // 2]:.2f} s  max {max(ts):.2f} s  spread {(max(ts) - min(ts)) / min(ts) * 100:.1f} %", flush=True)
+
+
+if os.environ.get("CLI_BCF_AB") or os.environ.get("CLI_PARENT_BIN"):
+    for mode, threads in runs:
+        if mode in ("u", "b"):
+            ab(mode, threads)
+    sys.exit(0)
 for mode, threads in runs:
     out = os.path.join(d, f"o_{mode}{threads}")
     t0 = time.perf_counter()

@@ -6,10 +6,12 @@ and for -O z --device-bgzf 1, on three shapes:
   c  1000 samples, depth 30, -e 0, --gvcf-dps 10,12,14,16: short blocks that alternate
 Everything is inside the wall time (process start, input parsing, PCIe, encoding, compression); the program's own [timing] line follows.
 Both settings must write the same body (the ##source line names the flag): checked on every pair.
+GVCF_RATE_BCF=1 measures the binary modes instead: -O u and -O b --device-bgzf 1, --device-gvcf 0 --device-bcf 0 (the host blocker, whose
+blocks go through a text line) against --device-gvcf 1 --device-bcf 1; the decompressed streams must be equal but for ##source=.
 usage (GPU box): python tools/gvcf_rate.py [shapes, e.g. abc] [POSITIONS]
 GVCF_RATE_DIR=dir keeps the inputs there (in_<shape>.vcf); GVCF_RATE_WRITE_ONLY=1 writes them and prints each shape's flags, e.g. for
 a profiler run of one vcfgl_hip process (with VCFGL_HIP_NORMAL_EXIT=1, so that the profiler's exit handlers run)."""
-import gzip, os, subprocess, sys, tempfile, time
+import gzip, hashlib, os, struct, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
@@ -53,22 +55,37 @@ for name in SHAPES:
     print(f"shape {name}: {sh['evals']:.3e} evaluations ({sh['flags']})", flush=True)
     if os.environ.get("GVCF_RATE_WRITE_ONLY"):
         continue
-    for mode, extra in (("v", []), ("z", ["--device-bgzf", "1"])):
+    BCF = bool(os.environ.get("GVCF_RATE_BCF"))
+    for mode, extra in ((("u", []), ("b", ["--device-bgzf", "1"])) if BCF else (("v", []), ("z", ["--device-bgzf", "1"]))):
         bodies = []
         for dev in (0, 1):
             out = os.path.join(d, f"o_{name}{mode}{dev}")
             argv = [BIN, "-i", vcf, "-o", out, "-O", mode, "--seed", "42", "--verbose", "1", "--device-gvcf", str(dev)] + extra + sh["flags"].split()
+            if BCF:
+                argv += ["--device-bcf", str(dev)]
             t0 = time.perf_counter()
             r = subprocess.run(argv, capture_output=True, text=True)
             dt = time.perf_counter() - t0
             assert r.returncode == 0, r.stderr[-800:]
-            fn = out + (".vcf" if mode == "v" else ".vcf.gz")
-            with (gzip.open if mode == "z" else open)(fn, "rb") as f:
-                body = [l for l in f.read().split(b"\n") if not l.startswith(b"##source=")]
-            bodies.append(body)
-            n_blk = sum(1 for l in body if b"MIN_DP=" in l)
-            print(f"  -O {mode} {' '.join(extra):16s} --device-gvcf {dev}: {dt:7.2f} s  {sh['evals'] / dt:10.3e} evals/s  "
-                  f"{len(body) - 1} lines, {n_blk} blocks, {os.path.getsize(fn) / 1e6:8.1f} MB", flush=True)
+            fn = out + (".bcf" if BCF else ".vcf" if mode == "v" else ".vcf.gz")
+            if BCF:                                                     # the stream without the ##source= lines of its header
+                with (gzip.open if mode == "b" else open)(fn, "rb") as f:
+                    raw = f.read()
+                l_text = struct.unpack_from("<I", raw, 5)[0]
+                hdr = b"\n".join(l for l in raw[9:9 + l_text].split(b"\n") if not l.startswith(b"##source="))
+                bodies.append(hashlib.sha1(hdr + raw[9 + l_text:]).hexdigest())
+                print(f"  -O {mode} {' '.join(extra):16s} --device-gvcf {dev} --device-bcf {dev}: {dt:7.2f} s  {sh['evals'] / dt:10.3e} evals/s  "
+                      f"{os.path.getsize(fn) / 1e6:8.1f} MB", flush=True)
+                for l in r.stderr.splitlines():
+                    if l.startswith("[device"):
+                        print("    " + l, flush=True)
+            else:
+                with (gzip.open if mode == "z" else open)(fn, "rb") as f:
+                    body = [l for l in f.read().split(b"\n") if not l.startswith(b"##source=")]
+                bodies.append(body)
+                n_blk = sum(1 for l in body if b"MIN_DP=" in l)
+                print(f"  -O {mode} {' '.join(extra):16s} --device-gvcf {dev}: {dt:7.2f} s  {sh['evals'] / dt:10.3e} evals/s  "
+                      f"{len(body) - 1} lines, {n_blk} blocks, {os.path.getsize(fn) / 1e6:8.1f} MB", flush=True)
             print("    " + [l for l in r.stderr.splitlines() if l.startswith("[timing]")][-1], flush=True)
             os.remove(fn)
-        assert bodies[0] == bodies[1], f"shape {name} -O {mode}: --device-gvcf 1 wrote other bytes"
+        assert bodies[0] == bodies[1], f"shape {name} -O {mode}: the device settings wrote other bytes"

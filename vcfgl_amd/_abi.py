@@ -95,6 +95,7 @@ EXPORTS = [
     "vgl_text_bound", "vgl_text_workspace_bytes", "vgl_text_format_device", "vgl_ctx_text_bound", "vgl_simulate_tile_text_async",
     "vgl_gvcf_workspace_bytes", "vgl_gvcf_blocks_device", "vgl_ctx_gvcf_text_bound", "vgl_simulate_tile_gvcf_async",
     "vgl_pileup_bound", "vgl_pileup_workspace_bytes", "vgl_pileup_format_device", "vgl_ctx_pileup_bound", "vgl_ctx_pileup_next",
+    "vgl_bcf_bound", "vgl_bcf_workspace_bytes", "vgl_bcf_encode_device", "vgl_ctx_bcf_keys",
 ]
 VGL_PACK_ROW, VGL_PACK_ROWS_G, VGL_PACK_ROWS_A = 0, 1, 2
 
@@ -109,6 +110,10 @@ VGL_TEXT_MAX_FIELDS = 8
 
 class TextField(C.Structure):
     _fields_ = [("key", C.c_char_p), ("is_float", C.c_int32), ("count", C.c_int32), ("base", C.c_void_p), ("site_stride", C.c_int64)]
+
+
+class BcfField(C.Structure):
+    _fields_ = [("key_id", C.c_int32), ("is_float", C.c_int32), ("count", C.c_int32), ("base", C.c_void_p), ("site_stride", C.c_int64)]
 
 
 VGL_GVCF_RECORD, VGL_GVCF_BLOCK = 0, 1
@@ -236,6 +241,13 @@ def load_library(hooks=False):
     lib.vgl_ctx_pileup_bound.restype = C.c_int64
     lib.vgl_ctx_pileup_bound.argtypes = [C.c_void_p, C.c_int32]
     lib.vgl_ctx_pileup_next.argtypes = [C.c_void_p, C.POINTER(PileupTile)]
+    lib.vgl_bcf_bound.restype = C.c_int64
+    lib.vgl_bcf_bound.argtypes = [C.c_int32, C.c_int32, C.POINTER(BcfField), C.c_int32, C.c_int32]
+    lib.vgl_bcf_workspace_bytes.restype = C.c_int64
+    lib.vgl_bcf_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.vgl_bcf_encode_device.argtypes = [C.c_int32, C.POINTER(BcfField), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vgl_ctx_bcf_keys.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

@@ -287,6 +287,33 @@ class Sink {
         finish(shared, indiv, out);
     }
 
+    // --device-bcf 1: the head of a binary record whose FORMAT part (`l_indiv` bytes, `n_fmt` fields) was encoded on the device --
+    // l_shared, l_indiv and the shared block of the eight fixed columns; the caller appends the device's bytes with put()
+    void encode_head(const std::string& shared8, uint32_t n_fmt, size_t l_indiv, std::string& out) const {
+        if (!binary()) fail("internal: encode_head needs a binary output mode");
+        std::vector<std::string> col; split(shared8, '\t', col);
+        if (col.size() != 8) fail("internal: shared part needs 8 columns");
+        std::string shared;
+        encode_shared(col, n_fmt, shared);
+        put_u32(out, (uint32_t)shared.size()); put_u32(out, (uint32_t)l_indiv);
+        out += shared;
+    }
+    // index of a FILTER / INFO / FORMAT key in the output header's string dictionary (binary modes)
+    int32_t key_id(const char* key) const { return (int32_t)dict_id(key); }
+    // one integer FORMAT field as encode_rec writes it: the typed key, the size/type byte(s) and `total` values of an n-per-sample
+    // vector in the type their range asks for (missing and vector-end values left out of the range)
+    static void encode_int_field(std::string& out, int32_t key, int n, const int32_t* v, size_t total) {
+        enc_int1(out, key);
+        int32_t mx = INT32_MIN, mn = INT32_MAX;
+        for (size_t j = 0; j < total; j++) {
+            if (v[j] == I32_MISSING || v[j] == I32_VEND) continue;
+            if (v[j] > mx) mx = v[j]; if (v[j] < mn) mn = v[j];
+        }
+        const int bt = int_type(mn, mx);
+        enc_size(out, n, bt);
+        put_typed_ints(out, v, total, bt);
+    }
+
     void close() {
         if (!fp) return;
         if (mode == 'z' || mode == 'b') bg.close();

@@ -61,6 +61,7 @@ struct Args {
     bool threads_given = false;
     int device_bgzf = 0;               // --device-bgzf 1: BGZF streams compressed on the first device of the run
     int device_text = 0;               // --device-text 1: the sample columns of VCF text records formatted on the device
+    int device_bcf = 0;                // --device-bcf 1: the FORMAT part of BCF records (-O u / -O b) encoded on the device
     int device_gvcf = 0;               // --device-gvcf 1: -doGVCF 1 blocks built and their / the records' sample columns formatted on the device
     int device_pileup = 0;             // --device-pileup 1: the N-wide part of -printPileup 1's lines formatted on the device
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
@@ -102,7 +103,12 @@ static const char USAGE[] =
     "                   or -O z, refused with -doGVCF 1 and --depth inf; a run without a GPU fails instead of falling back]\n"
     "                   --device-gvcf 0|1 [0: -doGVCF 1 blocks built on the host, site by site; 1: on the device that simulated the tile,\n"
     "                   with the sample columns of records and blocks formatted there (blocks that cross a tile are merged on the host).\n"
-    "                   Same bytes either way; needs -doGVCF 1 and -O v or -O z, refused with --depth inf; a run without a GPU fails]\n"
+    "                   Same bytes either way; needs -doGVCF 1 and -O v or -O z (-O u / -O b with --device-bcf 1), refused with --depth inf;\n"
+    "                   a run without a GPU fails]\n"
+    "                   --device-bcf 0|1 [0: the FORMAT arrays of -O u / -O b records typed and narrowed on the host; 1: encoded as BCF typed\n"
+    "                   vectors on the device that simulated the tile, and the encoded bytes cross the link instead of the FORMAT arrays.\n"
+    "                   Same bytes either way; needs -O u or -O b, refused with --depth inf and with -doGVCF 1 unless --device-gvcf 1 is\n"
+    "                   given too (which it then allows with -O u / -O b); a run without a GPU fails instead of falling back]\n"
     "                   --device-pileup 0|1 [0: -printPileup 1's lines formatted on the host from the read dump; 1: their sample columns\n"
     "                   formatted on the device that simulated the tile, and the text crosses the link instead of the read dump.  Same\n"
     "                   bytes either way; needs -printPileup 1, refused with --depth inf; a run without a GPU fails instead of falling back]\n"
@@ -185,6 +191,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--device-bgzf") a.device_bgzf = I(v);
         else if (f == "--device-text") a.device_text = I(v);
         else if (f == "--device-gvcf") a.device_gvcf = I(v);
+        else if (f == "--device-bcf") a.device_bcf = I(v);
         else if (f == "--device-pileup") a.device_pileup = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
@@ -195,6 +202,7 @@ static Args parse_args(int argc, char** argv) {
     if (!a.have_depth && a.depths_fn.empty()) die("Average per-site read depth value is required. Please set it using --depth or --depths-file and re-run.");
     if (a.depths_fn.empty()) range(a.depth, 0.0, 500.0, "--depth");
     if (a.device_gvcf == 1 && a.depth_inf) die("--device-gvcf 1 is not supported with --depth inf (no tile is simulated).");
+    if (a.device_bcf == 1 && a.depth_inf) die("--device-bcf 1 is not supported with --depth inf (no tile is simulated).");
     if (a.depth_inf) {                                                          // io.cpp:781-850, 1011-1018
         if (a.rm_invar & 4) die("[--rm-invar-sites %d] Cannot skip invariable sites when --depth inf is set.", a.rm_invar);
         if (a.do_gvcf) die("[-doGVCF 1] Cannot output gVCF when --depth inf is set.");
@@ -246,7 +254,14 @@ static Args parse_args(int argc, char** argv) {
     range(a.device_gvcf, 0, 1, "--device-gvcf");
     if (a.device_gvcf) {                                        // (checked before any GPU work: nothing is written)
         if (!a.do_gvcf) die("--device-gvcf 1 builds gVCF blocks: it needs -doGVCF 1.");
-        if (a.output_mode != "v" && a.output_mode != "z") die("--device-gvcf 1 writes gVCF text: it needs -O v or -O z (found -O %s).", a.output_mode.c_str());
+        if (a.output_mode != "v" && a.output_mode != "z" && a.device_bcf != 1)
+            die("--device-gvcf 1 writes gVCF text: it needs -O v or -O z (found -O %s).", a.output_mode.c_str());
+    }
+    range(a.device_bcf, 0, 1, "--device-bcf");
+    if (a.device_bcf) {                                         // (checked before any GPU work: nothing is written)
+        if (a.output_mode != "u" && a.output_mode != "b") die("--device-bcf 1 encodes BCF records: it needs -O u or -O b (found -O %s).", a.output_mode.c_str());
+        if (a.do_gvcf && !a.device_gvcf)
+            die("--device-bcf 1 is not supported with -doGVCF 1 alone (the host blocker reads the FORMAT arrays of every site); add --device-gvcf 1.");
     }
     range(a.device_pileup, 0, 1, "--device-pileup");
     if (a.device_pileup) {                                      // (checked before any GPU work: nothing is written)
@@ -807,6 +822,17 @@ int main(int argc, char** argv) {
         for (int i = 2; i < argc; i++) printf("%.17g\n", host_qs_to_errprob(atoi(argv[i])));
         return 0;
     }
+    if (argc >= 4 && !strcmp(argv[1], "--encode-ints")) {
+        // self-test hook of the BCF writer's integer vectors: --encode-ints <dictionary id> <n> [<int> | . | e ...] prints, in hex, the
+        // typed key, the size/type byte(s) and the values ("." missing, "e" vector end) in the type the writer picks for their range
+        std::vector<int32_t> v;
+        for (int i = 4; i < argc; i++) v.push_back(!strcmp(argv[i], ".") ? VGL_INT32_MISSING : !strcmp(argv[i], "e") ? INT32_MIN + 1 : (int32_t)strtol(argv[i], NULL, 10));
+        std::string b;
+        vsink::Sink::encode_int_field(b, (int32_t)strtol(argv[2], NULL, 10), atoi(argv[3]), v.data(), v.size());
+        for (unsigned char c : b) printf("%02x", c);
+        printf("\n");
+        return 0;
+    }
     if (argc >= 5 && !strcmp(argv[1], "--encode-selftest")) {
         // self-test hook of the BCF writer: --encode-selftest <mode> <out path> <int> [<int> ...] writes one record whose
         // FORMAT/X holds the given integers for sample s1 (and their reverse for s2) and INFO/Y the same list
@@ -951,6 +977,7 @@ int main(int argc, char** argv) {
     p.add_fmt_adf = a.add_fmt_adf; p.add_info_adf = a.add_info_adf; p.add_fmt_adr = a.add_fmt_adr; p.add_info_adr = a.add_info_adr;
     int TS = a.tile_sites > 0 ? a.tile_sites : 4096;
     const bool dpile = a.device_pileup != 0;                   // --device-pileup 1: the pileup's sample columns come from the device
+    const bool dbcf = a.device_bcf != 0;                       // --device-bcf 1: the FORMAT part of BCF records comes from the device
     // per-read dump rows: the library's own staging capacity (vgl_host.cpp: depth + 8 sqrt(depth) + 16)
     double dmax = a.depth; for (double d : a.depths) dmax = std::max(dmax, d); if (!(dmax >= 0)) dmax = 0;
     const int pile_cap = (((int)ceil(dmax + 8.0 * sqrt(dmax) + 16.0)) + 3) & ~3;
@@ -1001,6 +1028,14 @@ int main(int argc, char** argv) {
         // BGZF compression threads: --threads as in the reference; when it is not given, up to 8 (same bytes either way)
         out.open(a.out_prefix + ext, mode, hdr, vcf.samples, a.threads_given ? a.threads : (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())), bgzf_dev);
     }
+    int n_fmt = 0;                                              // FORMAT fields of a simulated record
+    if (dbcf) {                                                 // dictionary ids of the FORMAT keys: the device writes them as typed keys
+        const char* keys[7] = {"DP", "GL", "PL", "GP", "AD", "ADF", "ADR"};
+        const int on[7] = {a.add_fmt_dp, a.add_gl, a.add_pl, a.add_gp, a.add_fmt_ad, a.add_fmt_adf, a.add_fmt_adr};
+        int32_t ids[7];
+        for (int k = 0; k < 7; k++) { ids[k] = on[k] ? out.key_id(keys[k]) : 0; n_fmt += on[k] ? 1 : 0; }
+        for (int d = 0; d < D; d++) if (vgl_ctx_bcf_keys(ctxs[d], ids, 7) != VGL_OK) die("--device-bcf 1: %s", vgl_last_error());
+    }
     FILE* pile_fp = nullptr; vsink::Bgzf pile;            // the reference writes the pileup through htslib's BGZF (vcfgl.cpp:1776-1783)
     if (a.print_pileup) {
         pile_fp = fopen((a.out_prefix + ".pileup.gz").c_str(), "wb"); if (!pile_fp) die("Could not open pileup output");
@@ -1022,7 +1057,8 @@ int main(int argc, char** argv) {
 
     // ---- tile buffers (host side of vgl_tile_out): only what this run prints is requested from the device
     // --device-text 1: the FORMAT arrays stay on the device (formatted there), DP comes back only for the pileup / per-read listings
-    const bool dtext = a.device_text != 0;
+    // --device-bcf 1: the same two paths for -O u / -O b -- the tile's FORMAT part comes back as BCF typed vectors (vgl_ctx_bcf_keys)
+    const bool dtext = a.device_text != 0 || (dbcf && !a.do_gvcf);
     // --device-gvcf 1: the same for -doGVCF 1; the blocks are built on the device, the FORMAT arrays stay there
     const bool dgvcf = a.device_gvcf != 0;
     // --device-pileup 1: the read dump and DP stay on the device (the pileup's sample columns come back as text)
@@ -1077,7 +1113,7 @@ int main(int argc, char** argv) {
         }
         if (dtext) {
             B.text_cap = vgl_ctx_text_bound(ctxs[ri % (size_t)D], TS);
-            if (B.text_cap < 0) die("--device-text 1: %s", vgl_last_error());
+            if (B.text_cap < 0) die("%s 1: %s", dbcf ? "--device-bcf" : "--device-text", vgl_last_error());
             B.text.resize((size_t)std::max<int64_t>(B.text_cap, 1)); B.toff.resize((size_t)TS + 1);
             return;
         }
@@ -1106,7 +1142,7 @@ int main(int argc, char** argv) {
     struct Worker { std::thread th; std::mutex m; std::condition_variable cv; std::vector<TileBufs*> q; size_t head = 0; bool stop = false;
                     long tiles = 0, sites = 0; double t_first = -1.0, t_last = 0.0; double text_bytes = 0.0; };          // --verbose 1: what this device did (written by its own thread, read after the join)
     // bytes a finished tile brings back over the link, per site (the FORMAT arrays dominate: sample-major slabs, copied whole)
-    // (--device-text 1: the text instead of the FORMAT arrays, counted as it comes back)
+    // (--device-text 1 / --device-gvcf 1 / --device-bcf 1: the text or the encoded vectors instead of the FORMAT arrays, counted as they come back)
     const double bytes_per_site = (double)N * ((want_dp ? 4.0 : 0.0) + (dtext || dgvcf ? 0.0 : 4.0 * G * ((a.add_gl ? 1 : 0) + (a.add_pl ? 1 : 0) + (a.add_gp ? 1 : 0)) +
                                                4.0 * A * ((a.add_fmt_ad ? 1 : 0) + (a.add_fmt_adf ? 1 : 0) + (a.add_fmt_adr ? 1 : 0)))) + 64.0;
     std::vector<std::unique_ptr<Worker>> workers(D);
@@ -1219,11 +1255,17 @@ int main(int argc, char** argv) {
         vsink::parallel_for(ni, enc_threads, [&](int k) {
             enc[k].clear();
             const vgl_gvcf_item& t = it[k];
-            if (t.kind == VGL_GVCF_RECORD) { std::vector<std::string> al; std::vector<vsink::FmtDesc> fmt; build_record(B, t.first, enc[k], al, fmt); return; }
+            std::string sh8; std::string& col = dbcf ? sh8 : enc[k];    // --device-bcf 1: the fixed columns become the record's shared block
+            if (t.kind == VGL_GVCF_RECORD) {
+                std::vector<std::string> al; std::vector<vsink::FmtDesc> fmt; build_record(B, t.first, col, al, fmt);
+                if (dbcf) out.encode_head(sh8, (uint32_t)n_fmt, (size_t)(B.toff[t.first + 1] - B.toff[t.first]), enc[k]);
+                return;
+            }
             if ((k == 0 && merge) || k == ni - 1) return;            // carried on the host
             const int f = t.founder;
-            GvcfBlocker::fixed_columns(enc[k], out, B.meta[f].rec->chrom, B.meta[f].pos0, B.meta[t.last].pos0, site_alleles(B, f), t.min_dp,
+            GvcfBlocker::fixed_columns(col, out, B.meta[f].rec->chrom, B.meta[f].pos0, B.meta[t.last].pos0, site_alleles(B, f), t.min_dp,
                                        a.add_qs ? &B.qs[(size_t)f * A] : nullptr, a.add_qs ? (size_t)B.na[f] : 0);
+            if (dbcf) out.encode_head(sh8, 2, (size_t)(B.boff[t.block + 1] - B.boff[t.block]), enc[k]);        // PL, DP
         });
         lap(4);
         for (int k = 0; k < ni; k++) {
@@ -1332,6 +1374,7 @@ int main(int argc, char** argv) {
                 if (B.st[i] < 0) return;
                 std::string sh; std::vector<std::string> al; std::vector<vsink::FmtDesc> fmt;
                 build_record(B, i, sh, al, fmt);
+                if (dbcf) { out.encode_head(sh, (uint32_t)n_fmt, (size_t)(B.toff[i + 1] - B.toff[i]), enc[i]); return; }
                 if (dtext) { enc[i] = std::move(sh); return; }
                 out.encode_rec(sh, fmt, enc[i]);
             });

@@ -236,6 +236,9 @@ struct vgl_ctx {
         uint8_t* d_ptext = nullptr; int64_t d_ptext_bytes = 0; int64_t* d_poff = nullptr; void* d_pws = nullptr; int64_t d_pws_bytes = 0;
     } slot[2];
     vgl_pileup_tile* pile_next = nullptr;                           // vgl_ctx_pileup_next: taken by the next tile call
+    // vgl_ctx_bcf_keys: the text / gVCF tile calls deliver BCF typed vectors (vgl_bcf.hip) instead of text; dictionary ids of
+    // DP, GL, PL, GP, AD, ADF, ADR
+    bool bcf = false; int32_t bcf_keys[7] = {0, 0, 0, 0, 0, 0, 0};
     hipStream_t s_text = nullptr;                                   // text copies of vgl_tile_wait (never behind the next tile's copies)
     // a draw deeper than the staging capacity (vcfgl grows its read buffers, bcf_utils.cpp:618-648): the host entry points run such a tile again on
     // this sibling context, created on first need with the staging layout's largest capacity (VGL_READ_CAP_MAX reads) and tiles of at most
@@ -1130,10 +1133,36 @@ static int text_fields(const vgl_ctx* c, vgl_text_field* tf, int* fid) {
     return n;
 }
 
+// the same fields as BCF descriptors (vgl_ctx_bcf_keys: FIELDS[10 .. 16] = DP, GL, PL, GP, AD, ADF, ADR)
+static void bcf_fields(const vgl_ctx* c, const vgl_text_field* tf, const int* fid, int nf, vgl_bcf_field* bf) {
+    for (int k = 0; k < nf; k++) {
+        bf[k].key_id = c->bcf_keys[fid[k] - 10]; bf[k].is_float = tf[k].is_float; bf[k].count = tf[k].count; bf[k].base = tf[k].base;
+        bf[k].site_stride = tf[k].site_stride;
+    }
+}
+
+extern "C" int vgl_ctx_bcf_keys(vgl_ctx* c, const int32_t* key_ids, int32_t n) {
+    if (!c) return fail(VGL_E_ARG, "vgl_ctx_bcf_keys: null context");
+    if (!key_ids) { c->bcf = false; return VGL_OK; }
+    if (n != 7) return fail(VGL_E_ARG, "vgl_ctx_bcf_keys: 7 dictionary ids are expected (DP, GL, PL, GP, AD, ADF, ADR), %d given", (int)n);
+    vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
+    const int nf = text_fields(c, tf, fid);
+    for (int k = 0; k < nf; k++)
+        if (key_ids[fid[k] - 10] < 0) return fail(VGL_E_ARG, "vgl_ctx_bcf_keys: negative dictionary id of FORMAT/%s", tf[k].key);
+    memcpy(c->bcf_keys, key_ids, sizeof c->bcf_keys);
+    c->bcf = true;
+    return VGL_OK;
+}
+
 extern "C" int64_t vgl_ctx_text_bound(const vgl_ctx* c, int32_t n_sites) {
     if (!c || n_sites < 0) return -1;
     vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
     const int nf = text_fields(c, tf, fid);
+    if (c->bcf) {
+        vgl_bcf_field bf[VGL_TEXT_MAX_FIELDS];
+        bcf_fields(c, tf, fid, nf, bf);
+        return vgl_bcf_bound(c->dp.n_samples, n_sites, bf, nf, (int32_t)c->dp.A);
+    }
     return vgl_text_bound(c->dp.n_samples, n_sites, tf, nf, (int32_t)c->dp.A);
 }
 
@@ -1142,6 +1171,12 @@ static int enqueue_text(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites) {
     vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
     const int nf = text_fields(c, tf, fid);
     for (int k = 0; k < nf; k++) tf[k].base = S.d_out[fid[k]];
+    if (c->bcf) {
+        vgl_bcf_field bf[VGL_TEXT_MAX_FIELDS];
+        bcf_fields(c, tf, fid, nf, bf);
+        return vgl_bcf_encode_device(c->device, bf, nf, c->dp.n_samples, n_sites, (const int32_t*)S.d_out[0], (const int32_t*)S.d_out[1],
+                                     S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
+    }
     return vgl_text_format_device(c->device, tf, nf, c->dp.n_samples, n_sites, (const int32_t*)S.d_out[0], (const int32_t*)S.d_out[1],
                                   S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
 }
@@ -1163,7 +1198,16 @@ extern "C" int64_t vgl_ctx_gvcf_text_bound(const vgl_ctx* c, int32_t n_sites) {
     vgl_text_field bf[2];
     gvcf_block_fields(c, nullptr, bf);
     // a site is a record or a member of at most one block: the larger of the two texts per site
-    const int64_t rec = vgl_text_bound(c->dp.n_samples, 1, tf, nf, (int32_t)c->dp.A), blk = vgl_text_bound(c->dp.n_samples, 1, bf, 2, (int32_t)c->dp.A);
+    int64_t rec, blk;
+    if (c->bcf) {
+        vgl_bcf_field rb[VGL_TEXT_MAX_FIELDS], bb[2];
+        bcf_fields(c, tf, fid, nf, rb);
+        const int bfid[2] = {12, 10};                                   // PL, DP
+        bcf_fields(c, bf, bfid, 2, bb);
+        rec = vgl_bcf_bound(c->dp.n_samples, 1, rb, nf, (int32_t)c->dp.A); blk = vgl_bcf_bound(c->dp.n_samples, 1, bb, 2, (int32_t)c->dp.A);
+    } else {
+        rec = vgl_text_bound(c->dp.n_samples, 1, tf, nf, (int32_t)c->dp.A); blk = vgl_text_bound(c->dp.n_samples, 1, bf, 2, (int32_t)c->dp.A);
+    }
     if (rec < 0 || blk < 0) return -1;
     return (int64_t)n_sites * (rec > blk ? rec : blk);
 }
@@ -1185,10 +1229,19 @@ static int enqueue_gvcf(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites) {
     vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
     const int nf = text_fields(c, tf, fid);
     for (int k = 0; k < nf; k++) tf[k].base = S.d_out[fid[k]];
-    rc = vgl_text_format_device(c->device, tf, nf, N, n_sites, S.d_rst, in.n_alleles, S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
-    if (rc != VGL_OK) return rc;
     vgl_text_field bf[2];
     gvcf_block_fields(c, &S, bf);
+    if (c->bcf) {
+        vgl_bcf_field rb[VGL_TEXT_MAX_FIELDS], bb[2];
+        bcf_fields(c, tf, fid, nf, rb);
+        const int bfid[2] = {12, 10};                                   // PL, DP
+        bcf_fields(c, bf, bfid, 2, bb);
+        rc = vgl_bcf_encode_device(c->device, rb, nf, N, n_sites, S.d_rst, in.n_alleles, S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
+        if (rc != VGL_OK) return rc;
+        return vgl_bcf_encode_device(c->device, bb, 2, N, n_sites, S.d_bst, S.d_bna, S.d_btext, S.text_cap, S.d_boff, S.d_tws, S.d_tws_bytes, c->s_compute);
+    }
+    rc = vgl_text_format_device(c->device, tf, nf, N, n_sites, S.d_rst, in.n_alleles, S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
+    if (rc != VGL_OK) return rc;
     return vgl_text_format_device(c->device, bf, 2, N, n_sites, S.d_bst, S.d_bna, S.d_btext, S.text_cap, S.d_boff, S.d_tws, S.d_tws_bytes, c->s_compute);
 }
 
@@ -1356,7 +1409,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     }
     if (S.gvcf) { const int rc = stage_gvcf(c, S, n_sites, contig, pos0); if (rc != VGL_OK) return rc; }
     if (S.text || S.gvcf) {
-        const int64_t ws = vgl_text_workspace_bytes((int32_t)N, c->max_sites);
+        const int64_t ws = std::max(vgl_text_workspace_bytes((int32_t)N, c->max_sites), vgl_bcf_workspace_bytes((int32_t)N, c->max_sites));
         if (S.d_tws_bytes < ws) {
             if (S.d_tws) (void)hipFree(S.d_tws);
             S.d_tws = nullptr; S.d_tws_bytes = 0;
