@@ -42,7 +42,10 @@ static const int N_GT_OF_ALLELES[6] = {0, 1, 3, 6, 10, 15};   /* shared.cpp:29 *
 /* ------------------------------------------------------------------------------------ */
 /* rand48 (glibc drand48/erand48; rng.h:8-10).  state' = A*state + C mod 2^48, u = state'/2^48 */
 
+static uint64_t g_ndraw;        /* uniform draws taken so far (the window census below reads differences of it) */
+
 static inline double lcg_uniform(uint64_t* st) {
+    ++g_ndraw;
     *st = (*st * LCG_A + LCG_C) & MASK48;
     return (double)(*st) * TWO_M48;
 }
@@ -411,6 +414,7 @@ int vgl_oracle_errmod_cal(double depcorr, int n, const uint16_t* bases, float* q
 /* ------------------------------------------------------------------------------------ */
 /* oracle context */
 
+#define VGL_CENSUS_BINS 257
 typedef struct vgl_oracle {
     vgl_params p;
     double* depths;            /* private copy */
@@ -435,6 +439,11 @@ typedef struct vgl_oracle {
     int cap;                   /* reads capacity per sample */
     int* bases; int* qsc; int* adjq; double* errp;   /* [n_samples][cap] */
     int64_t n_draw_rand;       /* rand() draws consumed (I16) */
+    /* window census (VGL_RNG_TILE, test-only export vgl_oracle_census): how far the consumers of an evaluation step into their windows */
+    int cen_on;
+    uint64_t cen_max[4];       /* per stream: the largest distance from off[k] any evaluation reached (stream 3: r qs_read_stride + draws of read r) */
+    uint64_t cen_hap_diff;     /* evaluations whose haplotype stream took another number of draws than FORMAT/DP */
+    uint64_t cen_hist[VGL_CENSUS_BINS];   /* beta deviates by draws consumed (last bin: that many or more) */
 } vgl_oracle;
 
 static char g_err[512];
@@ -612,6 +621,12 @@ static double beta_draw(vgl_oracle* o, uint64_t* st_qs) {
     return x / (x + y);
 }
 
+/* window census: one beta deviate that started `start` draws behind off[3] and took `draws` draws */
+static void census_deviate(vgl_oracle* o, uint64_t start, uint64_t draws) {
+    if (start + draws > o->cen_max[3]) o->cen_max[3] = start + draws;
+    o->cen_hist[draws < VGL_CENSUS_BINS - 1 ? draws : VGL_CENSUS_BINS - 1]++;
+}
+
 /* GL model 2, one sample: gl_methods.cpp:22-59 / :94-139 / :171-220 */
 static void gl2_sample(const vgl_oracle* o, int s, int n, const int* acgt2alleles, int nAlleles, int nG, float* g) {
     const vgl_params* p = &o->p;
@@ -720,7 +735,9 @@ static int simulate_site(vgl_oracle* o, int64_t site_abs, int32_t ls, int32_t n_
             st_qs[s] = vgl_oracle_rand48_jump(o->x0, base + o->lay.off[3]);
             st_depth = &local_depth;
         } else st_depth = &o->st1;
+        const uint64_t c_depth = g_ndraw;
         int n = poisson_sample(&o->pois[o->n_pois == 1 ? 0 : s], st_depth);
+        if (o->cen_on && g_ndraw - c_depth > o->cen_max[0]) o->cen_max[0] = g_ndraw - c_depth;
         int a0 = gt[s] & 0xF, a1 = (gt[s] >> 4) & 0xF;
         if (a0 == VGL_GT_MISSING || a1 == VGL_GT_MISSING) { dp[s] = 0; continue; }
         dp[s] = n; info_dp += n;
@@ -743,7 +760,11 @@ static int simulate_site(vgl_oracle* o, int64_t site_abs, int32_t ls, int32_t n_
 
     /* ---- per-site base-pick error (error_qs 1: one beta deviate, vcfgl.cpp:425-437) */
     double base_pick_error_prob = p->error_rate;
-    if (1 == p->error_qs) base_pick_error_prob = beta_draw(o, tile ? &st_qs[0] : &o->st2);
+    if (1 == p->error_qs) {
+        const uint64_t c_site = g_ndraw;
+        base_pick_error_prob = beta_draw(o, tile ? &st_qs[0] : &o->st2);
+        if (o->cen_on) census_deviate(o, 0, g_ndraw - c_site);
+    }
     if (1 == p->error_qs && out->site_pick_err) out->site_pick_err[ls] = base_pick_error_prob;   /* -printBasePickError, :430-435 */
 
     /* ---- read loop (vcfgl.cpp:441-640) */
@@ -754,16 +775,22 @@ static int simulate_site(vgl_oracle* o, int64_t site_abs, int32_t ls, int32_t n_
         uint64_t* sh = tile ? &st_hap[s] : &o->st1;
         uint64_t* sb = tile ? &st_base[s] : &o->st0;
         uint64_t* sq = tile ? &st_qs[s] : &o->st2;
+        uint64_t n_hap = 0, n_base = 0;                                              /* draws of this evaluation (window census) */
         for (int r = 0; r < n; r++) {
+            const uint64_t c0 = g_ndraw;
             int true_base = (lcg_uniform(sh) < 0.5) ? a0 : a1;                       /* :473 */
+            const uint64_t c1 = g_ndraw;
             r_base = true_base;
             if (lcg_uniform(sb) < base_pick_error_prob)                              /* :486 */
                 while ((r_base = (int)floor(4 * lcg_uniform(sb))) == true_base);     /* :487 */
+            n_hap += c1 - c0; n_base += g_ndraw - c1;
             int q_i, aq_i;
             if (2 == p->error_qs) {                                                  /* :494-565 */
                 uint64_t st_read = 0;
                 if (tile) { st_read = vgl_oracle_rand48_jump(st_qs[s], (uint64_t)r * o->lay.qs_read_stride); sq = &st_read; }
+                const uint64_t c_qs = g_ndraw;
                 double ep = beta_draw(o, sq);
+                if (o->cen_on && tile) census_deviate(o, (uint64_t)r * o->lay.qs_read_stride, g_ndraw - c_qs);
                 if ((rc = errprob_to_qs(o, ep, 0, &q_i, &aq_i))) goto done;
                 if (aq_i < 0 && (p->adjust_qs & 3)) {       /* the reference exits: ASSERT(adjqScore_i != -1) :558, ASSERT(qs >= 0 ...) gl_methods.cpp:101 */
                     snprintf(g_err, sizeof g_err, "--adjust-qs %d: a read has no valid adjusted quality score (error probability %g)", p->adjust_qs, ep);
@@ -780,12 +807,18 @@ static int simulate_site(vgl_oracle* o, int64_t site_abs, int32_t ls, int32_t n_
             int strand = 0;
             if (sample_strand) {                                                     /* :581-605 */
                 strand = (lcg_uniform(sb) < 0.5) ? 0 : 1;
+                ++n_base;
                 if (strand == 0) adf[s * 4 + r_base]++; else adr[s * 4 + r_base]++;
             } else adf[s * 4 + r_base]++;
             nI16[2 * r_base + strand]++;
             o->bases[(size_t)s * o->cap + r] = r_base;
         }
         for (int b = 0; b < 4; b++) info_acgt[b] += ad[s * 4 + b];
+        if (o->cen_on) {
+            if (n_hap > o->cen_max[1]) o->cen_max[1] = n_hap;
+            if (n_base > o->cen_max[2]) o->cen_max[2] = n_base;
+            if (n_hap != (uint64_t)n) o->cen_hap_diff++;
+        }
     }
 
     if (p->add_i16) {                                                                /* :647-663 */
@@ -1002,3 +1035,21 @@ int vgl_oracle_beta_std_draws(double mean, double var, int32_t seed, int n, doub
 }
 
 void vgl_oracle_stream_states(const vgl_oracle* o, uint64_t st[3]) { st[0] = o->st0; st[1] = o->st1; st[2] = o->st2; }
+
+/* -------- window census (test-only): include/vcfgl_hip.h says a consumer that outruns its sub-window "simply keeps stepping"; this counts how far
+ * the consumers of the tiles simulated since vgl_oracle_census_begin() stepped.  max_draws[k]: the largest distance from off[k] an evaluation's
+ * stream k reached (stream 3: over its reads, r qs_read_stride + the draws of read r's deviate); hap_diff: evaluations whose haplotype stream took
+ * another number of draws than FORMAT/DP; hist[d], d < n_bins - 1: beta deviates that took d draws, hist[n_bins - 1]: those that took more. */
+void vgl_oracle_census_begin(vgl_oracle* o) {
+    o->cen_on = 1; o->cen_hap_diff = 0;
+    memset(o->cen_max, 0, sizeof o->cen_max); memset(o->cen_hist, 0, sizeof o->cen_hist);
+}
+
+int vgl_oracle_census(const vgl_oracle* o, uint64_t max_draws[4], uint64_t* hap_diff, uint64_t* hist, int n_bins) {
+    if (!o || !o->cen_on || n_bins < 2) OFAIL(VGL_E_ARG, "census: not begun, or fewer than two bins");
+    for (int k = 0; k < 4; k++) max_draws[k] = o->cen_max[k];
+    *hap_diff = o->cen_hap_diff;
+    memset(hist, 0, sizeof(uint64_t) * (size_t)n_bins);
+    for (int d = 0; d < VGL_CENSUS_BINS; d++) hist[d < n_bins - 1 ? d : n_bins - 1] += o->cen_hist[d];
+    return VGL_OK;
+}

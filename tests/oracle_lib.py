@@ -33,6 +33,9 @@ def lib():
         _lib.vgl_oracle_beta_rand48_draws.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_uint64), C.c_int, C.c_void_p]
         _lib.vgl_oracle_beta_std_draws.argtypes = [C.c_double, C.c_double, C.c_int32, C.c_int, C.c_void_p]
         _lib.vgl_oracle_errmod_cal.argtypes = [C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.vgl_oracle_census_begin.argtypes = [C.c_void_p]
+        _lib.vgl_oracle_census_begin.restype = None
+        _lib.vgl_oracle_census.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
     return _lib
 
 
@@ -60,6 +63,18 @@ class Oracle:
         if rc != 0:
             raise OracleError(rc, lib().vgl_oracle_last_error().decode())
         return tile
+
+    def census_begin(self):
+        """start counting how far the tile-mode consumers step into their windows (vgl_oracle_census_begin)"""
+        lib().vgl_oracle_census_begin(self.h)
+
+    def census(self, n_bins=257):
+        """(largest draws per stream [4], evaluations whose haplotype stream took != FORMAT/DP draws, beta deviates by draws taken [n_bins])"""
+        mx, diff, hist = (C.c_uint64 * 4)(), C.c_uint64(), (C.c_uint64 * n_bins)()
+        rc = lib().vgl_oracle_census(self.h, mx, C.byref(diff), hist, n_bins)
+        if rc != 0:
+            raise OracleError(rc, lib().vgl_oracle_last_error().decode())
+        return list(mx), diff.value, np.array(list(hist), dtype=np.int64)
 
     def close(self):
         if self.h:

@@ -60,14 +60,18 @@ def test_tile_mode_agrees_in_distribution_with_the_reference_order(eqs):
         valid = np.arange(cap)[:, None, None] < depth
         base, q = rd & 3, rd >> 2
         wrong = valid & (base != a0) & (base != a1)
-        return wrong.sum(), valid.sum(), np.bincount(q[valid].ravel(), minlength=64)
+        # the exact expectation for this genotype mix: every read is a Bernoulli trial of probability e (homozygote) or 2/3 e (heterozygote)
+        p_read = np.where(a0 == a1, 0.02, 2.0 / 3.0 * 0.02) * np.ones(valid.shape)
+        return wrong.sum(), valid.sum(), np.bincount(q[valid].ravel(), minlength=64), p_read[valid].sum(), (p_read * (1.0 - p_read))[valid].sum()
 
-    wa, na_, qa = read_stats(a)
-    wb, nb_, qb = read_stats(b)
+    wa, na_, qa, ea, va = read_stats(a)
+    wb, nb_, qb, eb, vb = read_stats(b)
     pa, pb = wa / na_, wb / nb_
     se = np.sqrt(pa * (1 - pa) / na_ + pb * (1 - pb) / nb_)
     assert abs(pa - pb) < 5 * se, ("wrong-base rate", pa, pb)
-    assert 0.0125 < pa < 0.0205 and 0.0125 < pb < 0.0205                    # e = 0.02 at homozygotes, 2/3 e at heterozygotes
+    for mode, w, e, v in (("serial", wa, ea, va), ("tile", wb, eb, vb)):    # 5-sigma binomial band around the expected count of the reads observed
+        print(f"wrong bases, {mode}: {w} observed, {e:.1f} expected, z = {(w - e) / np.sqrt(v):.2f}")
+        assert abs(w - e) < 5 * np.sqrt(v), ("wrong-base count", mode, w, e, np.sqrt(v))
     if eqs == 2:
         stat, dof = chi2_two_sample(qa, qb)
         assert stat < dof + 5 * np.sqrt(2 * dof), ("quality-score histogram", stat, dof)

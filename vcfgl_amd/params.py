@@ -103,6 +103,7 @@ class VcfglArgs:
     rng_mode: int = _abi.VGL_RNG_TILE
     beta_sampler: int = _abi.VGL_BETA_RAND48
     out_layout: int = _abi.VGL_LAYOUT_PLANES       # layout of the multi-valued FORMAT arrays (include/vcfgl_hip.h)
+    rng_layout: Optional[tuple] = None   # VGL_RNG_TILE windows of the caller: (block, (off0, off1, off2, off3), qs_read_stride); None = the library's default
     extra: dict = field(default_factory=dict)   # parsed but unused flags (output mode, threads, ...)
 
     # ------------------------------------------------------------------ parsing
@@ -221,6 +222,14 @@ class VcfglArgs:
                   "add_info_ad", "add_fmt_adf", "add_info_adf", "add_fmt_adr", "add_info_adr"):
             setattr(p, f, int(getattr(self, f)))
         p.out_layout = int(self.out_layout)
+        if self.rng_layout is not None:                            # vgl_rng_layout; left zero (block == 0) the library takes its default
+            block, off, stride = self.rng_layout
+            if len(off) != 4:
+                raise VcfglArgError("rng_layout is (block, (off0, off1, off2, off3), qs_read_stride)")
+            p.layout.block = int(block)
+            for k in range(4):
+                p.layout.off[k] = int(off[k])
+            p.layout.qs_read_stride = int(stride)
         return p, keep
 
     @property
