@@ -608,6 +608,58 @@ VGL_API int vgl_bcf_encode_device(int32_t device, const vgl_bcf_field* fields, i
                                   void* workspace, int64_t workspace_bytes, void* hip_stream);
 VGL_API int vgl_ctx_bcf_keys(vgl_ctx* ctx, const int32_t* key_ids, int32_t n);
 
+/* ---- a tile's record stream assembled and compressed on the device (ABI 7, additive) -------------------------------------------------
+ * A record of the output is a HEAD the host builds from the tile's per-site arrays (the eight fixed columns of a VCF line; l_shared,
+ * l_indiv and the shared block of a BCF record) followed by the BODY the device built (vgl_simulate_tile_text_async: the sample columns,
+ * or the indiv block after vgl_ctx_bcf_keys).  These calls keep the bodies on the device, take the heads up the link, interleave the
+ * two there and compress the stream with vgl_bgzf_compress_device: only heads go up, only BGZF members come down.
+ *   vgl_stream_assemble_device  heads, head_offsets (int64 [n_sites + 1]), bodies, body_offsets (int64 [n_sites + 1]), dst [dst_cap] and
+ *                             total (int64) are device memory of `device`; work is enqueued on `hip_stream` without synchronising.
+ *                             Both offset arrays are non-decreasing prefix sums that may start at any value: `heads` and `bodies`
+ *                             point at the first byte of site 0, so head i is heads[head_offsets[i] - head_offsets[0] ..
+ *                             head_offsets[i + 1] - head_offsets[0]), body i likewise.  Record i = head i then body i, written at
+ *                             dst + (head_offsets[i] - head_offsets[0]) + (body_offsets[i] - body_offsets[0]); a site whose head and
+ *                             body are empty contributes nothing.  *total = the stream's length.  When it exceeds dst_cap NOTHING is
+ *                             written to dst and *total still says what is needed.  heads, bodies and dst may start at any byte; all
+ *                             offsets and counts are 64-bit (a tile's text can exceed 2 GiB).  n_sites = 0 writes *total = 0 only.
+ *   vgl_ctx_text_device       on != 0: from then on the `text` argument of vgl_simulate_tile_text_async is memory of the context's
+ *                             DEVICE: the formatter (or the BCF encoder) writes the tile's bodies there and vgl_tile_wait copies no
+ *                             text; `offsets` stays host memory and receives the site offsets as before (offsets[n_sites] = the total;
+ *                             beyond text_cap: VGL_E_CAPACITY and nothing written).  A tile that is run again after a deep draw is
+ *                             delivered to the same place.  vgl_simulate_tile_gvcf_async and the pileup are unaffected.  Call it while
+ *                             no tile of the context is in flight.
+ * Host handle, for a program that writes BGZF from host memory (the host program's --device-stream 1).  It is independent of any
+ * vgl_ctx: one thread may drive the context while another drives the handle.  It owns n_buffers (1 .. 8) device body buffers of
+ * max_body_bytes, the device stream and member buffers, the BGZF workspace, its HIP streams and page-locked member buffers.
+ *   vgl_stream_host_body      body buffer k (device memory; NULL for a k out of range): the `text` of a tile call on a context with
+ *                             vgl_ctx_text_device, text_cap = max_body_bytes.
+ *   vgl_stream_host_submit    n_sites <= max_sites sites whose bodies lie in buffer k at [body_offsets[i], body_offsets[i + 1]) -- the
+ *                             offsets the tile call returned, complete once vgl_tile_wait has returned -- and whose heads are the host
+ *                             bytes heads[head_offsets[i] .. head_offsets[i + 1]).  Both arrays index ABSOLUTELY here -- the offsets
+ *                             of the tile call address the body buffer as they are, and `heads` is indexed the same way -- whereas
+ *                             vgl_stream_assemble_device takes pointers to site 0's first byte.  Copies heads and offsets (the caller's arrays are
+ *                             free again on return), enqueues upload, assembly and compression, and returns at once with a ticket.
+ *                             VGL_E_ARG, before any device call, with a message naming the argument: k out of range, buffer k still in
+ *                             flight, n_sites out of range, offsets that decrease, head bytes beyond max_head_bytes, body offsets
+ *                             outside the buffer.
+ *   vgl_stream_host_wait      blocks until the ticket's members are in host memory: *members (owned by the handle, valid until buffer k
+ *                             is submitted again) holds *members_n bytes of BGZF members WITHOUT the EOF member, *raw_n (may be NULL)
+ *                             the length of the stream they decompress to.  The members are those vgl_bgzf_compress_device gives for the
+ *                             stream: cut every 0xff00 bytes from the tile's first byte, the last one shorter.  n_sites = 0 or an empty
+ *                             stream gives *members_n = 0.  Tickets are waited for in submit order (VGL_E_ARG otherwise).
+ * No HIP device: VGL_E_NODEVICE from create. */
+typedef struct vgl_stream_host vgl_stream_host;
+VGL_API int vgl_stream_assemble_device(int32_t device, int32_t n_sites, const uint8_t* heads, const int64_t* head_offsets, const uint8_t* bodies,
+                                       const int64_t* body_offsets, uint8_t* dst, int64_t dst_cap, int64_t* total, void* hip_stream);
+VGL_API int vgl_ctx_text_device(vgl_ctx* ctx, int32_t on);
+VGL_API int vgl_stream_host_create(int32_t device, int32_t n_buffers, int32_t max_sites, int64_t max_head_bytes, int64_t max_body_bytes,
+                                   vgl_stream_host** out);
+VGL_API uint8_t* vgl_stream_host_body(vgl_stream_host* h, int32_t k);
+VGL_API int vgl_stream_host_submit(vgl_stream_host* h, int32_t k, int32_t n_sites, const uint8_t* heads, const int64_t* head_offsets,
+                                   const int64_t* body_offsets, int32_t* ticket);
+VGL_API int vgl_stream_host_wait(vgl_stream_host* h, int32_t ticket, const uint8_t** members, int64_t* members_n, int64_t* raw_n);
+VGL_API int vgl_stream_host_destroy(vgl_stream_host* h);
+
 #ifdef __cplusplus
 }
 #endif

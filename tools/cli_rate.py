@@ -5,7 +5,10 @@ inside the measured wall time: process start, input parsing, PCIe copies, record
 usage (GPU box): python tools/cli_rate.py [sites] [samples]
 CLI_BCF_AB=1: every binary mode of the list is run with --device-bcf 0 and --device-bcf 1, alternating, CLI_REPS times each (default 3);
 both settings must write the same stream (decompressed, the ##source= lines taken out): checked on every pair.  CLI_PARENT_BIN=path
-alternates another build of the program (without the flag) with this one at --device-bcf 0 instead: the run-to-run spread of the two."""
+alternates another build of the program (without the flag) with this one at --device-bcf 0 instead: the run-to-run spread of the two.
+CLI_STREAM_AB=1: the modes b and z of the list are run with --device-stream 0 and --device-stream 1 (beside --device-bgzf 1 and the
+companion flag: --device-bcf 1 for b, --device-text 1 for z), alternating, CLI_REPS times each; with CLI_PARENT_BIN that build (which
+does not know the flag) is the third setting of the rotation.  All settings must write the same decompressed stream."""
 import gzip, hashlib, os, struct, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -44,11 +47,24 @@ def bcf_digest(fn):
     return h.hexdigest()
 
 
-def ab(mode, threads):
-    """alternating runs of two settings of one binary mode: times, [timing] and [device] lines, output size, equal streams"""
+def vcf_digest(fn):
+    """sha1 of a bgzip'd VCF stream without its ##source= lines"""
+    with gzip.open(fn, "rb") as f:
+        raw = f.read()
+    return hashlib.sha1(b"\n".join(l for l in raw.split(b"\n") if not l.startswith(b"##source="))).hexdigest()
+
+
+def ab(mode, threads, stream=False):
+    """alternating runs of two (or three) settings of one mode: times, [timing] and [device] lines, output size, equal streams"""
     parent = os.environ.get("CLI_PARENT_BIN")
-    settings = [("parent", parent, []), ("--device-bcf 0", BIN, ["--device-bcf", "0"])] if parent else \
-               [("--device-bcf 0", BIN, ["--device-bcf", "0"]), ("--device-bcf 1", BIN, ["--device-bcf", "1"])]
+    ext = ".vcf.gz" if mode == "z" else ".bcf"
+    if stream:
+        common = ["--device-bgzf", "1"] + (["--device-text", "1"] if mode == "z" else ["--device-bcf", "1"])
+        settings = ([("parent", parent, common)] if parent else []) + \
+                   [("--device-stream 0", BIN, common + ["--device-stream", "0"]), ("--device-stream 1", BIN, common + ["--device-stream", "1"])]
+    else:
+        settings = [("parent", parent, []), ("--device-bcf 0", BIN, ["--device-bcf", "0"])] if parent else \
+                   [("--device-bcf 0", BIN, ["--device-bcf", "0"]), ("--device-bcf 1", BIN, ["--device-bcf", "1"])]
     th = ["--threads", str(threads)] if threads else []
     times, digests = {k: [] for k, _, _ in settings}, {}
     for rep in range(int(os.environ.get("CLI_REPS", "3"))):
@@ -59,18 +75,23 @@ def ab(mode, threads):
             dt = time.perf_counter() - t0
             assert r.returncode == 0, r.stderr[-800:]
             times[name].append(dt)
-            print(f"-O {mode} --threads {threads:3d} {name:16s} run {rep}: {dt:7.2f} s  {S * N / dt:10.3e} evals/s  output {os.path.getsize(out + '.bcf') / 1e6:8.1f} MB", flush=True)
+            print(f"-O {mode} --threads {threads:3d} {name:16s} run {rep}: {dt:7.2f} s  {S * N / dt:10.3e} evals/s  output {os.path.getsize(out + ext) / 1e6:8.1f} MB", flush=True)
             if rep == 0:
                 for l in r.stderr.splitlines():
                     if l.startswith("[timing]") or l.startswith("[device"):
                         print("    " + l, flush=True)
-                digests[name] = bcf_digest(out + ".bcf")
-            os.remove(out + ".bcf")
-    assert len(set(digests.values())) == 1, f"-O {mode}: the two settings wrote different streams"
+                digests[name] = vcf_digest(out + ext) if mode == "z" else bcf_digest(out + ext)
+            os.remove(out + ext)
+    assert len(set(digests.values())) == 1, f"-O {mode}: the settings wrote different streams"
     for name, ts in times.items():
         print(f"  {name:16s} min {min(ts):.2f} s  median {sorted(ts)[len(ts) // 2]:.2f} s  max {max(ts):.2f} s  spread {(max(ts) - min(ts)) / min(ts) * 100:.1f} %", flush=True)
 
 
+if os.environ.get("CLI_STREAM_AB"):
+    for mode, threads in runs:
+        if mode in ("b", "z"):
+            ab(mode, threads, stream=True)
+    sys.exit(0)
 if os.environ.get("CLI_BCF_AB") or os.environ.get("CLI_PARENT_BIN"):
     for mode, threads in runs:
         if mode in ("u", "b"):

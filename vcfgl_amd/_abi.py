@@ -96,6 +96,8 @@ EXPORTS = [
     "vgl_gvcf_workspace_bytes", "vgl_gvcf_blocks_device", "vgl_ctx_gvcf_text_bound", "vgl_simulate_tile_gvcf_async",
     "vgl_pileup_bound", "vgl_pileup_workspace_bytes", "vgl_pileup_format_device", "vgl_ctx_pileup_bound", "vgl_ctx_pileup_next",
     "vgl_bcf_bound", "vgl_bcf_workspace_bytes", "vgl_bcf_encode_device", "vgl_ctx_bcf_keys",
+    "vgl_stream_assemble_device", "vgl_ctx_text_device",
+    "vgl_stream_host_create", "vgl_stream_host_body", "vgl_stream_host_submit", "vgl_stream_host_wait", "vgl_stream_host_destroy",
 ]
 VGL_PACK_ROW, VGL_PACK_ROWS_G, VGL_PACK_ROWS_A = 0, 1, 2
 
@@ -248,6 +250,15 @@ def load_library(hooks=False):
     lib.vgl_bcf_encode_device.argtypes = [C.c_int32, C.POINTER(BcfField), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.vgl_ctx_bcf_keys.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    lib.vgl_stream_assemble_device.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.c_void_p]
+    lib.vgl_ctx_text_device.argtypes = [C.c_void_p, C.c_int32]
+    lib.vgl_stream_host_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
+    lib.vgl_stream_host_body.restype = C.c_void_p
+    lib.vgl_stream_host_body.argtypes = [C.c_void_p, C.c_int32]
+    lib.vgl_stream_host_submit.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    lib.vgl_stream_host_wait.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.vgl_stream_host_destroy.argtypes = [C.c_void_p]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

@@ -85,6 +85,14 @@ class Bgzf {
         for (auto& o : out) if (fwrite(o.data(), 1, o.size(), fp) != o.size()) fail("write error");
         buf.clear();
     }
+    // finished members made elsewhere (--device-stream 1: a tile's records, assembled and compressed on the device that simulated it).
+    // What is buffered becomes members first, and in device mode the batch in flight is written too, so the file keeps its order
+    // (the header's members precede the first tile's).
+    void put_members(const void* p, size_t n) {
+        flush();
+        if (device >= 0) dev_retrieve();
+        if (n && fwrite(p, 1, n, fp) != n) fail("write error");
+    }
     void close() {
         flush();
         if (device >= 0) { dev_retrieve(); vgl_bgzf_host_destroy(dev); dev = nullptr; for (auto& p : h_in) { vgl_host_free(p); p = nullptr; } }
@@ -209,6 +217,10 @@ class Sink {
     // encode different records at once) and appended to the file in order by put().
     void put(const std::string& bytes) { emit(bytes.data(), bytes.size()); }
     void put(const void* bytes, size_t n) { emit(bytes, n); }          // bytes encoded elsewhere (--device-text 1: a record's sample columns)
+    void put_members(const void* members, size_t n) {                  // finished BGZF members of records (--device-stream 1), see Bgzf::put_members
+        if (mode != 'z' && mode != 'b') fail("internal: put_members needs a BGZF output mode");
+        bg.put_members(members, n);
+    }
     void write_line(const std::string& line) { std::string b; encode_line(line, b); put(b); }
     void write_rec(const std::string& shared8, const std::vector<FmtDesc>& fmt) { std::string b; encode_rec(shared8, fmt, b); put(b); }
 

@@ -64,6 +64,7 @@ struct Args {
     int device_bcf = 0;                // --device-bcf 1: the FORMAT part of BCF records (-O u / -O b) encoded on the device
     int device_gvcf = 0;               // --device-gvcf 1: -doGVCF 1 blocks built and their / the records' sample columns formatted on the device
     int device_pileup = 0;             // --device-pileup 1: the N-wide part of -printPileup 1's lines formatted on the device
+    int device_stream = 0;             // --device-stream 1: a tile's records assembled and BGZF-compressed on the device that simulated it
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -112,6 +113,11 @@ static const char USAGE[] =
     "                   --device-pileup 0|1 [0: -printPileup 1's lines formatted on the host from the read dump; 1: their sample columns\n"
     "                   formatted on the device that simulated the tile, and the text crosses the link instead of the read dump.  Same\n"
     "                   bytes either way; needs -printPileup 1, refused with --depth inf; a run without a GPU fails instead of falling back]\n"
+    "                   --device-stream 0|1 [0: the records of -O b / -O z are put together on the host and compressed in batches; 1: a tile's\n"
+    "                   records are assembled and BGZF-compressed on the device that simulated the tile: only the host-built heads (the\n"
+    "                   fixed columns) go up and only compressed members come down.  The file decompresses to the same bytes; its\n"
+    "                   members restart at every tile (more and shorter members), the EOF member ends it once.  Needs -O b with\n"
+    "                   --device-bcf 1 or -O z with --device-text 1, refused with -doGVCF 1 and --depth inf; a run without a GPU fails]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 static Args parse_args(int argc, char** argv) {
@@ -193,6 +199,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--device-gvcf") a.device_gvcf = I(v);
         else if (f == "--device-bcf") a.device_bcf = I(v);
         else if (f == "--device-pileup") a.device_pileup = I(v);
+        else if (f == "--device-stream") a.device_stream = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -201,6 +208,8 @@ static Args parse_args(int argc, char** argv) {
     if (a.in_fn.empty()) die("Input file is not specified. Please use -i/--input option to specify the input file.");
     if (!a.have_depth && a.depths_fn.empty()) die("Average per-site read depth value is required. Please set it using --depth or --depths-file and re-run.");
     if (a.depths_fn.empty()) range(a.depth, 0.0, 500.0, "--depth");
+    range(a.device_stream, 0, 1, "--device-stream");
+    if (a.device_stream == 1 && a.depth_inf) die("--device-stream 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_gvcf == 1 && a.depth_inf) die("--device-gvcf 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_bcf == 1 && a.depth_inf) die("--device-bcf 1 is not supported with --depth inf (no tile is simulated).");
     if (a.depth_inf) {                                                          // io.cpp:781-850, 1011-1018
@@ -262,6 +271,13 @@ static Args parse_args(int argc, char** argv) {
         if (a.output_mode != "u" && a.output_mode != "b") die("--device-bcf 1 encodes BCF records: it needs -O u or -O b (found -O %s).", a.output_mode.c_str());
         if (a.do_gvcf && !a.device_gvcf)
             die("--device-bcf 1 is not supported with -doGVCF 1 alone (the host blocker reads the FORMAT arrays of every site); add --device-gvcf 1.");
+    }
+    if (a.device_stream) {                                      // (checked before any GPU work: nothing is written)
+        if (a.output_mode != "b" && a.output_mode != "z")
+            die("--device-stream 1 assembles and compresses BGZF streams: it needs -O b or -O z (found -O %s).", a.output_mode.c_str());
+        if (a.do_gvcf) die("--device-stream 1 is not supported with -doGVCF 1 (blocks carried across tiles are emitted by the host).");
+        if (a.output_mode == "b" && !a.device_bcf) die("--device-stream 1 with -O b assembles the records --device-bcf 1 encodes: add --device-bcf 1.");
+        if (a.output_mode == "z" && !a.device_text) die("--device-stream 1 with -O z assembles the records --device-text 1 formats: add --device-text 1.");
     }
     range(a.device_pileup, 0, 1, "--device-pileup");
     if (a.device_pileup) {                                      // (checked before any GPU work: nothing is written)
@@ -1071,6 +1087,9 @@ int main(int argc, char** argv) {
         PBuf<int32_t> st, na, nobs, idp, iad, iadf, iadr, dp, pl, ad, adf, adr;
         PBuf<int8_t> a2b; PBuf<float> qs, i16, gl, gp; PBuf<double> errp, pick;
         PBuf<uint8_t> text; PBuf<int64_t> toff; int64_t text_cap = 0;      // --device-text 1: the tile's sample columns and site offsets
+        // --device-stream 1: the sample columns stay in body buffer `sbuf` of the device's stream handle; the heads of the tile's records
+        // back to back and their offsets go up; sticket: the handle's ticket while the tile's members are on their way
+        int sbuf = 0; int32_t sticket = -1; std::string heads; std::vector<int64_t> hoff;
         // --device-gvcf 1: contig id and position per site (in), the items, block offsets and the first / last block's aggregates (out)
         std::vector<int32_t> contig; std::vector<int64_t> pos0;
         PBuf<int32_t> gitems, fdp, fpl, ldp, lpl; PBuf<int64_t> boff; vgl_gvcf_tile g;
@@ -1079,7 +1098,12 @@ int main(int argc, char** argv) {
         std::mutex m; std::condition_variable cv; bool done = false;
     };
     const size_t E = (size_t)TS * N;
-    const int R = 2 * D;                                        // tiles in flight: two per device
+    const bool dstream = a.device_stream != 0;                  // --device-stream 1: records assembled and compressed where the tile was simulated
+    // tiles in flight: two per device.  --device-stream 1: three -- an entry stays busy until its members are written, one tile behind
+    // the writer, and with two the device would wait for the writer before every other tile
+    const int R = (dstream ? 3 : 2) * D;
+    // the stream handles (one per device) are created once the contexts know what a tile's bodies can take (below)
+    std::vector<vgl_stream_host*> hstream(D, nullptr);
     std::vector<std::unique_ptr<TileBufs>> ring(R);
     // An entry's buffers are page-locked when the entry is first used (about 0.04 s per 250 MB): the second entry of a device is
     // prepared while the device already works on the first tile
@@ -1114,7 +1138,9 @@ int main(int argc, char** argv) {
         if (dtext) {
             B.text_cap = vgl_ctx_text_bound(ctxs[ri % (size_t)D], TS);
             if (B.text_cap < 0) die("%s 1: %s", dbcf ? "--device-bcf" : "--device-text", vgl_last_error());
-            B.text.resize((size_t)std::max<int64_t>(B.text_cap, 1)); B.toff.resize((size_t)TS + 1);
+            B.toff.resize((size_t)TS + 1);
+            if (dstream) { B.sbuf = (int)(ri / (size_t)D); B.hoff.resize((size_t)TS + 1); return; }     // (B.text is not allocated: the bodies stay on the device)
+            B.text.resize((size_t)std::max<int64_t>(B.text_cap, 1));
             return;
         }
         if (dgvcf) {
@@ -1137,6 +1163,27 @@ int main(int argc, char** argv) {
         if (a.add_fmt_adf) { B.adf.resize(E * A); B.o.fmt_adf = B.adf.data(); }
         if (a.add_fmt_adr) { B.adr.resize(E * A); B.o.fmt_adr = B.adr.data(); }
     };
+    if (dstream) {
+        // The largest head of a site, from what build_record writes.  Text: chrom, id, qual, filt and the input's own INFO; POS (at most 20
+        // digits); REF and ALT (at most five alleles, the longest "<NON_REF>", with commas: 32); eight tabs; and per INFO tag this run adds
+        // ";KEY=" (at most 5) and its numbers with commas, 16 bytes each (an int32 takes 11, kputd's forms and %g of a float 13, the binary
+        // placeholder "~%08x" 9): DP 1, QS and the AD tags one per allele (A), I16 16.  BCF (encode_head): 8 bytes of lengths, 24 of fixed
+        // fields, and every column typed -- a string or vector costs at most 5 bytes over its text, an added number 4 bytes, and the
+        // input's INFO at most twice its text (a one-digit number with its comma becomes a 4-byte float): bounded by the same sum with
+        // the INFO doubled and 64 bytes more.  The handle refuses a tile whose heads take more.
+        size_t longest = 0;
+        for (const Rec& r : vcf.recs) longest = std::max(longest, r.chrom.size() + r.id.size() + r.qual.size() + r.filt.size() + 2 * r.info.size());
+        const size_t n_added = (a.add_info_dp ? 1 : 0) + (a.add_qs ? A : 0) + (a.add_i16 ? 16 : 0) + (size_t)A * ((a.add_info_ad ? 1 : 0) + (a.add_info_adf ? 1 : 0) + (a.add_info_adr ? 1 : 0));
+        const size_t per_site = longest + 20 + 32 + 8 + 6 * 5 + 16 * n_added + 64 + 64;
+        const int64_t max_head = (int64_t)TS * (int64_t)per_site;
+        for (int d = 0; d < D; d++) {
+            const int64_t cap = vgl_ctx_text_bound(ctxs[d], TS);
+            if (cap < 0) die("--device-stream 1: %s", vgl_last_error());
+            if (vgl_stream_host_create(devices[d], R / D, TS, max_head, std::max<int64_t>(cap, 1), &hstream[d]) != VGL_OK)
+                die("--device-stream 1: %s (device %d)", vgl_last_error(), devices[d]);
+            if (vgl_ctx_text_device(ctxs[d], 1) != VGL_OK) die("--device-stream 1: %s", vgl_last_error());
+        }
+    }
     alloc_entry(0);
     // one worker per device: simulates the tiles handed to it, in order
     struct Worker { std::thread th; std::mutex m; std::condition_variable cv; std::vector<TileBufs*> q; size_t head = 0; bool stop = false;
@@ -1151,7 +1198,8 @@ int main(int argc, char** argv) {
         Worker* W = workers[d].get();
         vgl_ctx* ctx = ctxs[d];
         const int32_t* dps = a.gvcf_dps.data(); const int32_t n_dps = (int32_t)a.gvcf_dps.size();
-        W->th = std::thread([W, ctx, &now, dtext, dgvcf, dpile, dps, n_dps]() {
+        vgl_stream_host* hs = hstream[d];
+        W->th = std::thread([W, ctx, hs, &now, dtext, dgvcf, dpile, dps, n_dps]() {
             // a tile is submitted (vgl_simulate_tile_async) before the previous one is waited for: its kernels run while the
             // previous tile's tags are still on their way to the host
             TileBufs* prev = nullptr; int32_t prev_ticket = 0;
@@ -1170,11 +1218,13 @@ int main(int argc, char** argv) {
                 if (B && dgvcf && vgl_simulate_tile_gvcf_async(ctx, B->t0, B->ns, B->gt.data(), B->contig.data(), B->pos0.data(), dps, n_dps, &B->o, &B->g,
                                                                &ticket) != VGL_OK)
                     die("%s", vgl_last_error());
-                if (B && dtext && vgl_simulate_tile_text_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, B->text.data(), B->text_cap, B->toff.data(), &ticket) != VGL_OK)
+                // (--device-stream 1: the text stays on the device, in the entry's body buffer of the stream handle)
+                if (B && dtext && vgl_simulate_tile_text_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, hs ? vgl_stream_host_body(hs, B->sbuf) : B->text.data(),
+                                                               B->text_cap, B->toff.data(), &ticket) != VGL_OK)
                     die("%s", vgl_last_error());
                 if (prev) {
                     if (vgl_tile_wait(ctx, prev_ticket) != VGL_OK) die("%s", vgl_last_error());
-                    if (dtext) W->text_bytes += (double)prev->toff[prev->ns];
+                    if (dtext && !hs) W->text_bytes += (double)prev->toff[prev->ns];
                     if (dgvcf) W->text_bytes += (double)prev->g.text_needed;
                     if (dpile) W->text_bytes += (double)prev->pt.text_needed;
                     W->tiles += 1; W->sites += prev->ns; W->t_last = now();
@@ -1300,6 +1350,17 @@ int main(int argc, char** argv) {
         }
         lap(5);
     };
+    // --device-stream 1: bytes of heads and offsets sent up and of members brought back, per device (--verbose 1)
+    std::vector<double> stream_up(D, 0.0), stream_down(D, 0.0);
+    // the members of a tile whose heads were submitted: to the file, in tile order
+    auto retire_tile = [&](TileBufs& B) {
+        const uint8_t* m; int64_t mn, raw;
+        if (vgl_stream_host_wait(hstream[B.dev], B.sticket, &m, &mn, &raw) != VGL_OK) die("--device-stream 1: %s", vgl_last_error());
+        if (raw != B.hoff[B.ns] + B.toff[B.ns]) die("--device-stream 1: the device assembled %lld bytes of %lld", (long long)raw, (long long)(B.hoff[B.ns] + B.toff[B.ns]));
+        out.put_members(m, (size_t)mn);
+        stream_down[B.dev] += (double)mn;
+        B.sticket = -1;
+    };
     // everything the writer does with one finished tile, in site order (TSV lines, pileup, gVCF blocks, records)
     auto write_tile = [&](TileBufs& B) {
         const int ns = B.ns;
@@ -1378,6 +1439,17 @@ int main(int argc, char** argv) {
                 if (dtext) { enc[i] = std::move(sh); return; }
                 out.encode_rec(sh, fmt, enc[i]);
             });
+            if (dstream) {                                          // the heads go up; the device puts the records together and compresses them
+                B.heads.clear();
+                for (int i = 0; i < ns; i++) { B.hoff[i] = (int64_t)B.heads.size(); B.heads += enc[i]; if (B.st[i] >= 0) n_out++; }
+                B.hoff[ns] = (int64_t)B.heads.size();
+                lap(4);
+                if (vgl_stream_host_submit(hstream[B.dev], B.sbuf, ns, (const uint8_t*)B.heads.data(), B.hoff.data(), B.toff.data(), &B.sticket) != VGL_OK)
+                    die("--device-stream 1: %s", vgl_last_error());
+                stream_up[B.dev] += (double)B.heads.size() + 16.0 * (ns + 1);
+                lap(5);
+                return;
+            }
             lap(4);
             for (int i = 0; i < ns; i++) if (B.st[i] >= 0) {
                 out.put(enc[i]);
@@ -1390,11 +1462,12 @@ int main(int argc, char** argv) {
 
     // ---- the tile ring: produce (decode sites, hand the tile to its device) up to R tiles ahead, write in order
     size_t produced = 0, consumed = 0;
+    size_t retired = 0;                                         // --device-stream 1: tiles whose members are written (one behind `consumed`); else = consumed
     bool eof = false;
     std::map<std::string, int32_t> contig_ids; const std::string* last_chrom = nullptr; int32_t last_id = 0;
     lap(6);
     for (;;) {
-        while (!eof && produced - consumed < (size_t)R) {
+        while (!eof && produced - retired < (size_t)R) {
             alloc_entry(produced % R);
             TileBufs& B = *ring[produced % R];
             B.ns = 0; B.t0 = (int64_t)n_sites_total; B.done = false; B.dev = (int)(produced % D);
@@ -1427,7 +1500,11 @@ int main(int argc, char** argv) {
         write_tile(B);
         lap(5);
         consumed++;
+        // --device-stream 1: this tile is being assembled and compressed; meanwhile the one before it is written
+        if (dstream) { while (retired + 1 < consumed) { retire_tile(*ring[retired % R]); retired++; } lap(5); }
+        else retired = consumed;
     }
+    if (dstream) { t_mark = now(); while (retired < consumed) { retire_tile(*ring[retired % R]); retired++; } lap(5); }
     for (auto& W : workers) { { std::lock_guard<std::mutex> lk(W->m); W->stop = true; } W->cv.notify_all(); W->th.join(); }
     if (a.do_gvcf && gv.prepare(nullptr) == GvcfBlocker::FLUSH_BLOCK) { gv.emit(out, N); n_out++; }
     t_mark = now();
@@ -1445,7 +1522,8 @@ int main(int argc, char** argv) {
             const Worker& W = *workers[d];
             vgl_ctx_info_t ci; memset(&ci, 0, sizeof ci); ci.size = (int32_t)sizeof ci;
             (void)vgl_ctx_info(ctxs[d], &ci);
-            const double dt = W.t_last - W.t_first, gb = (bytes_per_site * (double)W.sites + W.text_bytes) / 1e9;
+            const double dt = W.t_last - W.t_first, gb = (bytes_per_site * (double)W.sites + W.text_bytes + stream_down[d]) / 1e9;
+            if (dstream) fprintf(stderr, "[device %d] --device-stream 1: %.6f GB of heads and offsets sent up, %.6f GB of BGZF members copied back\n", devices[d], stream_up[d] / 1e9, stream_down[d] / 1e9);
             fprintf(stderr, "[device %d] %ld tiles, %ld sites, %.3f GB of tags copied back in %.3f s = %.1f GB/s, %.3g evaluations/s; context: %.2f GB workspace, k_sample build %d, fused %d (split %d)\n",
                     devices[d], W.tiles, W.sites, gb, dt > 0 ? dt : 0.0, dt > 0 ? gb / dt : 0.0, dt > 0 ? (double)W.sites * N / dt : 0.0,
                     (double)ci.workspace_bytes / 1e9, ci.sample_lean, ci.fused, ci.fused_split);

@@ -220,6 +220,7 @@ struct vgl_ctx {
         // vgl_simulate_tile_text_async: the FORMAT tags formatted on the device (vgl_text.hip); the text is copied back by vgl_tile_wait,
         // which knows its size
         bool text = false; uint8_t* h_text = nullptr; int64_t text_cap = 0; int64_t* h_toff = nullptr;
+        bool text_dev = false;                                      // vgl_ctx_text_device: h_text is device memory, written in place
         uint32_t dev_fields = 0;                                    // fields of d_out the tile's kernels wrote (bit f: FIELDS[f])
         uint8_t* d_text = nullptr; int64_t d_text_bytes = 0; int64_t* d_toff = nullptr; void* d_tws = nullptr; int64_t d_tws_bytes = 0;
         // vgl_simulate_tile_gvcf_async: the tile blocked on the device (vgl_gvcf.hip), its record and block columns formatted there
@@ -239,6 +240,7 @@ struct vgl_ctx {
     // vgl_ctx_bcf_keys: the text / gVCF tile calls deliver BCF typed vectors (vgl_bcf.hip) instead of text; dictionary ids of
     // DP, GL, PL, GP, AD, ADF, ADR
     bool bcf = false; int32_t bcf_keys[7] = {0, 0, 0, 0, 0, 0, 0};
+    bool text_dev = false;                                          // vgl_ctx_text_device: the text tile call's `text` is device memory
     hipStream_t s_text = nullptr;                                   // text copies of vgl_tile_wait (never behind the next tile's copies)
     // a draw deeper than the staging capacity (vcfgl grows its read buffers, bcf_utils.cpp:618-648): the host entry points run such a tile again on
     // this sibling context, created on first need with the staging layout's largest capacity (VGL_READ_CAP_MAX reads) and tiles of at most
@@ -1154,6 +1156,13 @@ extern "C" int vgl_ctx_bcf_keys(vgl_ctx* c, const int32_t* key_ids, int32_t n) {
     return VGL_OK;
 }
 
+extern "C" int vgl_ctx_text_device(vgl_ctx* c, int32_t on) {
+    if (!c) return fail(VGL_E_ARG, "vgl_ctx_text_device: null context");
+    for (int k = 0; k < 2; k++) if (c->slot[k].busy) return fail(VGL_E_ARG, "vgl_ctx_text_device: a tile is in flight (vgl_tile_wait it first)");
+    c->text_dev = on != 0;
+    return VGL_OK;
+}
+
 extern "C" int64_t vgl_ctx_text_bound(const vgl_ctx* c, int32_t n_sites) {
     if (!c || n_sites < 0) return -1;
     vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
@@ -1171,14 +1180,15 @@ static int enqueue_text(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites) {
     vgl_text_field tf[VGL_TEXT_MAX_FIELDS]; int fid[VGL_TEXT_MAX_FIELDS];
     const int nf = text_fields(c, tf, fid);
     for (int k = 0; k < nf; k++) tf[k].base = S.d_out[fid[k]];
+    uint8_t* const dst = S.text_dev ? S.h_text : S.d_text;         // (a device destination is written in place: no copy in vgl_tile_wait)
     if (c->bcf) {
         vgl_bcf_field bf[VGL_TEXT_MAX_FIELDS];
         bcf_fields(c, tf, fid, nf, bf);
         return vgl_bcf_encode_device(c->device, bf, nf, c->dp.n_samples, n_sites, (const int32_t*)S.d_out[0], (const int32_t*)S.d_out[1],
-                                     S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
+                                     dst, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
     }
     return vgl_text_format_device(c->device, tf, nf, c->dp.n_samples, n_sites, (const int32_t*)S.d_out[0], (const int32_t*)S.d_out[1],
-                                  S.d_text, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
+                                  dst, S.text_cap, S.d_toff, S.d_tws, S.d_tws_bytes, c->s_compute);
 }
 
 extern "C" int vgl_gvcf_edges_device(int32_t n_samples, int32_t n_sites, const vgl_gvcf_in* in, const vgl_gvcf_out* out, void* workspace,
@@ -1417,7 +1427,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
             S.d_tws_bytes = ws;
         }
         if (!S.d_toff) HIPCHK(hipMalloc((void**)&S.d_toff, sizeof(int64_t) * ((size_t)c->max_sites + 1)));
-        if (S.d_text_bytes < S.text_cap) {
+        if (!S.text_dev && S.d_text_bytes < S.text_cap) {
             if (S.d_text) (void)hipFree(S.d_text);
             S.d_text = nullptr; S.d_text_bytes = 0;
             HIPCHK(hipMalloc((void**)&S.d_text, (size_t)S.text_cap));
@@ -1503,6 +1513,7 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     S.rc = VGL_OK; *S.h_flag = 0;
     S.site0 = site0; S.n_sites = n_sites; S.o = *o;
     S.text = want_text; S.h_text = text; S.text_cap = text_cap; S.h_toff = toff;
+    S.text_dev = want_text && c->text_dev;
     S.gvcf = gq != nullptr; S.h_gv = gq ? gq->g : nullptr;
     S.pile = pile;
     if (pile) { const int rc = pileup_qual_char(c, &S.pile_qc); if (rc != VGL_OK) { S.pile = nullptr; return rc; } }
@@ -1672,7 +1683,7 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
     if (total < 0 || total > S.text_cap)
         return fail(VGL_E_CAPACITY, "the tile's text needs %lld bytes, text_cap is %lld (offsets[n_sites] holds the size; vgl_ctx_text_bound bounds it)",
                     (long long)total, (long long)S.text_cap);
-    if (total > 0) {
+    if (total > 0 && !S.text_dev) {
         HIPCHK(hipMemcpyAsync(S.h_text, S.d_text, (size_t)total, hipMemcpyDeviceToHost, c->s_text));
         HIPCHK(hipStreamSynchronize(c->s_text));
     }
