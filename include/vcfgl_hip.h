@@ -660,6 +660,49 @@ VGL_API int vgl_stream_host_submit(vgl_stream_host* h, int32_t k, int32_t n_site
 VGL_API int vgl_stream_host_wait(vgl_stream_host* h, int32_t ticket, const uint8_t** members, int64_t* members_n, int64_t* raw_n);
 VGL_API int vgl_stream_host_destroy(vgl_stream_host* h);
 
+/* ---- genotype calls and their discordance against the truth, tallied on the device (ABI 7, additive) -----------------------------
+ * What the reference's misc/gtDiscordance computes from a call file and -printTruth's file, from a tile's arrays where they are
+ * computed.  Per kept site (site_status >= 0) and sample:
+ *   call missing  fmt_dp == 0 (a missing true genotype is simulated with depth 0), a true allele nibble outside 0 .. 3, or a site without a
+ *                 genotype of two A/C/G/T alleles: callmis[sample] goes up and nothing else is counted
+ *   call          the lowest g < nG(site) with the smallest PL among the genotypes whose two alleles both map to A/C/G/T through
+ *                 alleles2acgt -- a genotype with the unobserved allele is never called; g = b (b + 1) / 2 + a, a <= b (htslib's order)
+ *   GQ            gtDiscordance -doGQ 8: the smallest PL over ALL g < nG(site) that is not 0, capped at 127; 127 when there is none
+ *                 (a one-allele site, every PL 0): 1 .. 127
+ *   PL            pl_u8 or pl.  An int32 value outside [0, 255] (VGL_INT32_MISSING included) counts as 255, the byte pl_u8 holds for it:
+ *                 both forms give the same table
+ *   cell          true bases (the nibbles of gt) against called bases as unordered pairs: VGL_DISC_*
+ * A skipped site (site_status < 0) is a site of the truth file that the call file lacks.
+ * The table is int64: cell[sample][VGL_DISC_CELLS][128] indexed by GQ (index 0 unused), then callmis[sample], then sites[2] = kept,
+ * skipped.  Totals over samples are left to the reader.  Every count is an integer sum: the table depends neither on the tiling nor on
+ * the order of the additions.
+ *   vgl_disc_table_len     elements of the table: n_samples * (6 * 128 + 1) + 2 (-1 for n_samples < 0).  Pure host arithmetic.
+ *   vgl_disc_tally_device  ADDS one tile to `table`.  Every pointer is device memory of `device`; exactly one of pl_u8 / pl is non-NULL,
+ *                          in `layout` (VGL_LAYOUT_*) with max_genotypes planes per site (vgl_max_genotypes; 1 .. 15); gt as for
+ *                          vgl_simulate_tile.  Work is enqueued on `hip_stream`; the call returns without synchronising.
+ *   vgl_ctx_discordance    on != 0: every following tile of the context is tallied behind its likelihood kernel into a table the context
+ *                          owns (zeroed when it is first switched on), whichever entry point enqueues it: vgl_simulate_tile, _async,
+ *                          _device, _text_async, _gvcf_async, with or without vgl_ctx_bcf_keys / vgl_ctx_pileup_next.  The caller need
+ *                          not ask for PL or DP: the context keeps what the tally reads on the device, and the caller's own outputs are
+ *                          unchanged.  A tile whose draw exceeded the staging capacity is not counted; the host entry points count the
+ *                          run that replaces it, once (vgl_simulate_tile_device: nothing is counted from such a tile until
+ *                          vgl_ctx_check has cleared the error).  Call it while no tile of the context is in flight.
+ *   vgl_ctx_discordance_read  waits for the device, copies the table to host_table [vgl_disc_table_len(n_samples)] and, with reset != 0,
+ *                          zeroes the context's table. */
+#define VGL_DISC_CELLS          6
+#define VGL_DISC_HOM_HOM_CONC   0
+#define VGL_DISC_HOM_HOM_DISC   1
+#define VGL_DISC_HET_HET_CONC   2
+#define VGL_DISC_HET_HET_DISC   3
+#define VGL_DISC_HOM_HET        4   /* always discordant */
+#define VGL_DISC_HET_HOM        5   /* always discordant */
+VGL_API int64_t vgl_disc_table_len(int32_t n_samples);
+VGL_API int vgl_disc_tally_device(int32_t device, int32_t n_samples, int32_t n_sites, int32_t max_genotypes, int32_t layout,
+                                  const int32_t* site_status, const int32_t* n_alleles, const int8_t* alleles2acgt, const int32_t* fmt_dp,
+                                  const uint8_t* pl_u8, const int32_t* pl, const uint8_t* gt, int64_t* table, void* hip_stream);
+VGL_API int vgl_ctx_discordance(vgl_ctx* ctx, int32_t on);
+VGL_API int vgl_ctx_discordance_read(vgl_ctx* ctx, int64_t* host_table, int32_t reset);
+
 #ifdef __cplusplus
 }
 #endif

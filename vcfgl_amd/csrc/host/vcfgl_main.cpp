@@ -65,6 +65,9 @@ struct Args {
     int device_gvcf = 0;               // --device-gvcf 1: -doGVCF 1 blocks built and their / the records' sample columns formatted on the device
     int device_pileup = 0;             // --device-pileup 1: the N-wide part of -printPileup 1's lines formatted on the device
     int device_stream = 0;             // --device-stream 1: a tile's records assembled and BGZF-compressed on the device that simulated it
+    int gt_disc = 0;                   // --gt-discordance 1: calls tallied against the truth on the device, <prefix>.discordance.tsv
+    int disc_gq = 0;                   // --discordance-gq 0|3|4|5|6: gtDiscordance's -doGQ layout of that file
+    int records = 1;                   // --records 0: no record file; only the discordance table comes back
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -118,6 +121,15 @@ static const char USAGE[] =
     "                   fixed columns) go up and only compressed members come down.  The file decompresses to the same bytes; its\n"
     "                   members restart at every tile (more and shorter members), the EOF member ends it once.  Needs -O b with\n"
     "                   --device-bcf 1 or -O z with --device-text 1, refused with -doGVCF 1 and --depth inf; a run without a GPU fails]\n"
+    "                   --gt-discordance 0|1 [0; 1: every simulated tile is genotyped on the device that simulated it (maximum-likelihood call\n"
+    "                   from PL over the A/C/G/T genotypes, GQ = the second smallest PL capped at 127) and compared with its true genotypes;\n"
+    "                   the counts are written to <prefix>.discordance.tsv, what misc/gtDiscordance prints for the records and -printTruth's\n"
+    "                   file.  Works with every output mode, --device-* path, --devices and --rng-mode; refused with --depth inf]\n"
+    "                   --discordance-gq 0|3|4|5|6 [0: gtDiscordance's -doGQ layout of that file: 0 one line per sample, 3 / 4 counts by GQ\n"
+    "                   over all samples, 5 / 6 by sample and GQ (7 and 8 equal 6 here: every call has a GQ)]\n"
+    "                   --records 0|1 [1; 0: no record file is opened and no FORMAT array, text or encoded record crosses the link: only the\n"
+    "                   discordance table comes back.  Needs --gt-discordance 1; refused with -printPileup 1, -printTruth 1, -doGVCF 1 and\n"
+    "                   the per-read listings]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 static Args parse_args(int argc, char** argv) {
@@ -200,6 +212,9 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--device-bcf") a.device_bcf = I(v);
         else if (f == "--device-pileup") a.device_pileup = I(v);
         else if (f == "--device-stream") a.device_stream = I(v);
+        else if (f == "--gt-discordance") a.gt_disc = I(v);
+        else if (f == "--discordance-gq") a.disc_gq = I(v);
+        else if (f == "--records") a.records = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -209,6 +224,20 @@ static Args parse_args(int argc, char** argv) {
     if (!a.have_depth && a.depths_fn.empty()) die("Average per-site read depth value is required. Please set it using --depth or --depths-file and re-run.");
     if (a.depths_fn.empty()) range(a.depth, 0.0, 500.0, "--depth");
     range(a.device_stream, 0, 1, "--device-stream");
+    // the discordance tally and a run without records (checked before any GPU work: nothing is written)
+    range(a.gt_disc, 0, 1, "--gt-discordance"); range(a.records, 0, 1, "--records");
+    if (a.disc_gq != 0 && (a.disc_gq < 3 || a.disc_gq > 6)) die("[Bad argument value: '--discordance-gq %d'] Allowed values are 0, 3, 4, 5, 6", a.disc_gq);
+    if (a.disc_gq != 0 && !a.gt_disc) die("--discordance-gq %d selects the layout of --gt-discordance 1's file: add --gt-discordance 1.", a.disc_gq);
+    if (a.gt_disc && a.depth_inf) die("--gt-discordance 1 is not supported with --depth inf (no tile is simulated: every call would be the truth).");
+    if (!a.records) {
+        if (!a.gt_disc) die("--records 0 writes no record file: it needs --gt-discordance 1, whose table is then the run's only output.");
+        if (a.print_pileup) die("--records 0 is not supported with -printPileup 1 (the pileup is a listing of every read).");
+        if (a.print_truth) die("--records 0 is not supported with -printTruth 1 (the truth file is a record file).");
+        if (a.do_gvcf) die("--records 0 is not supported with -doGVCF 1 (gVCF blocks are records).");
+        if (a.print_bpe || a.print_qs_err || a.print_gl_err || a.print_qscores)
+            die("--records 0 is not supported with -printBasePickError / -printQsError / -printGlError / -printQScores 1 (per-read listings).");
+        a.device_text = a.device_bcf = a.device_gvcf = a.device_stream = a.device_pileup = 0;      // nothing to format, encode or assemble
+    }
     if (a.device_stream == 1 && a.depth_inf) die("--device-stream 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_gvcf == 1 && a.depth_inf) die("--device-gvcf 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_bcf == 1 && a.depth_inf) die("--device-bcf 1 is not supported with --depth inf (no tile is simulated).");
@@ -827,6 +856,64 @@ struct RunLog {
     }
 };
 
+// <prefix>.discordance.tsv: the table of --gt-discordance 1 (include/vcfgl_hip.h: cell[sample][6][128] by GQ, callmis[sample], sites[2]) in
+// the layout misc/gtDiscordance prints for -doGQ `mode` (gtDiscordance.cpp:629-833: columns, order, %d / %f; rows k = 1 .. 129)
+static std::string format_discordance(const std::vector<int64_t>& t, const std::vector<std::string>& names, int mode) {
+    const size_t n = names.size();
+    const int64_t* cell = t.data(); const int64_t* mis = cell + n * VGL_DISC_CELLS * 128; const int64_t* sites = mis + n;
+    auto at = [&](size_t i, int c, int k) -> long long { return k < 128 ? (long long)cell[(i * VGL_DISC_CELLS + c) * 128 + k] : 0; };
+    auto rate = [](double num, double den) { char b[64]; if (den == 0) return std::string("-nan"); snprintf(b, sizeof b, "%f", num / den); return std::string(b); };
+    std::string o; char b[512];
+    if (mode == 0) {
+        const long long kept = sites[0], skipped = sites[1], total = kept + skipped;
+        for (size_t i = 0; i < n; i++) {
+            long long c[VGL_DISC_CELLS];
+            for (int j = 0; j < VGL_DISC_CELLS; j++) { c[j] = 0; for (int k = 0; k < 128; k++) c[j] += at(i, j, k); }
+            const long long compared = c[0] + c[1] + c[2] + c[3] + c[4] + c[5], disc = c[1] + c[3] + c[4] + c[5];
+            char m[64]; snprintf(m, sizeof m, "%f", total ? 1.0 - (double)compared / (double)total : 0.0);
+            o += names[i];
+            snprintf(b, sizeof b, "\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t", total, kept, compared, (long long)mis[i], disc, skipped, compared - disc); o += b;
+            o += total ? std::string(m) : std::string("-nan"); o += '\t'; o += rate((double)disc, (double)compared); o += '\t'; o += rate((double)(compared - disc), (double)compared);
+            snprintf(b, sizeof b, "\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld", c[VGL_DISC_HOM_HOM_CONC], c[VGL_DISC_HET_HET_CONC], c[VGL_DISC_HOM_HOM_DISC], c[VGL_DISC_HOM_HET],
+                     c[VGL_DISC_HET_HOM], c[VGL_DISC_HET_HET_DISC]); o += b;
+            const int ord[6] = {VGL_DISC_HOM_HOM_CONC, VGL_DISC_HET_HET_CONC, VGL_DISC_HOM_HOM_DISC, VGL_DISC_HOM_HET, VGL_DISC_HET_HOM, VGL_DISC_HET_HET_DISC};
+            for (int j : ord) { o += '\t'; o += rate((double)c[j], (double)compared); }
+            o += '\n';
+        }
+        return o;
+    }
+    // a -doGQ 4 row: discordant (all, hom->hom, hom->het, het->hom, het->het), concordant (all, hom->hom, het->het)
+    auto row = [&](size_t i0, size_t i1, int k, long long r[8]) {
+        for (int j = 0; j < 8; j++) r[j] = 0;
+        for (size_t i = i0; i < i1; i++) {
+            r[1] += at(i, VGL_DISC_HOM_HOM_DISC, k); r[2] += at(i, VGL_DISC_HOM_HET, k); r[3] += at(i, VGL_DISC_HET_HOM, k); r[4] += at(i, VGL_DISC_HET_HET_DISC, k);
+            r[6] += at(i, VGL_DISC_HOM_HOM_CONC, k); r[7] += at(i, VGL_DISC_HET_HET_CONC, k);
+        }
+        r[0] = r[1] + r[2] + r[3] + r[4]; r[5] = r[6] + r[7];
+    };
+    long long r[8];
+    if (mode == 3 || mode == 4) {
+        for (int k = 1; k < 130; k++) {
+            row(0, n, k, r);
+            if (mode == 3) snprintf(b, sizeof b, "%d\t%lld\t%lld\n", k, r[0], r[5]);
+            else snprintf(b, sizeof b, "%d\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\n", k, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
+            o += b;
+        }
+        return o;
+    }
+    for (size_t i = 0; i < n; i++) {
+        long long compared = 0;
+        for (int j = 0; j < VGL_DISC_CELLS; j++) for (int k = 0; k < 128; k++) compared += at(i, j, k);
+        for (int k = 1; k < 130; k++) {
+            row(i, i + 1, k, r);
+            if (mode == 5) snprintf(b, sizeof b, "%zu\t%d\t%lld\t%lld\t%lld\n", i, k, r[0], r[5], compared);
+            else snprintf(b, sizeof b, "%zu\t%d\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\n", i, k, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], compared);
+            o += b;
+        }
+    }
+    return o;
+}
+
 // ---------------------------------------------------------------------------------------
 int main(int argc, char** argv) {
     if (argc >= 2 && !strcmp(argv[1], "--format-floats")) {
@@ -1012,12 +1099,14 @@ int main(int argc, char** argv) {
     std::vector<vgl_ctx*> ctxs(D, nullptr);
     t_mark = now();
     for (int d = 0; d < D; d++) if (vgl_ctx_create(&p, devices[d], TS, &ctxs[d]) != VGL_OK) die("%s", vgl_last_error());
+    if (a.gt_disc) for (int d = 0; d < D; d++) if (vgl_ctx_discordance(ctxs[d], 1) != VGL_OK) die("--gt-discordance 1: %s", vgl_last_error());
     lap(2);
     const int A = vgl_max_alleles(&p), G = vgl_max_genotypes(&p);
+    const bool rec0 = a.records == 0;                         // --records 0: no record file, no FORMAT array back; the tiles are simulated and tallied
 
     // ---- output header (set_hdr, bcf_utils.cpp:511-615): input header minus FORMAT/GT, plus our tags
     vsink::Sink out; out.text_float = put_float;
-    {
+    if (!rec0) {
         std::vector<std::string> hdr;
         char hb[128];
         for (const std::string& h : vcf.header) if (h.find("##FORMAT=<ID=GT,") == std::string::npos) hdr.push_back(h);
@@ -1078,7 +1167,7 @@ int main(int argc, char** argv) {
     // --device-gvcf 1: the same for -doGVCF 1; the blocks are built on the device, the FORMAT arrays stay there
     const bool dgvcf = a.device_gvcf != 0;
     // --device-pileup 1: the read dump and DP stay on the device (the pileup's sample columns come back as text)
-    const bool want_dp = (a.add_fmt_dp && !dtext && !dgvcf) || (a.do_gvcf && !dgvcf) || (pile_fp && !dpile) || dump_reads;
+    const bool want_dp = !rec0 && ((a.add_fmt_dp && !dtext && !dgvcf) || (a.do_gvcf && !dgvcf) || (pile_fp && !dpile) || dump_reads);
     struct TileBufs {
         int ns = 0; int64_t t0 = 0; int dev = 0;
         std::vector<SiteMeta> meta; std::vector<uint8_t> gt;
@@ -1121,6 +1210,7 @@ int main(int argc, char** argv) {
         B.st.resize(TS); B.na.resize(TS); B.nobs.resize(TS); B.a2b.resize((size_t)TS * 5);
         memset(&B.o, 0, sizeof B.o);
         B.o.site_status = B.st.data(); B.o.n_alleles = B.na.data(); B.o.n_alleles_obs = B.nobs.data(); B.o.alleles2acgt = B.a2b.data();
+        if (rec0) return;                                        // (the per-site status and alleles above: a few bytes per site, for the run's summary)
         B.idp.resize(TS); B.o.info_dp = B.idp.data();           // also tells which sites reach the read loop (TSV dumps)
         if (a.add_info_ad) { B.iad.resize((size_t)TS * A); B.o.info_ad = B.iad.data(); }
         if (a.add_info_adf) { B.iadf.resize((size_t)TS * A); B.o.info_adf = B.iadf.data(); }
@@ -1190,7 +1280,7 @@ int main(int argc, char** argv) {
                     long tiles = 0, sites = 0; double t_first = -1.0, t_last = 0.0; double text_bytes = 0.0; };          // --verbose 1: what this device did (written by its own thread, read after the join)
     // bytes a finished tile brings back over the link, per site (the FORMAT arrays dominate: sample-major slabs, copied whole)
     // (--device-text 1 / --device-gvcf 1 / --device-bcf 1: the text or the encoded vectors instead of the FORMAT arrays, counted as they come back)
-    const double bytes_per_site = (double)N * ((want_dp ? 4.0 : 0.0) + (dtext || dgvcf ? 0.0 : 4.0 * G * ((a.add_gl ? 1 : 0) + (a.add_pl ? 1 : 0) + (a.add_gp ? 1 : 0)) +
+    const double bytes_per_site = rec0 ? 64.0 : (double)N * ((want_dp ? 4.0 : 0.0) + (dtext || dgvcf ? 0.0 : 4.0 * G * ((a.add_gl ? 1 : 0) + (a.add_pl ? 1 : 0) + (a.add_gp ? 1 : 0)) +
                                                4.0 * A * ((a.add_fmt_ad ? 1 : 0) + (a.add_fmt_adf ? 1 : 0) + (a.add_fmt_adr ? 1 : 0)))) + 64.0;
     std::vector<std::unique_ptr<Worker>> workers(D);
     for (int d = 0; d < D; d++) {
@@ -1364,6 +1454,7 @@ int main(int argc, char** argv) {
     // everything the writer does with one finished tile, in site order (TSV lines, pileup, gVCF blocks, records)
     auto write_tile = [&](TileBufs& B) {
         const int ns = B.ns;
+        if (rec0) { for (int i = 0; i < ns; i++) if (B.st[i] < 0) n_skipped++; return; }
         for (int i = 0; i < ns; i++) {
             const SiteMeta& S = B.meta[i];
             if ((dump_pick || dump_reads) && B.st[i] != VGL_SITE_SKIP_EMPTY && B.idp[i] > 0) {      // sites that reach the read loop (vcfgl.cpp:396-404)
@@ -1508,8 +1599,20 @@ int main(int argc, char** argv) {
     for (auto& W : workers) { { std::lock_guard<std::mutex> lk(W->m); W->stop = true; } W->cv.notify_all(); W->th.join(); }
     if (a.do_gvcf && gv.prepare(nullptr) == GvcfBlocker::FLUSH_BLOCK) { gv.emit(out, N); n_out++; }
     t_mark = now();
-    out.close();
+    if (!rec0) out.close();
     if (a.print_truth) truth_sink.close();
+    if (a.gt_disc) {                                            // every context's table, summed: integer counts, the same for any device count
+        const int64_t len = vgl_disc_table_len(N);
+        std::vector<int64_t> table((size_t)len, 0), part((size_t)len);
+        for (int d = 0; d < D; d++) {
+            if (vgl_ctx_discordance_read(ctxs[d], part.data(), 0) != VGL_OK) die("--gt-discordance 1: %s", vgl_last_error());
+            for (int64_t k = 0; k < len; k++) table[(size_t)k] += part[(size_t)k];
+        }
+        const std::string tsv_text = format_discordance(table, vcf.samples, a.disc_gq);
+        FILE* fp = fopen((a.out_prefix + ".discordance.tsv").c_str(), "w");
+        if (!fp) die("Could not open file: %s.discordance.tsv", a.out_prefix.c_str());
+        if (fwrite(tsv_text.data(), 1, tsv_text.size(), fp) != tsv_text.size() || fclose(fp) != 0) die("Could not write file: %s.discordance.tsv", a.out_prefix.c_str());
+    }
     lap(5);
     if (pile_fp) { pile.close(); fclose(pile_fp); }
     // contexts and page-locked buffers are not torn down one by one (0.06 s): the process ends below with _exit(), after the run
@@ -1535,7 +1638,9 @@ int main(int argc, char** argv) {
     snprintf(sb, sizeof sb, "\n\n-> Simulation finished successfully.\n\nSummary:\n\tNumber of samples: %d\n\tTotal number of sites simulated: %zu\n"
                             "\tNumber of sites included in simulation output file: %ld\n\tNumber of sites skipped: %ld\n", N, n_sites_total, n_out, n_skipped);
     fputs(sb, stderr);
-    std::vector<std::string> files = {"-> Simulation output file: " + a.out_prefix + ext};
+    std::vector<std::string> files;
+    if (!rec0) files.push_back("-> Simulation output file: " + a.out_prefix + ext);
+    if (a.gt_disc) files.push_back("-> Genotype discordance file: " + a.out_prefix + ".discordance.tsv");
     if (a.print_pileup) files.push_back("-> Pileup output file: " + a.out_prefix + ".pileup.gz");
     if (a.print_truth) files.push_back("-> True genotypes output file: " + a.out_prefix + ".truth" + ext);
     if (a.print_bpe) files.push_back("-> Base pick error output: stdout");

@@ -35,6 +35,9 @@ static int hook_int(const char* name, int dflt) { const char* v = hook_env(name)
 extern "C" const char* vgl_last_error(void) { return g_err; }
 extern "C" int vgl_abi_version(void) { return VGL_ABI_VERSION; }
 extern "C" int vgl_pack_set_error(int code, const char* msg);      // (vgl_pack.hip reports through vgl_last_error() too; not exported)
+extern "C" int vgl_disc_tally_impl(int32_t device, int32_t n_samples, int32_t n_sites, int32_t max_genotypes, int32_t layout, const int32_t* site_status,
+                                   const int32_t* n_alleles, const int8_t* alleles2acgt, const int32_t* fmt_dp, const uint8_t* pl_u8, const int32_t* pl,
+                                   const uint8_t* gt, int64_t* table, const uint32_t* errflag, void* hip_stream);      // vgl_disc.hip (not exported)
 
 // PROGRAM_WILL_ADD_UNOBSERVED (shared.h:151-152): <*> / <NON_REF> appended => 5 alleles
 extern "C" int32_t vgl_max_alleles(const vgl_params* p) {
@@ -247,6 +250,11 @@ struct vgl_ctx {
     // VGL_DEEP_TILE_SITES sites.  VGL_RNG_TILE only (a value depends on (seed, site, sample) alone, so the second run is the same tile)
     vgl_ctx* deep = nullptr;
     int32_t deep_runs = 0;
+    // vgl_ctx_discordance: every tile is tallied behind its likelihood kernel (vgl_disc.hip).  The table is shared with the sibling
+    // context `deep` (disc_shared there: not its to free); d_disc_dp / d_disc_pl hold FORMAT/DP and the one-byte PL of a tile whose
+    // caller asks for neither (one set: the tally runs on the tile's own stream, ahead of the next tile's kernels)
+    bool disc = false, disc_shared = false;
+    int64_t* d_disc_table = nullptr; int32_t* d_disc_dp = nullptr; uint8_t* d_disc_pl = nullptr;
     hipStream_t s_compute = nullptr, s_copy = nullptr;
     int next_slot = 0;
     // timing
@@ -365,6 +373,9 @@ extern "C" int vgl_ctx_destroy(vgl_ctx* c) {
                     c->d_depth_tab, c->d_site_base, c->d_site_hash, c->d_dp_pre, c->d_hts_off, c->d_hts_base, c->d_roff, c->d_rtotal, c->d_errp_lin, c->d_cw, c->d_ccons, c->d_cexit,
                     c->d_ccnt, c->d_centry, c->d_cbase, c->d_cpos, c->d_csnap, c->d_csnapw, c->d_cctl};
     for (void* q : ptrs) if (q) (void)hipFree(q);
+    if (c->d_disc_dp) (void)hipFree(c->d_disc_dp);
+    if (c->d_disc_pl) (void)hipFree(c->d_disc_pl);
+    if (c->d_disc_table && !c->disc_shared) (void)hipFree(c->d_disc_table);
     for (auto& S : c->slot) {
         if (S.busy && S.ev_copied) (void)hipEventSynchronize(S.ev_copied);
         for (void* q : S.d_out) if (q) (void)hipFree(q);
@@ -954,6 +965,16 @@ extern "C" int vgl_simulate_tile_device(vgl_ctx* c, int64_t site0, int32_t n_sit
     const bool errp_always = (c->p.precise_gl || (D.serial && !D.beta_chain)) && D.error_qs == 2;    // as sized by vgl_ctx_create
     T.errp = (errp_always || dump_errp) ? c->d_errp : nullptr;
     T.site_pick_err = (D.error_qs == 1) ? o->site_pick_err : nullptr;
+    if (c->disc) {                                                // the tally reads FORMAT/DP and PL: kept on the device when the caller asks for neither
+        if (!T.fmt_dp) {
+            if (!c->d_disc_dp && dmalloc(&c->d_disc_dp, (size_t)c->max_sites * D.n_samples)) return fail(VGL_E_NOMEM, "out of device memory (discordance: FORMAT/DP)");
+            T.fmt_dp = c->d_disc_dp;
+        }
+        if (!T.pl && !T.pl_u8) {
+            if (!c->d_disc_pl && dmalloc(&c->d_disc_pl, (size_t)c->max_sites * D.G * D.n_samples)) return fail(VGL_E_NOMEM, "out of device memory (discordance: PL)");
+            T.pl_u8 = c->d_disc_pl;
+        }
+    }
 
     // the timing events belong to this call until the last one is recorded: any early return below destroys them (a failed call
     // leaks nothing), the successful end hands them to the context
@@ -1005,6 +1026,8 @@ extern "C" int vgl_simulate_tile_device(vgl_ctx* c, int64_t site0, int32_t n_sit
         if ((size_t)o->read_capacity > rows)
             HIPCHK(hipMemsetAsync(o->read_errp + rows * row, 0xFF, ((size_t)o->read_capacity - rows) * row * sizeof(double), st));
     }
+    if (c->disc && vgl_disc_tally_impl(c->device, D.n_samples, n_sites, D.G, D.out_layout, T.site_status, T.n_alleles, T.alleles2acgt, T.fmt_dp,
+                                       T.pl_u8, T.pl_u8 ? nullptr : T.pl, gt, c->d_disc_table, c->d_errflag, st)) return VGL_E_NODEVICE;
     if (c->timing) HIPCHK(hipEventRecord(e[VGL_NEV - 1], st));
     if (c->timing) for (int k = 0; k < VGL_NEV; k++) c->ev.push_back(e[k]);
     evg.armed = false;
@@ -1053,6 +1076,38 @@ extern "C" __attribute__((visibility("default"))) int vgl_dbg_redo_count(vgl_ctx
     return VGL_OK;
 }
 #endif
+
+// ---- discordance tally of a context's tiles (vgl_disc.hip) ------------------------------------------------------------------------
+extern "C" int vgl_ctx_discordance(vgl_ctx* c, int32_t on) {
+    if (!c) return fail(VGL_E_ARG, "vgl_ctx_discordance: null context");
+    for (const auto& S : c->slot) if (S.busy) return fail(VGL_E_ARG, "vgl_ctx_discordance: a tile of the context is in flight");
+    if (on && !c->d_disc_table) {
+        HIPCHK(hipSetDevice(c->device));
+        AcctScope acct(c);
+        const size_t n = (size_t)vgl_disc_table_len(c->dp.n_samples);
+        if (dmalloc(&c->d_disc_table, n)) return fail(VGL_E_NOMEM, "out of device memory (discordance table)");
+        HIPCHK(hipMemset(c->d_disc_table, 0, n * sizeof(int64_t)));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    c->disc = on != 0;
+    return VGL_OK;
+}
+
+extern "C" int vgl_ctx_discordance_read(vgl_ctx* c, int64_t* host_table, int32_t reset) {
+    if (!c || !host_table) return fail(VGL_E_ARG, "vgl_ctx_discordance_read: null argument");
+    if (!c->d_disc_table) return fail(VGL_E_ARG, "vgl_ctx_discordance_read: the context has no table (vgl_ctx_discordance was never switched on)");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    const size_t bytes = (size_t)vgl_disc_table_len(c->dp.n_samples) * sizeof(int64_t);
+    HIPCHK(hipMemcpy(host_table, c->d_disc_table, bytes, hipMemcpyDeviceToHost));
+    if (reset) { HIPCHK(hipMemset(c->d_disc_table, 0, bytes)); HIPCHK(hipDeviceSynchronize()); }
+    return VGL_OK;
+}
+
+// the sibling context of a deep tile counts into its parent's table
+static void deep_share_disc(vgl_ctx* c) {
+    c->deep->disc = c->disc; c->deep->disc_shared = true; c->deep->d_disc_table = c->d_disc_table;
+}
 
 extern "C" int vgl_ctx_check(vgl_ctx* c, void* stream) {
     if (!c) return fail(VGL_E_ARG, "null ctx");
@@ -1577,6 +1632,7 @@ static int deep_ctx(vgl_ctx* c, vgl_ctx::HostSlot& S) {
 }
 static int deep_rerun(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     if (deep_ctx(c, S) != VGL_OK) return VGL_E_CAPACITY;
+    deep_share_disc(c);
     const size_t N = (size_t)c->dp.n_samples;
     for (int32_t k = 0; k < S.n_sites; k += c->deep->max_sites) {
         const int32_t n = (S.n_sites - k < c->deep->max_sites) ? (S.n_sites - k) : c->deep->max_sites;
@@ -1596,6 +1652,7 @@ static int deep_rerun(vgl_ctx* c, vgl_ctx::HostSlot& S) {
 // the whole tile is formatted again and its per-site arrays and offsets copied again (compute stream, synchronously: a rare path).
 static int deep_rerun_text(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     if (deep_ctx(c, S) != VGL_OK) return VGL_E_CAPACITY;
+    deep_share_disc(c);
     const size_t N = (size_t)c->dp.n_samples;
     for (int32_t k = 0; k < S.n_sites; k += c->deep->max_sites) {
         const int32_t n = (S.n_sites - k < c->deep->max_sites) ? (S.n_sites - k) : c->deep->max_sites;

@@ -97,6 +97,18 @@ class Simulator:
         self._check(self.lib.vgl_ctx_info(self.ctx, C.byref(ci)))
         return {f: getattr(ci, f) for f, _ in _abi.CtxInfo._fields_}
 
+    def discordance(self, on=1):
+        """vgl_ctx_discordance: every following tile of this context is tallied on the device against its true genotypes
+        (vcfgl_amd.discordance), whatever outputs the caller asks for"""
+        self._check(self.lib.vgl_ctx_discordance(self.ctx, 1 if on else 0))
+
+    def discordance_table(self, reset=False):
+        """the context's table on the host (numpy int64; vcfgl_amd.discordance.split_table / format_table read it)"""
+        from .discordance import table_len
+        t = np.zeros(table_len(self.n_samples), dtype=np.int64)
+        self._check(self.lib.vgl_ctx_discordance_read(self.ctx, t.ctypes.data, 1 if reset else 0))
+        return t
+
     def close(self):
         if getattr(self, "ctx", None):
             self.lib.vgl_ctx_destroy(self.ctx)
