@@ -703,6 +703,51 @@ VGL_API int vgl_disc_tally_device(int32_t device, int32_t n_samples, int32_t n_s
 VGL_API int vgl_ctx_discordance(vgl_ctx* ctx, int32_t on);
 VGL_API int vgl_ctx_discordance_read(vgl_ctx* ctx, int64_t* host_table, int32_t reset);
 
+/* ---- the sample columns of VCF text parsed on the device (ABI 7, additive: the version stays 7) ------------------------------------
+ * The host program's own record parser is the specification.  A line is the bytes up to its '\n'; its sample region is what follows
+ * the ninth tab; sample column s lies between the tabs of that region.  The token of a column is its gti-th ':'-separated subfield
+ * (gti = the index of GT in the line's FORMAT); a column with fewer subfields has no token and both alleles are missing.
+ *   plain line    every token is absent or A or A S A: A = '.' or one or two decimal digits, S = the first '|' or '/'; a token
+ *                 without S gives a1 = a0.  The line gets status VGL_VCFIN_OK, gt_out[line][s] = (b1 << 4) | b0 with
+ *                 b = allele_map[line][a] & 0xF (0xF for a missing allele: allele_map holds what the caller maps allele a to,
+ *                 -1 for none), and allelesum_out[line] = the sum of the non-missing allele indices.
+ *   any other     an empty allele, a byte outside that grammar ('\r' included), three or more alleles, more than two digits, an
+ *                 allele index >= n_alleles[line], a number of sample columns that is not n_samples, or a line whose gti is
+ *                 negative or whose n_alleles is outside 1 .. 5 (allele_map has five entries): status VGL_VCFIN_HOST,
+ *                 the line's row and sum are unspecified and the caller parses the line itself.
+ * The kernel reads no byte outside [line_begin, line_end) and writes no byte outside the line's row, whatever the text holds.
+ *   vgl_vcfin_workspace_bytes  bytes of device workspace vgl_vcfin_parse_device needs (-1 for bad arguments).  Pure host arithmetic.
+ *   vgl_vcfin_parse_device     every pointer is device memory of `device`.  line_begin[i] is the offset in `text` of line i's first
+ *                              sample column, line_end[i] that of its '\n' (text_bytes for a last line without one); gti and
+ *                              n_alleles are int32 per line, allele_map int8 [n_lines][5].  The line ranges are compared with
+ *                              text_bytes by a small kernel whose one word the call waits for: a range outside the text
+ *                              (line_begin < 0, line_begin > line_end, line_end > text_bytes) returns VGL_E_ARG before the parser
+ *                              is launched.  The parse itself is enqueued on `hip_stream` and not waited for.
+ *   vgl_vcfin_host_create      for a program without HIP of its own: batches of lines from host memory, parsed on `device`, with
+ *                              page-locked staging and device buffers owned by the handle for two batches of at most max_lines
+ *                              lines and max_text_bytes bytes of text each.
+ *   vgl_vcfin_host_submit      copies the text and the per-line arrays (host memory; offsets relative to `text`) into the handle's
+ *                              staging, enqueues copy, parse and copy back, and returns at once with a ticket: one batch is on the
+ *                              device while the caller prepares the next.  A third submit before a wait fails with VGL_E_ARG, and
+ *                              so does a line range outside the text (nothing is enqueued).
+ *   vgl_vcfin_host_wait        blocks until the ticket's results are in host memory: gt [n_lines][n_samples], allelesum [n_lines],
+ *                              status [n_lines], owned by the handle and valid until the second submit after this one.
+ * No HIP device: VGL_E_NODEVICE from vgl_vcfin_parse_device and vgl_vcfin_host_create. */
+#define VGL_VCFIN_OK    0
+#define VGL_VCFIN_HOST  1
+typedef struct vgl_vcfin_host vgl_vcfin_host;
+VGL_API int64_t vgl_vcfin_workspace_bytes(int32_t n_samples, int32_t n_lines);
+VGL_API int vgl_vcfin_parse_device(int32_t device, const uint8_t* text, int64_t text_bytes, int32_t n_lines, const int64_t* line_begin,
+                                   const int64_t* line_end, const int32_t* gti, const int32_t* n_alleles, const int8_t* allele_map,
+                                   int32_t n_samples, uint8_t* gt_out, int32_t* allelesum_out, int32_t* status_out, void* workspace,
+                                   void* hip_stream);
+VGL_API int vgl_vcfin_host_create(int32_t device, int32_t n_samples, int32_t max_lines, int64_t max_text_bytes, vgl_vcfin_host** out);
+VGL_API int vgl_vcfin_host_submit(vgl_vcfin_host* h, const uint8_t* text, int64_t text_bytes, int32_t n_lines, const int64_t* line_begin,
+                                  const int64_t* line_end, const int32_t* gti, const int32_t* n_alleles, const int8_t* allele_map,
+                                  int32_t* ticket);
+VGL_API int vgl_vcfin_host_wait(vgl_vcfin_host* h, int32_t ticket, const uint8_t** gt, const int32_t** allelesum, const int32_t** status);
+VGL_API int vgl_vcfin_host_destroy(vgl_vcfin_host* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,7 @@ struct Args {
     int gt_disc = 0;                   // --gt-discordance 1: calls tallied against the truth on the device, <prefix>.discordance.tsv
     int disc_gq = 0;                   // --discordance-gq 0|3|4|5|6: gtDiscordance's -doGQ layout of that file
     int records = 1;                   // --records 0: no record file; only the discordance table comes back
+    int device_input = 0;              // --device-input 1: the sample columns of the input VCF text parsed on the first device of the run
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -130,6 +131,11 @@ static const char USAGE[] =
     "                   --records 0|1 [1; 0: no record file is opened and no FORMAT array, text or encoded record crosses the link: only the\n"
     "                   discordance table comes back.  Needs --gt-discordance 1; refused with -printPileup 1, -printTruth 1, -doGVCF 1 and\n"
     "                   the per-read listings]\n"
+    "                   --device-input 0|1 [0: the genotype columns of the input VCF are parsed on the host; 1: on the first GPU of --device /\n"
+    "                   --devices: the host reads the file, finds the lines and parses their first nine columns, the text goes up in batches of\n"
+    "                   --tile-sites lines and one packed byte per sample comes back.  A line outside the plain grammar (GT alleles of '.' or\n"
+    "                   one or two digits, at most two of them) is parsed by the host as with 0.  Same output either way; VCF text input only\n"
+    "                   (BCF input is refused), refused with --depth inf; a run without a GPU fails instead of falling back]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 static Args parse_args(int argc, char** argv) {
@@ -215,6 +221,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--gt-discordance") a.gt_disc = I(v);
         else if (f == "--discordance-gq") a.disc_gq = I(v);
         else if (f == "--records") a.records = I(v);
+        else if (f == "--device-input") a.device_input = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -238,6 +245,8 @@ static Args parse_args(int argc, char** argv) {
             die("--records 0 is not supported with -printBasePickError / -printQsError / -printGlError / -printQScores 1 (per-read listings).");
         a.device_text = a.device_bcf = a.device_gvcf = a.device_stream = a.device_pileup = 0;      // nothing to format, encode or assemble
     }
+    range(a.device_input, 0, 1, "--device-input");
+    if (a.device_input == 1 && a.depth_inf) die("--device-input 1 is not supported with --depth inf (no device is used).");
     if (a.device_stream == 1 && a.depth_inf) die("--device-stream 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_gvcf == 1 && a.depth_inf) die("--device-gvcf 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_bcf == 1 && a.depth_inf) die("--device-bcf 1 is not supported with --depth inf (no tile is simulated).");
@@ -376,13 +385,21 @@ struct Rec {
     std::vector<int8_t> gt;            // 2 per sample, allele index or -1
     std::vector<std::string> gt_str;   // GT tokens as written in the input (for -printTruth)
     char ref_char;
+    const uint8_t* dev_row = nullptr;  // --device-input 1: the packed row the device parsed (Vcf::gt_rows), gt stays empty
+    int32_t dev_sum = 0;               //                   and its allele sum
+    int8_t in_status = -1;             // --dump-gt: VGL_VCFIN_OK / VGL_VCFIN_HOST of the line
 };
+
+// --device-input: how read_vcf is to parse the sample columns, and what it did (the [input] line of --verbose 1)
+struct InputOpt { int device_input = 0, source = 0, device = 0, tile_sites = 4096; bool classify = false; };
+struct InputStats { double t_read = 0, t_scan = 0, t_fixed = 0, t_dev = 0, t_host = 0; long lines_dev = 0, lines_host = 0; int64_t text_up = 0; };
 
 struct Vcf {
     std::vector<std::string> header;   // '##' lines
     std::vector<std::string> samples;
     std::map<std::string, long> contig_len;
     std::vector<Rec> recs;
+    std::vector<uint8_t> gt_rows;      // --device-input 1: one row of packed true genotypes per record line (Rec::dev_row points here)
 };
 
 static void split(const std::string& s, char c, std::vector<std::string>& out) {
@@ -521,24 +538,30 @@ static Vcf read_bcf(std::vector<uint8_t>&& raw, bool keep_gt_text) {
 }
 
 // keep_gt_text: the GT tokens as written are needed only by -printTruth
-// one record line [lb, le) -> Rec (thread safe: records are parsed in parallel)
-static void parse_record(const char* lb, const char* le, const size_t n_hdr, const bool keep_gt_text, Rec& r) {
+// The first nine columns of one record line [lb, le) -> Rec, the index of GT in FORMAT and the start of the sample columns.
+// strict: exits on a line without ten columns or without GT; otherwise such a line returns false (r is then to be discarded).
+static bool parse_fixed(const char* lb, const char* le, const bool strict, Rec& r, int& gti, const char*& samples) {
     const char* col_at[10]; int nc = 0; col_at[0] = lb;
     for (const char* q = lb; q < le && nc < 9; q++) if (*q == '\t') col_at[++nc] = q + 1;
-    if (nc < 9) die("VCF record with fewer than 10 columns (a FORMAT/GT column is required)");
+    if (nc < 9) { if (!strict) return false; die("VCF record with fewer than 10 columns (a FORMAT/GT column is required)"); }
     auto col = [&](int k) { return std::string(col_at[k], (size_t)(col_at[k + 1] - 1 - col_at[k])); };
     std::vector<std::string> g, fmt;
     r.chrom = col(0); r.pos0 = atol(col(1).c_str()) - 1; r.id = col(2); r.qual = col(5); r.filt = col(6); r.info = col(7);
     const std::string ref = col(3), alt = col(4);
     r.alleles.push_back(ref);
     if (alt != ".") { split(alt, ',', g); for (auto& x : g) r.alleles.push_back(x); }
-    if (ref.empty()) die("Empty REF at position %ld.", r.pos0 + 1);
+    if (ref.empty()) { if (!strict) return false; die("Empty REF at position %ld.", r.pos0 + 1); }
     r.ref_char = ref[0];
     split(col(8), ':', fmt);
-    int gti = -1; for (size_t i = 0; i < fmt.size(); i++) if (fmt[i] == "GT") gti = (int)i;
-    if (gti < 0) die("Could not find GT tag at position %ld.", r.pos0 + 1);
+    gti = -1; for (size_t i = 0; i < fmt.size(); i++) if (fmt[i] == "GT") gti = (int)i;
+    if (gti < 0) { if (!strict) return false; die("Could not find GT tag at position %ld.", r.pos0 + 1); }
+    samples = col_at[9];
+    return true;
+}
+
+// The sample columns [p, le) of a record line -> Rec::gt (and the tokens as written)
+static void parse_samples(const char* p, const char* le, const int gti, const size_t n_hdr, const bool keep_gt_text, Rec& r) {
     r.gt.assign(2 * n_hdr, -1);
-    const char* p = col_at[9];
     const char* const end = le;
     size_t s = 0;
     while (true) {                                       // p at the start of a sample column
@@ -563,9 +586,141 @@ static void parse_record(const char* lb, const char* le, const size_t n_hdr, con
     if (s != n_hdr) die("Record at position %ld has %zu sample columns, the header names %zu samples.", r.pos0 + 1, s, n_hdr);
 }
 
+// one record line [lb, le) -> Rec (thread safe: records are parsed in parallel)
+static void parse_record(const char* lb, const char* le, const size_t n_hdr, const bool keep_gt_text, Rec& r) {
+    int gti; const char* p;
+    parse_fixed(lb, le, true, r, gti, p);
+    parse_samples(p, le, gti, n_hdr, keep_gt_text, r);
+}
+
+// --dump-gt: the status the device parser gives the sample columns [p, le) (include/vcfgl_hip.h: the plain grammar), on the host
+static int classify_samples(const char* p, const char* le, const int gti, const int n_alleles, const size_t n_hdr) {
+    size_t s = 0; bool plain = true;
+    auto allele = [&](const char*& q, const char* te) {          // '.' or one or two digits below n_alleles
+        if (q == te) return false;
+        if (*q == '.') { q++; return true; }
+        if (*q < '0' || *q > '9') return false;
+        int v = *q++ - '0';
+        if (q < te && *q >= '0' && *q <= '9') v = v * 10 + (*q++ - '0');
+        return v < n_alleles;
+    };
+    while (true) {
+        const char* ce = (const char*)memchr(p, '\t', (size_t)(le - p)); if (!ce) ce = le;
+        const char* t = p;
+        for (int k = 0; k < gti && t; k++) { t = (const char*)memchr(t, ':', (size_t)(ce - t)); if (t) t++; }
+        if (t) {
+            const char* te = (const char*)memchr(t, ':', (size_t)(ce - t)); if (!te) te = ce;
+            const char* q = t;
+            if (!allele(q, te)) plain = false;
+            else if (q != te) { if (*q != '|' && *q != '/') plain = false; else { q++; if (!allele(q, te) || q != te) plain = false; } }
+        }
+        s++;
+        if (ce == le) break;
+        p = ce + 1;
+    }
+    return (plain && s == n_hdr) ? VGL_VCFIN_OK : VGL_VCFIN_HOST;
+}
+
+static int allele_to_int(const std::string& a);
+static double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
+
+// make_site's allele table ra[] for a record, without its exits: false where make_site would refuse the record
+static bool allele_table(const Rec& r, const int source, int8_t ra[5]) {
+    for (int i = 0; i < 5; i++) ra[i] = -1;
+    const int n = (int)r.alleles.size();
+    if (n > 5 || (source == 0 && n > 2)) return false;
+    for (int i = 0; i < n; i++) {
+        if (source == 1) { const int x = r.alleles[i].empty() ? -1 : allele_to_int(r.alleles[i]); if (x == -1) return false; ra[i] = (int8_t)x; }
+        else { const int x = (r.alleles[i].empty() ? 0 : r.alleles[i][0]) - '0'; if (x != 0 && x != 1) return false; ra[i] = (int8_t)x; }
+    }
+    return true;
+}
+
+// --device-input 1: the record lines' first nine columns on `threads` host threads, their sample columns on the device in batches of
+// at most tile_sites lines (vgl_vcfin_host_*: one batch is copied up and parsed while the next is put together), and the host's own
+// parser for every line the device hands back (VGL_VCFIN_HOST) or the fixed columns cannot describe -- its exits and messages are
+// therefore those of --device-input 0.
+static void parse_lines_device(const uint8_t* raw, const std::vector<std::pair<const char*, const char*>>& rec_lines, const size_t n_hdr,
+                               const bool keep_gt_text, const int threads, const InputOpt& opt, Vcf& v, InputStats& st) {
+    const int n = (int)rec_lines.size();
+    const int N = (int)n_hdr;
+    double t0 = now_s();
+    std::vector<int64_t> lb((size_t)n), le((size_t)n);
+    std::vector<int32_t> gti((size_t)n), nal((size_t)n);
+    std::vector<int8_t> amap((size_t)n * 5);
+    std::vector<uint8_t> sent((size_t)n, 0);
+    vsink::parallel_for(n, threads, [&](int i) {
+        Rec& r = v.recs[i];
+        int g = -1; const char* p = nullptr;
+        if (parse_fixed(rec_lines[i].first, rec_lines[i].second, false, r, g, p) && allele_table(r, opt.source, &amap[(size_t)i * 5])) {
+            lb[i] = p - (const char*)raw; le[i] = rec_lines[i].second - (const char*)raw; gti[i] = g; nal[i] = (int32_t)r.alleles.size();
+            sent[i] = 1;
+        } else { r = Rec(); parse_record(rec_lines[i].first, rec_lines[i].second, n_hdr, keep_gt_text, r); r.in_status = VGL_VCFIN_HOST; }
+    });
+    st.t_fixed = now_s() - t0; t0 = now_s();
+    const int TS = std::max(1, opt.tile_sites);
+    const int nb = (n + TS - 1) / TS;
+    // a batch: the sent lines among TS consecutive ones, and the text from the first one's sample columns to the last one's end
+    struct Batch { std::vector<int> idx; int64_t t0 = 0, t1 = 0; };
+    std::vector<Batch> batches((size_t)nb);
+    int64_t max_text = 1; int max_lines = 1;
+    for (int b = 0; b < nb; b++) {
+        Batch& B = batches[b];
+        for (int i = b * TS; i < std::min(n, (b + 1) * TS); i++) if (sent[i]) B.idx.push_back(i);
+        if (B.idx.empty()) continue;
+        B.t0 = lb[B.idx.front()]; B.t1 = le[B.idx.back()];
+        max_text = std::max(max_text, B.t1 - B.t0); max_lines = std::max(max_lines, (int)B.idx.size());
+    }
+    v.gt_rows.resize((size_t)n * (size_t)N);
+    std::vector<int> again;                                          // lines the device handed back
+    vgl_vcfin_host* h = nullptr;
+    if (vgl_vcfin_host_create(opt.device, N, max_lines, max_text, &h) != VGL_OK) die("--device-input 1: %s", vgl_last_error());
+    std::vector<int64_t> blb[2], ble[2]; std::vector<int32_t> bg[2], bn[2]; std::vector<int8_t> bm[2];
+    int32_t ticket[2] = {-1, -1};
+    auto submit = [&](int b) {
+        const Batch& B = batches[b]; const int k = b & 1; const size_t m = B.idx.size();
+        blb[k].resize(m); ble[k].resize(m); bg[k].resize(m); bn[k].resize(m); bm[k].resize(m * 5);
+        for (size_t j = 0; j < m; j++) {
+            const int i = B.idx[j];
+            blb[k][j] = lb[i] - B.t0; ble[k][j] = le[i] - B.t0; bg[k][j] = gti[i]; bn[k][j] = nal[i]; memcpy(&bm[k][j * 5], &amap[(size_t)i * 5], 5);
+        }
+        if (vgl_vcfin_host_submit(h, raw + B.t0, B.t1 - B.t0, (int32_t)m, blb[k].data(), ble[k].data(), bg[k].data(), bn[k].data(), bm[k].data(), &ticket[k]) != VGL_OK)
+            die("--device-input 1: %s", vgl_last_error());
+        st.text_up += m ? B.t1 - B.t0 : 0; st.lines_dev += (long)m;
+    };
+    auto retire = [&](int b) {
+        const Batch& B = batches[b];
+        const uint8_t* rows; const int32_t* sums; const int32_t* status;
+        if (vgl_vcfin_host_wait(h, ticket[b & 1], &rows, &sums, &status) != VGL_OK) die("--device-input 1: %s", vgl_last_error());
+        for (size_t j = 0; j < B.idx.size(); j++) {
+            const int i = B.idx[j];
+            if (status[j] != VGL_VCFIN_OK) { again.push_back(i); continue; }
+            uint8_t* dst = &v.gt_rows[(size_t)i * (size_t)N];
+            memcpy(dst, rows + j * (size_t)N, (size_t)N);
+            v.recs[i].dev_row = dst; v.recs[i].dev_sum = sums[j]; v.recs[i].in_status = VGL_VCFIN_OK;
+        }
+    };
+    for (int b = 0; b < nb; b++) { submit(b); if (b > 0) retire(b - 1); }
+    if (nb > 0) retire(nb - 1);
+    vgl_vcfin_host_destroy(h);
+    st.t_dev = now_s() - t0; t0 = now_s();
+    st.lines_host = (long)again.size();
+    vsink::parallel_for((int)again.size(), threads, [&](int k) {
+        const int i = again[k]; Rec& r = v.recs[i];
+        r = Rec(); parse_record(rec_lines[i].first, rec_lines[i].second, n_hdr, keep_gt_text, r); r.in_status = VGL_VCFIN_HOST;
+    });
+    // -printTruth 1 writes the GT tokens as they stand in the input: collected on the host, as with --device-input 0
+    if (keep_gt_text) vsink::parallel_for(n, threads, [&](int i) {
+        Rec& r = v.recs[i];
+        if (r.dev_row) { parse_samples((const char*)raw + lb[i], rec_lines[i].second, gti[i], n_hdr, true, r); r.gt.clear(); r.gt.shrink_to_fit(); }
+    });
+    st.t_host = now_s() - t0;
+}
+
 // keep_gt_text: the GT tokens as written are needed only by -printTruth.  The (decompressed) file is read whole,
 // the header lines are taken in order and the record lines are parsed on `threads` threads.
-static Vcf read_vcf(const std::string& fn, bool keep_gt_text, int threads) {
+static Vcf read_vcf(const std::string& fn, bool keep_gt_text, int threads, const InputOpt& opt = InputOpt(), InputStats* stats = nullptr) {
+    InputStats st; double t0 = now_s();
     gzFile fp = gzopen(fn.c_str(), "r");               // plain text, gzip / BGZF, or BCF inside either
     if (!fp) die("Could not open file: %s", fn.c_str());
     gzbuffer(fp, 1 << 20);
@@ -573,7 +728,11 @@ static Vcf read_vcf(const std::string& fn, bool keep_gt_text, int threads) {
     int k;
     while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) raw.insert(raw.end(), chunk.begin(), chunk.begin() + k);
     gzclose(fp);
-    if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) return read_bcf(std::move(raw), keep_gt_text);
+    if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) {
+        if (opt.device_input) die("--device-input 1 is not supported with BCF input (its genotypes are binary already: there is no text to parse).");
+        return read_bcf(std::move(raw), keep_gt_text);
+    }
+    st.t_read = now_s() - t0; t0 = now_s();
     Vcf v;
     std::vector<std::string> f;
     std::vector<std::pair<const char*, const char*>> rec_lines;
@@ -597,9 +756,22 @@ static Vcf read_vcf(const std::string& fn, bool keep_gt_text, int threads) {
         }
         p = nl ? nl + 1 : end;
     }
+    st.t_scan = now_s() - t0; t0 = now_s();
     v.recs.resize(rec_lines.size());
     const size_t n_hdr = v.samples.size();
-    vsink::parallel_for((int)rec_lines.size(), threads, [&](int i) { parse_record(rec_lines[i].first, rec_lines[i].second, n_hdr, keep_gt_text, v.recs[i]); });
+    if (opt.device_input && n_hdr > 0) parse_lines_device(raw.data(), rec_lines, n_hdr, keep_gt_text, threads, opt, v, st);
+    else {
+        vsink::parallel_for((int)rec_lines.size(), threads, [&](int i) {
+            Rec& r = v.recs[i];
+            if (!opt.classify) { parse_record(rec_lines[i].first, rec_lines[i].second, n_hdr, keep_gt_text, r); return; }
+            int gti; const char* sp;
+            parse_fixed(rec_lines[i].first, rec_lines[i].second, true, r, gti, sp);
+            parse_samples(sp, rec_lines[i].second, gti, n_hdr, keep_gt_text, r);
+            r.in_status = (int8_t)classify_samples(sp, rec_lines[i].second, gti, (int)r.alleles.size(), n_hdr);
+        });
+        st.t_host = now_s() - t0; st.lines_host = (long)rec_lines.size();
+    }
+    if (stats) *stats = st;
     return v;
 }
 
@@ -659,7 +831,8 @@ static bool make_site(const Args& a, const Rec& rec, long pos0, bool blank, int 
     }
     if (a.source == 0 && n_alleles > 2) die("Multiallelic sites are not supported when using binary GT source.");
     long allelesum = 0;
-    for (int s = 0; s < N; s++) {
+    if (rec.dev_row && !blank) { memcpy(gt_row, rec.dev_row, (size_t)N); allelesum = rec.dev_sum; }      // --device-input 1: parsed, mapped through ra[] and summed on the device
+    else for (int s = 0; s < N; s++) {
         int g0 = blank ? 0 : rec.gt[2 * s], g1 = blank ? 0 : rec.gt[2 * s + 1];
         int b0 = 0xF, b1 = 0xF;
         if (g0 >= 0) { if (g0 >= n_alleles) die("GT allele index out of range at position %ld", pos0 + 1); allelesum += g0; b0 = ra[g0] & 0xF; }
@@ -953,7 +1126,34 @@ int main(int argc, char** argv) {
         out.close();
         return 0;
     }
+    if (argc == 5 && !strcmp(argv[1], "--dump-gt")) {
+        // test hook of the input parser: --dump-gt <file> <source 0|1> <device-input 0|1> prints per record line "pos status allelesum row":
+        // the row make_site hands to the tile calls in hex, the status of the line (VGL_VCFIN_*: 1 = outside the device parser's plain
+        // grammar), through the host parser (0, no GPU needed) or the device parser (1)
+        Args a; a.source = atoi(argv[3]);
+        InputOpt opt; opt.device_input = atoi(argv[4]); opt.source = a.source; opt.classify = true; opt.tile_sites = 256;
+        if (a.source < 0 || a.source > 1 || opt.device_input < 0 || opt.device_input > 1) die("--dump-gt <file> <source 0|1> <device-input 0|1>");
+        Vcf vcf = read_vcf(argv[2], false, 4, opt);
+        const int N = (int)vcf.samples.size();
+        if (N <= 0) die("no samples in %s", argv[2]);
+        std::vector<uint8_t> row((size_t)N); SiteMeta m; std::string line;
+        for (const Rec& r : vcf.recs) {
+            make_site(a, r, r.pos0, false, N, row.data(), m, nullptr);
+            long sum = 0;
+            if (r.dev_row) sum = r.dev_sum; else for (int8_t g : r.gt) if (g > 0) sum += g;
+            char hb[64]; snprintf(hb, sizeof hb, "%ld %d %ld ", r.pos0 + 1, (int)r.in_status, sum); line = hb;
+            for (int s = 0; s < N; s++) { snprintf(hb, sizeof hb, "%02x", row[s]); line += hb; }
+            puts(line.c_str());
+        }
+        return 0;
+    }
     Args a = parse_args(argc, argv);
+    if (a.device_input) {                                       // (checked before any file of the run exists, the .arg file included)
+        gzFile fp = gzopen(a.in_fn.c_str(), "r"); char magic[3] = {0, 0, 0};
+        if (!fp) die("Could not open file: %s", a.in_fn.c_str());
+        const int k = gzread(fp, magic, 3); gzclose(fp);
+        if (k == 3 && !memcmp(magic, "BCF", 3)) die("--device-input 1 is not supported with BCF input (its genotypes are binary already: there is no text to parse).");
+    }
     RunLog runlog; runlog.open(a);
     // --verbose 1: wall-clock seconds per stage on stderr at the end
     double t_stage[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};          // read, sites, context, waiting for the device, encode, write, tile buffers (page-locked), teardown, pileup
@@ -971,7 +1171,9 @@ int main(int argc, char** argv) {
     const int warm_dev = a.devices.empty() ? a.device : a.devices[0];
     const int bgzf_dev = a.device_bgzf ? warm_dev : -1;         // --device-bgzf 1: the run's first device compresses every BGZF stream
     if (!a.depth_inf) hip_warm = std::thread([warm_dev] { vgl_host_free(vgl_host_alloc_on(warm_dev, 4096)); });
-    Vcf vcf = read_vcf(a.in_fn, a.print_truth != 0, enc_threads);
+    InputOpt in_opt; in_opt.device_input = a.device_input; in_opt.source = a.source; in_opt.device = warm_dev; in_opt.tile_sites = a.tile_sites > 0 ? a.tile_sites : 4096;
+    InputStats in_stats;
+    Vcf vcf = read_vcf(a.in_fn, a.print_truth != 0, enc_threads, in_opt, &in_stats);
     if (hip_warm.joinable()) hip_warm.join();
     lap(0);
     const int N = (int)vcf.samples.size();
@@ -1634,6 +1836,10 @@ int main(int argc, char** argv) {
     }
     if (a.verbose) fprintf(stderr, "\n[timing] read input %.3f s, decode sites %.3f s, device context(s) %.3f s, waiting for the device(s) (simulation incl. PCIe, overlapped with the writer) %.3f s, encode %.3f s, write/compress %.3f s, tile buffers %.3f s, teardown %.3f s, pileup %.3f s\n",
                            t_stage[0], t_stage[1], t_stage[2], t_stage[3], t_stage[4], t_stage[5], t_stage[6], t_stage[7], t_stage[8]);
+    // the parts of "read input" (the HIP runtime's start-up, which the reading overlaps with, is what remains of it)
+    if (a.verbose) fprintf(stderr, "[input] --device-input %d: %ld lines parsed on the device, %ld of them again on the host, %.3f GB of text sent up; file read %.3f s, line scan %.3f s, fixed columns %.3f s, device parse and wait %.3f s, host %s %.3f s\n",
+                           a.device_input, in_stats.lines_dev, a.device_input ? in_stats.lines_host : 0L, in_stats.text_up / 1e9, in_stats.t_read, in_stats.t_scan, in_stats.t_fixed,
+                           in_stats.t_dev, a.device_input ? "re-parse" : "parse", in_stats.t_host);
     char sb[512];
     snprintf(sb, sizeof sb, "\n\n-> Simulation finished successfully.\n\nSummary:\n\tNumber of samples: %d\n\tTotal number of sites simulated: %zu\n"
                             "\tNumber of sites included in simulation output file: %ld\n\tNumber of sites skipped: %ld\n", N, n_sites_total, n_out, n_skipped);
