@@ -748,6 +748,57 @@ VGL_API int vgl_vcfin_host_submit(vgl_vcfin_host* h, const uint8_t* text, int64_
 VGL_API int vgl_vcfin_host_wait(vgl_vcfin_host* h, int32_t ticket, const uint8_t** gt, const int32_t** allelesum, const int32_t** status);
 VGL_API int vgl_vcfin_host_destroy(vgl_vcfin_host* h);
 
+/* ---- BGZF input inflated on the device (ABI 7, additive: the version stays 7) -------------------------------------------------------
+ * The counterpart of vgl_bgzf_compress_device: a BGZF stream (SAMv1 4.1: independent gzip members of at most 64 KiB, each with its
+ * size in a 'BC' extra subfield) is inflated one member per workgroup, RFC 1951 complete (stored, fixed and dynamic blocks, any
+ * number of them per member).  zlib's inflate is the specification: a member gets
+ *   VGL_INFLATE_OK    its output has exactly ISIZE bytes, their CRC32 is the trailer's, and the deflate data ends where the trailer
+ *                     begins;
+ *   VGL_INFLATE_HOST  anything else (a header that is not a BGZF member's, BTYPE 11, LEN / NLEN mismatch, an oversubscribed or
+ *                     incomplete code -- other than the two incomplete codes zlib accepts: no distance code, or one code of one bit
+ *                     --, literal/length symbol 286 / 287, distance symbol 30 / 31, a distance beyond the bytes produced, output
+ *                     past ISIZE or short of it, input running out or left over, a trailer ISIZE that is not isize[m], CRC mismatch):
+ *                     the member's output bytes are unspecified and the caller inflates it (or the file) itself.
+ * Whatever the bytes hold, the kernel reads no byte outside [begin, begin + csize) and writes no byte outside
+ * [out_off, out_off + isize) of a member.
+ *   vgl_bgzf_index              pure host arithmetic, no GPU: walks the members of raw [n] by their gzip headers (magic 1f 8b 08, FLG 4,
+ *                               the 'BC' subfield of length 2 anywhere among the extra subfields of XLEN bytes; BSIZE from it, ISIZE
+ *                               from the trailer, ISIZE <= 65536) and writes begin / csize / isize of at most max_members members and
+ *                               their number (the 28-byte EOF member counts like any other, ISIZE 0).  The arrays may be NULL with
+ *                               max_members = 0 to count.  VGL_E_UNSUPPORTED for anything that is not a clean series of such members
+ *                               up to byte n (plain gzip, plain text, an empty buffer, a truncated last member, trailing bytes);
+ *                               VGL_E_CAPACITY (and *n_members = the count) when there are more than max_members.
+ *   vgl_inflate_workspace_bytes device workspace of a call on n_members members (-1 for n_members < 0).  Pure host arithmetic.
+ *   vgl_inflate_members_device  every pointer is device memory of `device`: src [src_bytes], begin (int64), csize, isize (int32) and
+ *                               out_off (int64) per member, dst [dst_cap], status (int32 per member).  A small kernel compares the
+ *                               ranges with the buffers and the call waits for its one word: begin < 0, csize < 0, begin + csize >
+ *                               src_bytes, isize < 0 or > 65536, out_off < 0 or out_off + isize > dst_cap return VGL_E_ARG before the
+ *                               decoder is launched (which clamps all the same).  The decode itself is enqueued on `hip_stream` and
+ *                               not waited for.  Output ranges of different members must not overlap.
+ *   vgl_inflate_host_create     for a program without HIP of its own: batches of at most max_members members from host memory,
+ *                               inflated on `device`, with page-locked staging and device buffers for two batches on one stream.
+ *   vgl_inflate_host_submit     src [src_bytes] holds the batch's members at begin[m] (offsets relative to src), csize[m] bytes each,
+ *                               isize[m] bytes of output each; outputs lie back to back in member order.  Enqueues copy, decode and
+ *                               copy back and returns at once with a ticket; a submit of batch b is allowed before the wait for
+ *                               b - 1.  A third submit before a wait fails with VGL_E_ARG, and so does a range outside src or an
+ *                               isize > 65536 (nothing is enqueued).
+ *   vgl_inflate_host_wait       blocks until the ticket's bytes are in host memory: out [*out_bytes = the sum of isize], status
+ *                               [n_members], owned by the handle and valid until the second submit after this one.
+ * No HIP device: VGL_E_NODEVICE from vgl_inflate_members_device and vgl_inflate_host_create. */
+#define VGL_INFLATE_OK    0
+#define VGL_INFLATE_HOST  1
+typedef struct vgl_inflate_host vgl_inflate_host;
+VGL_API int vgl_bgzf_index(const uint8_t* raw, int64_t n, int64_t max_members, int64_t* begin, int32_t* csize, int32_t* isize, int64_t* n_members);
+VGL_API int64_t vgl_inflate_workspace_bytes(int64_t n_members);
+VGL_API int vgl_inflate_members_device(int32_t device, const uint8_t* src, int64_t src_bytes, int64_t n_members, const int64_t* begin,
+                                       const int32_t* csize, const int64_t* out_off, const int32_t* isize, uint8_t* dst, int64_t dst_cap,
+                                       int32_t* status, void* workspace, int64_t workspace_bytes, void* hip_stream);
+VGL_API int vgl_inflate_host_create(int32_t device, int32_t max_members, vgl_inflate_host** out);
+VGL_API int vgl_inflate_host_submit(vgl_inflate_host* h, const uint8_t* src, int64_t src_bytes, int32_t n_members, const int64_t* begin,
+                                    const int32_t* csize, const int32_t* isize, int32_t* ticket);
+VGL_API int vgl_inflate_host_wait(vgl_inflate_host* h, int32_t ticket, const uint8_t** out, int64_t* out_bytes, const int32_t** status);
+VGL_API int vgl_inflate_host_destroy(vgl_inflate_host* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,9 +101,13 @@ EXPORTS = [
     "vgl_disc_table_len", "vgl_disc_tally_device", "vgl_ctx_discordance", "vgl_ctx_discordance_read",
     "vgl_vcfin_workspace_bytes", "vgl_vcfin_parse_device",
     "vgl_vcfin_host_create", "vgl_vcfin_host_submit", "vgl_vcfin_host_wait", "vgl_vcfin_host_destroy",
+    "vgl_bgzf_index", "vgl_inflate_workspace_bytes", "vgl_inflate_members_device",
+    "vgl_inflate_host_create", "vgl_inflate_host_submit", "vgl_inflate_host_wait", "vgl_inflate_host_destroy",
 ]
 # status of a line from the device parser (VGL_VCFIN_*): parsed, or left to the caller's own parser
 VCFIN_OK, VCFIN_HOST = 0, 1
+# status of a BGZF member from the device inflater (VGL_INFLATE_*): inflated to its exact end, or left to the caller's own inflater
+INFLATE_OK, INFLATE_HOST = 0, 1
 # cells of the discordance table (VGL_DISC_*): cell[sample][6][128] by GQ, callmis[sample], sites[2]
 DISC_CELLS, DISC_GQ = 6, 128
 DISC_HOM_HOM_CONC, DISC_HOM_HOM_DISC, DISC_HET_HET_CONC, DISC_HET_HET_DISC, DISC_HOM_HET, DISC_HET_HOM = range(6)
@@ -282,6 +286,15 @@ def load_library(hooks=False):
                                           C.c_void_p, C.POINTER(C.c_int32)]
     lib.vgl_vcfin_host_wait.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.vgl_vcfin_host_destroy.argtypes = [C.c_void_p]
+    lib.vgl_bgzf_index.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.vgl_inflate_workspace_bytes.restype = C.c_int64
+    lib.vgl_inflate_workspace_bytes.argtypes = [C.c_int64]
+    lib.vgl_inflate_members_device.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vgl_inflate_host_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.vgl_inflate_host_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    lib.vgl_inflate_host_wait.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]
+    lib.vgl_inflate_host_destroy.argtypes = [C.c_void_p]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

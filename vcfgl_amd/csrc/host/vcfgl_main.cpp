@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -68,6 +69,7 @@ struct Args {
     int gt_disc = 0;                   // --gt-discordance 1: calls tallied against the truth on the device, <prefix>.discordance.tsv
     int disc_gq = 0;                   // --discordance-gq 0|3|4|5|6: gtDiscordance's -doGQ layout of that file
     int records = 1;                   // --records 0: no record file; only the discordance table comes back
+    int device_inflate = 0;            // --device-inflate 1: a BGZF input is inflated on the first device of the run
     int device_input = 0;              // --device-input 1: the sample columns of the input VCF text parsed on the first device of the run
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
@@ -136,6 +138,11 @@ static const char USAGE[] =
     "                   --tile-sites lines and one packed byte per sample comes back.  A line outside the plain grammar (GT alleles of '.' or\n"
     "                   one or two digits, at most two of them) is parsed by the host as with 0.  Same output either way; VCF text input only\n"
     "                   (BCF input is refused), refused with --depth inf; a run without a GPU fails instead of falling back]\n"
+    "                   --device-inflate 0|1 [0: the input is read and inflated by zlib on one host thread; 1: a BGZF input (bgzip'd VCF text, compressed\n"
+    "                   BCF) is read as it lies in the file and its members are inflated on the first GPU of --device / --devices, 512 members\n"
+    "                   a batch.  A file that is not BGZF (plain text, gzip) and a file with a member the device does not take to its exact end\n"
+    "                   are read by zlib as with 0: same bytes either way.  Refused with --depth inf; a run without a GPU fails instead of\n"
+    "                   falling back]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 static Args parse_args(int argc, char** argv) {
@@ -222,6 +229,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--discordance-gq") a.disc_gq = I(v);
         else if (f == "--records") a.records = I(v);
         else if (f == "--device-input") a.device_input = I(v);
+        else if (f == "--device-inflate") a.device_inflate = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -247,6 +255,8 @@ static Args parse_args(int argc, char** argv) {
     }
     range(a.device_input, 0, 1, "--device-input");
     if (a.device_input == 1 && a.depth_inf) die("--device-input 1 is not supported with --depth inf (no device is used).");
+    range(a.device_inflate, 0, 1, "--device-inflate");
+    if (a.device_inflate == 1 && a.depth_inf) die("--device-inflate 1 is not supported with --depth inf (no device is used).");
     if (a.device_stream == 1 && a.depth_inf) die("--device-stream 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_gvcf == 1 && a.depth_inf) die("--device-gvcf 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_bcf == 1 && a.depth_inf) die("--device-bcf 1 is not supported with --depth inf (no tile is simulated).");
@@ -391,8 +401,16 @@ struct Rec {
 };
 
 // --device-input: how read_vcf is to parse the sample columns, and what it did (the [input] line of --verbose 1)
-struct InputOpt { int device_input = 0, source = 0, device = 0, tile_sites = 4096; bool classify = false; };
-struct InputStats { double t_read = 0, t_scan = 0, t_fixed = 0, t_dev = 0, t_host = 0; long lines_dev = 0, lines_host = 0; int64_t text_up = 0; };
+struct InputOpt {
+    int device_input = 0, source = 0, device = 0, tile_sites = 4096; bool classify = false;
+    int device_inflate = 0;                                  // --device-inflate 1: a BGZF file's members are inflated on `device`
+    std::function<vgl_inflate_host*()> inflater;            // the host object, created beside the file read (waits for its creation; dies without a device)
+};
+struct InputStats {
+    double t_read = 0, t_scan = 0, t_fixed = 0, t_dev = 0, t_host = 0; long lines_dev = 0, lines_host = 0; int64_t text_up = 0;
+    // --device-inflate 1: members inflated on the device, compressed bytes sent up, inflated bytes received, why zlib read the file after all
+    long members_dev = 0; int64_t inflate_up = 0, inflate_down = 0; const char* fallback = nullptr; double t_inflate = 0;
+};
 
 struct Vcf {
     std::vector<std::string> header;   // '##' lines
@@ -719,17 +737,78 @@ static void parse_lines_device(const uint8_t* raw, const std::vector<std::pair<c
 
 // keep_gt_text: the GT tokens as written are needed only by -printTruth.  The (decompressed) file is read whole,
 // the header lines are taken in order and the record lines are parsed on `threads` threads.
+// --device-inflate 1: the file as it lies on the disk, its members listed by vgl_bgzf_index and inflated on the device in batches of
+// 512 (the compressor's batch: 32 MiB of output at most), two batches in flight.  false, with the reason in st.fallback, when the
+// file is not a series of BGZF members or a member came back VGL_INFLATE_HOST: zlib then reads the whole file as without the flag,
+// so that a damaged file gives what it gives today.  A device error ends the run.
+static const int INFLATE_BATCH = 512;
+static bool inflate_on_device(const std::string& fn, const InputOpt& opt, std::vector<uint8_t>& raw, InputStats& st) {
+    std::vector<uint8_t> file;
+    {
+        FILE* f = fopen(fn.c_str(), "rb");
+        if (!f) die("Could not open file: %s", fn.c_str());
+        std::vector<uint8_t> chunk(1 << 22);
+        size_t k;
+        while ((k = fread(chunk.data(), 1, chunk.size(), f)) > 0) file.insert(file.end(), chunk.begin(), chunk.begin() + k);
+        fclose(f);
+    }
+    vgl_inflate_host* h = opt.inflater();                 // (without a device the run ends here, whatever the file holds)
+    const double t0 = now_s();
+    const int64_t cap = (int64_t)file.size() / 28 + 1;
+    std::vector<int64_t> begin((size_t)cap); std::vector<int32_t> csize((size_t)cap), isize((size_t)cap);
+    int64_t n = 0;
+    if (file.empty() || vgl_bgzf_index(file.data(), (int64_t)file.size(), cap, begin.data(), csize.data(), isize.data(), &n) != VGL_OK) {
+        st.fallback = "the file is not a series of BGZF members"; st.t_inflate = now_s() - t0;
+        return false;
+    }
+    int64_t total = 0;
+    for (int64_t m = 0; m < n; m++) total += isize[(size_t)m];
+    raw.resize((size_t)total);
+    const int64_t n_batches = (n + INFLATE_BATCH - 1) / INFLATE_BATCH;
+    int32_t ticket[2] = {0, 0};
+    bool ok = true;
+    int64_t out_at = 0;
+    auto submit = [&](int64_t b) {
+        const int64_t m0 = b * INFLATE_BATCH, m1 = std::min(n, m0 + INFLATE_BATCH);
+        const int64_t lo = begin[(size_t)m0], hi = begin[(size_t)m1 - 1] + csize[(size_t)m1 - 1];
+        std::vector<int64_t> rel((size_t)(m1 - m0));
+        for (int64_t m = m0; m < m1; m++) rel[(size_t)(m - m0)] = begin[(size_t)m] - lo;
+        if (vgl_inflate_host_submit(h, file.data() + lo, hi - lo, (int32_t)(m1 - m0), rel.data(), csize.data() + m0, isize.data() + m0, &ticket[b & 1]) != VGL_OK)
+            die("--device-inflate 1: %s", vgl_last_error());
+        st.inflate_up += hi - lo;
+    };
+    if (n_batches > 0) submit(0);
+    for (int64_t b = 0; b < n_batches; b++) {
+        if (b + 1 < n_batches) submit(b + 1);
+        const uint8_t* out; int64_t out_n; const int32_t* status;
+        if (vgl_inflate_host_wait(h, ticket[b & 1], &out, &out_n, &status) != VGL_OK) die("--device-inflate 1: %s", vgl_last_error());
+        const int64_t m0 = b * INFLATE_BATCH, m1 = std::min(n, m0 + INFLATE_BATCH);
+        for (int64_t m = m0; m < m1; m++) if (status[m - m0] != VGL_INFLATE_OK) ok = false;
+        if (out_at + out_n > total) die("--device-inflate 1: a batch returned more bytes than its members' ISIZE fields hold");
+        if (out_n > 0) memcpy(raw.data() + out_at, out, (size_t)out_n);
+        out_at += out_n; st.inflate_down += out_n; st.members_dev += (long)(m1 - m0);
+    }
+    st.t_inflate = now_s() - t0;
+    if (!ok) { st.fallback = "a member was left to the host (VGL_INFLATE_HOST)"; raw.clear(); return false; }
+    return true;
+}
+
 static Vcf read_vcf(const std::string& fn, bool keep_gt_text, int threads, const InputOpt& opt = InputOpt(), InputStats* stats = nullptr) {
     InputStats st; double t0 = now_s();
-    gzFile fp = gzopen(fn.c_str(), "r");               // plain text, gzip / BGZF, or BCF inside either
-    if (!fp) die("Could not open file: %s", fn.c_str());
-    gzbuffer(fp, 1 << 20);
-    std::vector<uint8_t> raw, chunk(1 << 22);
-    int k;
-    while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) raw.insert(raw.end(), chunk.begin(), chunk.begin() + k);
-    gzclose(fp);
+    std::vector<uint8_t> raw;
+    if (!opt.device_inflate || !inflate_on_device(fn, opt, raw, st)) {
+        gzFile fp = gzopen(fn.c_str(), "r");               // plain text, gzip / BGZF, or BCF inside either
+        if (!fp) die("Could not open file: %s", fn.c_str());
+        gzbuffer(fp, 1 << 20);
+        std::vector<uint8_t> chunk(1 << 22);
+        int k;
+        while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) raw.insert(raw.end(), chunk.begin(), chunk.begin() + k);
+        gzclose(fp);
+    }
     if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) {
         if (opt.device_input) die("--device-input 1 is not supported with BCF input (its genotypes are binary already: there is no text to parse).");
+        st.t_read = now_s() - t0;
+        if (stats) *stats = st;
         return read_bcf(std::move(raw), keep_gt_text);
     }
     st.t_read = now_s() - t0; t0 = now_s();
@@ -1170,11 +1249,24 @@ int main(int argc, char** argv) {
     //  a failure here is not swallowed for good -- vgl_ctx_create on the same device reports it below)
     const int warm_dev = a.devices.empty() ? a.device : a.devices[0];
     const int bgzf_dev = a.device_bgzf ? warm_dev : -1;         // --device-bgzf 1: the run's first device compresses every BGZF stream
-    if (!a.depth_inf) hip_warm = std::thread([warm_dev] { vgl_host_free(vgl_host_alloc_on(warm_dev, 4096)); });
-    InputOpt in_opt; in_opt.device_input = a.device_input; in_opt.source = a.source; in_opt.device = warm_dev; in_opt.tile_sites = a.tile_sites > 0 ? a.tile_sites : 4096;
+    // --device-inflate 1: the inflater's page-locked staging and device buffers are made on that thread too, while the file is read
+    vgl_inflate_host* inflater = nullptr; int inflater_rc = VGL_OK; std::string inflater_err;
+    const bool want_inflater = a.device_inflate == 1;
+    if (!a.depth_inf) hip_warm = std::thread([warm_dev, want_inflater, &inflater, &inflater_rc, &inflater_err] {
+        vgl_host_free(vgl_host_alloc_on(warm_dev, 4096));
+        if (want_inflater && (inflater_rc = vgl_inflate_host_create(warm_dev, INFLATE_BATCH, &inflater)) != VGL_OK) inflater_err = vgl_last_error();
+    });
+    InputOpt in_opt; in_opt.device_inflate = a.device_inflate;
+    in_opt.inflater = [&]() -> vgl_inflate_host* {
+        if (hip_warm.joinable()) hip_warm.join();
+        if (inflater_rc != VGL_OK || !inflater) die("--device-inflate 1: %s", inflater_err.c_str());
+        return inflater;
+    };
+    in_opt.device_input = a.device_input; in_opt.source = a.source; in_opt.device = warm_dev; in_opt.tile_sites = a.tile_sites > 0 ? a.tile_sites : 4096;
     InputStats in_stats;
     Vcf vcf = read_vcf(a.in_fn, a.print_truth != 0, enc_threads, in_opt, &in_stats);
     if (hip_warm.joinable()) hip_warm.join();
+    if (inflater) { vgl_inflate_host_destroy(inflater); inflater = nullptr; }
     lap(0);
     const int N = (int)vcf.samples.size();
     if (N <= 0) die("no samples in %s", a.in_fn.c_str());
@@ -1840,6 +1932,12 @@ int main(int argc, char** argv) {
     if (a.verbose) fprintf(stderr, "[input] --device-input %d: %ld lines parsed on the device, %ld of them again on the host, %.3f GB of text sent up; file read %.3f s, line scan %.3f s, fixed columns %.3f s, device parse and wait %.3f s, host %s %.3f s\n",
                            a.device_input, in_stats.lines_dev, a.device_input ? in_stats.lines_host : 0L, in_stats.text_up / 1e9, in_stats.t_read, in_stats.t_scan, in_stats.t_fixed,
                            in_stats.t_dev, a.device_input ? "re-parse" : "parse", in_stats.t_host);
+    if (a.verbose) {
+        if (!a.device_inflate) fprintf(stderr, "[input] --device-inflate 0: the host read the file (zlib)\n");
+        else fprintf(stderr, "[input] --device-inflate 1: %ld members inflated on the device, %lld compressed bytes sent up, %lld inflated bytes received, %s%s; inflate stage %.3f s of file read %.3f s\n",
+                     in_stats.members_dev, (long long)in_stats.inflate_up, (long long)in_stats.inflate_down, in_stats.fallback ? "the host read the file (zlib): " : "no fallback",
+                     in_stats.fallback ? in_stats.fallback : "", in_stats.t_inflate, in_stats.t_read);
+    }
     char sb[512];
     snprintf(sb, sizeof sb, "\n\n-> Simulation finished successfully.\n\nSummary:\n\tNumber of samples: %d\n\tTotal number of sites simulated: %zu\n"
                             "\tNumber of sites included in simulation output file: %ld\n\tNumber of sites skipped: %ld\n", N, n_sites_total, n_out, n_skipped);

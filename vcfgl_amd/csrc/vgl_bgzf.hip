@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/vcfgl_hip.h"
+#include "vgl_crc32.hip.h"
 
 namespace {
 
@@ -33,28 +34,7 @@ constexpr int MAX_SEGS = (MEMBER + SEG - 1) / SEG;
 constexpr int GRID_MAX = 512;                   // resident member workgroups (per-workgroup match scratch in the workspace)
 constexpr int64_t MEMBER_OVERHEAD = 18 + 5 + 8; // header + stored block header + trailer
 
-// ---- CRC32 (reflected, polynomial 0xEDB88320): shift operators F^(64 * 2^k bytes), k = 0..9, computed at compile time ----------
-struct Gf2 { uint32_t m[32]; };
-constexpr uint32_t gf2_apply(const Gf2& a, uint32_t v) {
-    uint32_t r = 0;
-    for (int i = 0; i < 32; ++i) if ((v >> i) & 1u) r ^= a.m[i];
-    return r;
-}
-constexpr Gf2 gf2_square(const Gf2& a) {
-    Gf2 r{};
-    for (int i = 0; i < 32; ++i) r.m[i] = gf2_apply(a, a.m[i]);
-    return r;
-}
-struct CrcShifts { Gf2 s[10]; };
-constexpr CrcShifts make_crc_shifts() {
-    Gf2 a{};
-    a.m[0] = 0xEDB88320u;                                         // one zero bit shifted through the register
-    for (int i = 1; i < 32; ++i) a.m[i] = 1u << (i - 1);
-    for (int k = 0; k < 9; ++k) a = gf2_square(a);                // 2^9 bits = 64 bytes
-    CrcShifts r{};
-    for (int k = 0; k < 10; ++k) { r.s[k] = a; a = gf2_square(a); }
-    return r;
-}
+// CRC32: shift operators F^(64 * 2^k bytes), k = 0..9 (vgl_crc32.hip.h)
 __constant__ CrcShifts c_crc_shift = make_crc_shifts();
 // RFC 1951 3.2.7: order of the code-length code's lengths; the first 16 bytes of every BGZF member (SAMv1 4.1)
 __constant__ uint8_t c_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};

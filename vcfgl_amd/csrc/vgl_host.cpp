@@ -15,6 +15,7 @@
 
 #include "../../include/vcfgl_hip.h"
 #include "vgl_device.h"
+#include "vgl_inflate_core.h"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, ...) {
@@ -833,6 +834,16 @@ extern "C" int vgl_ctx_kernel_ms(vgl_ctx* c, double* ms, int64_t* launches, int3
 }
 
 extern "C" int vgl_pack_set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+
+// ---- the members of a BGZF stream (pure host arithmetic: vgl_inflate_core.h holds the walk) -----------------------------------------
+extern "C" int vgl_bgzf_index(const uint8_t* raw, int64_t n, int64_t max_members, int64_t* begin, int32_t* csize, int32_t* isize, int64_t* n_members) {
+    if (!raw || n < 0 || max_members < 0 || !n_members || (max_members > 0 && (!begin || !csize || !isize))) return fail(VGL_E_ARG, "vgl_bgzf_index: bad argument");
+    *n_members = 0;
+    if (vgl_bgzf_index_core(raw, n, max_members, begin, csize, isize, n_members) != 0)
+        return fail(VGL_E_UNSUPPORTED, "vgl_bgzf_index: the bytes are not a series of whole BGZF members (gzip members with FLG 4, a 'BC' subfield and ISIZE <= 65536)");
+    if (*n_members > max_members) return fail(VGL_E_CAPACITY, "vgl_bgzf_index: %lld members, room for %lld", (long long)*n_members, (long long)max_members);
+    return VGL_OK;
+}
 
 // what this context launches (include/vcfgl_hip.h: vgl_ctx_info_t)
 extern "C" int vgl_ctx_info(const vgl_ctx* c, vgl_ctx_info_t* out) {
