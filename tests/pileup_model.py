@@ -1,4 +1,4 @@
-"""A plain Python model of the host writer's pileup columns (vcfgl_hip -printPileup 1, host/vcfgl_main.cpp write_tile): what follows
+"""A plain Python model of the host writer's pileup columns (vcfgl_hip -printPileup 1, host/tile_writer.h TileWriter::pileup_line): what follows
 the prefix chrom "\\t" pos "\\t" ref on every line, from a tile's site_status, DP and read dump and the quality rule.
 
     text, offsets = render(site_status, dp, reads)                 # each read's own score + 33

@@ -1,5 +1,5 @@
 """Plain-Python statement of what the device parser of VCF sample columns computes (include/vcfgl_hip.h, "the sample columns of
-VCF text"), and of what the host program's own parser (parse_record + make_site of vcfgl_main.cpp) computes for ANY line.
+VCF text"), and of what the host program's own parser (parse_record of host/vcf_input.h + make_site of host/sites.h) computes for ANY line.
 
     plain_line   the device's contract: (row, allelesum, VCFIN_OK) for a line inside the plain grammar, (None, None, VCFIN_HOST) else
     host_line    the host parser: the row and sum of any line it accepts (atoi on the allele bytes, int8 wrap, a1 = a0 without a

@@ -1,5 +1,5 @@
 """Plain Python model of the VCF text the host writer appends behind a simulated record's eight fixed columns (host/vcf_sink.h,
-Sink::encode_rec, text branch) and of the number formatter it uses (vcfgl_main.cpp put_float / put_int, htslib's kputd):
+Sink::encode_rec, text branch) and of the number formatter it uses (host/host_util.h put_float / put_int, htslib's kputd):
 
     "\\t" KEYS ( "\\t" sample_0 ) ... ( "\\t" sample_{N-1} ) "\\n"
 
