@@ -799,6 +799,56 @@ VGL_API int vgl_inflate_host_submit(vgl_inflate_host* h, const uint8_t* src, int
 VGL_API int vgl_inflate_host_wait(vgl_inflate_host* h, int32_t ticket, const uint8_t** out, int64_t* out_bytes, const int32_t** status);
 VGL_API int vgl_inflate_host_destroy(vgl_inflate_host* h);
 
+/* ---- one genotype's FORMAT/GL as CSV text on the device (ABI 7, additive: the version stays 7) --------------------------------------
+ * What the reference's misc/fetchGl prints behind "POS," for a record: the GL of one requested genotype for every sample.  Alleles
+ * are given as 0 .. 4 (A, C, G, T, the unobserved allele <*> / <NON_REF>), the values of alleles2acgt.  A site has a line when
+ * site_status >= 0 and both alleles occur among its n_alleles entries of alleles2acgt, at indices j0 and j1; the genotype is
+ * g = max (max + 1) / 2 + min and the line is value(0) "," ... "," value(n_samples - 1) "\n".  Every other site (and a site whose
+ * genotype count exceeds max_genotypes) has no bytes.
+ * A value: bits 0x7F800001 -> "MISSING"; otherwise glibc's %f (the exact binary value correctly rounded to six decimals, ties to even,
+ * "-0.000000" for a negative value that rounds to zero, "inf" / "-inf").  The tool prints the float of the file it reads:
+ *   VGL_FETCHGL_FLOAT   the simulated float (what a BCF holds): bits 0x7F800002 -> "END", another NaN -> "nan" / "-nan" by its sign
+ *   VGL_FETCHGL_TEXT    the float a VCF text file gives back: the writers' 6 significant digits (vgl_text_format_device) read as the
+ *                       nearest double, then the nearest float; every NaN but the missing pattern -> "nan"; from 1e21 on as _FLOAT
+ *   vgl_fetchgl_bound            n_sites * n_samples * 48: the longest %f of a float has 47 characters, plus its separator or newline
+ *                                (-1 for a negative argument).  Pure host arithmetic.
+ *   vgl_fetchgl_workspace_bytes  device workspace of a call (-1 for a negative argument).  Pure host arithmetic.
+ *   vgl_fetchgl_format_device    every pointer is device memory of `device`: gl in `layout` (VGL_LAYOUT_*) with max_genotypes
+ *                                (1 .. 15) planes per site.  The contract of vgl_text_format_device: offsets [n_sites + 1] (int64),
+ *                                offsets[i] = where site i's text starts in dst, offsets[n_sites] = the total; a site without a line
+ *                                has length 0.  When the total exceeds dst_cap nothing is written and offsets[n_sites] is the size
+ *                                needed.  Work is enqueued on `hip_stream`; the call returns without synchronising.  VGL_E_ARG for a
+ *                                bad a, b, value_mode, layout, max_genotypes or n_samples < 1.
+ *   vgl_ctx_fetchgl              sets the genotype (a, b in 0 .. 4) and the value mode of a context; a < 0 switches it off.  VGL_E_ARG
+ *                                when the context has add_gl == 0.  Call it while no tile of the context is in flight.
+ *   vgl_ctx_fetchgl_bound        vgl_fetchgl_bound for the context's samples.
+ *   vgl_ctx_fetchgl_next         the side channel of vgl_ctx_pileup_next: the NEXT tile submitted on ctx by vgl_simulate_tile_async,
+ *                                _text_async or _gvcf_async (vgl_simulate_tile included) is also fetched -- whether or not the caller
+ *                                asks for gl: the context keeps the tile's GL on the device, the caller's own outputs are unchanged.
+ *                                text and offsets [n_sites + 1] are host memory that stays valid until vgl_tile_wait, which copies only
+ *                                the bytes produced.  A text larger than text_cap: VGL_E_CAPACITY from vgl_tile_wait with text_needed
+ *                                set.  A tile that is run again on the sibling context after a deep draw is fetched again from the
+ *                                rerun's values; the first run's text is never delivered.  NULL withdraws the request.
+ *                                vgl_simulate_tile_device has no side channel: its caller holds the tile's device arrays and calls
+ *                                vgl_fetchgl_format_device on them. */
+typedef struct vgl_fetchgl_tile {
+    uint8_t* text;          /* host, text_cap bytes */
+    int64_t  text_cap;
+    int64_t* offsets;       /* host, n_sites + 1 */
+    int64_t  text_needed;   /* out (vgl_tile_wait): the size of the tile's text */
+} vgl_fetchgl_tile;
+#define VGL_FETCHGL_FLOAT 0
+#define VGL_FETCHGL_TEXT  1
+VGL_API int64_t vgl_fetchgl_bound(int32_t n_samples, int32_t n_sites);
+VGL_API int64_t vgl_fetchgl_workspace_bytes(int32_t n_samples, int32_t n_sites);
+VGL_API int vgl_fetchgl_format_device(int32_t device, int32_t n_samples, int32_t n_sites, int32_t max_genotypes, int32_t layout,
+                                      const int32_t* site_status, const int32_t* n_alleles, const int8_t* alleles2acgt, const float* gl,
+                                      int32_t a, int32_t b, int32_t value_mode, uint8_t* dst, int64_t dst_cap, int64_t* offsets,
+                                      void* workspace, int64_t workspace_bytes, void* hip_stream);
+VGL_API int vgl_ctx_fetchgl(vgl_ctx* ctx, int32_t a, int32_t b, int32_t value_mode);
+VGL_API int64_t vgl_ctx_fetchgl_bound(const vgl_ctx* ctx, int32_t n_sites);
+VGL_API int vgl_ctx_fetchgl_next(vgl_ctx* ctx, vgl_fetchgl_tile* p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,7 +103,11 @@ EXPORTS = [
     "vgl_vcfin_host_create", "vgl_vcfin_host_submit", "vgl_vcfin_host_wait", "vgl_vcfin_host_destroy",
     "vgl_bgzf_index", "vgl_inflate_workspace_bytes", "vgl_inflate_members_device",
     "vgl_inflate_host_create", "vgl_inflate_host_submit", "vgl_inflate_host_wait", "vgl_inflate_host_destroy",
+    "vgl_fetchgl_bound", "vgl_fetchgl_workspace_bytes", "vgl_fetchgl_format_device",
+    "vgl_ctx_fetchgl", "vgl_ctx_fetchgl_bound", "vgl_ctx_fetchgl_next",
 ]
+# value modes of the fetch-GL formatter (VGL_FETCHGL_*): the simulated float, or the float its VCF text reads back as
+FETCHGL_FLOAT, FETCHGL_TEXT = 0, 1
 # status of a line from the device parser (VGL_VCFIN_*): parsed, or left to the caller's own parser
 VCFIN_OK, VCFIN_HOST = 0, 1
 # status of a BGZF member from the device inflater (VGL_INFLATE_*): inflated to its exact end, or left to the caller's own inflater
@@ -157,6 +161,10 @@ class GvcfTile(C.Structure):
 
 
 class PileupTile(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_cap", C.c_int64), ("offsets", C.c_void_p), ("text_needed", C.c_int64)]
+
+
+class FetchGlTile(C.Structure):
     _fields_ = [("text", C.c_void_p), ("text_cap", C.c_int64), ("offsets", C.c_void_p), ("text_needed", C.c_int64)]
 
 
@@ -295,6 +303,16 @@ def load_library(hooks=False):
     lib.vgl_inflate_host_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     lib.vgl_inflate_host_wait.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]
     lib.vgl_inflate_host_destroy.argtypes = [C.c_void_p]
+    lib.vgl_fetchgl_bound.restype = C.c_int64
+    lib.vgl_fetchgl_bound.argtypes = [C.c_int32, C.c_int32]
+    lib.vgl_fetchgl_workspace_bytes.restype = C.c_int64
+    lib.vgl_fetchgl_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.vgl_fetchgl_format_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vgl_ctx_fetchgl.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    lib.vgl_ctx_fetchgl_bound.restype = C.c_int64
+    lib.vgl_ctx_fetchgl_bound.argtypes = [C.c_void_p, C.c_int32]
+    lib.vgl_ctx_fetchgl_next.argtypes = [C.c_void_p, C.POINTER(FetchGlTile)]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

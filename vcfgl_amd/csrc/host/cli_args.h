@@ -19,7 +19,10 @@ struct Args {
     int device_stream = 0;             // --device-stream 1: a tile's records assembled and BGZF-compressed on the device that simulated it
     int gt_disc = 0;                   // --gt-discordance 1: calls tallied against the truth on the device, <prefix>.discordance.tsv
     int disc_gq = 0;                   // --discordance-gq 0|3|4|5|6: gtDiscordance's -doGQ layout of that file
-    int records = 1;                   // --records 0: no record file; only the discordance table comes back
+    int records = 1;                   // --records 0: no record file; only the discordance table and / or the fetched GLs come back
+    bool fetch = false, fetch_value_given = false;   // --fetch-gl XY: one genotype's GL per site and sample, <prefix>.fetchgl.csv (misc/fetchGl)
+    std::string fetch_gl; int fetch_a = -1, fetch_b = -1;      // the two alleles as 0 .. 4 (A, C, G, T, <*>)
+    int fetch_value = 0, fetch_mode = VGL_FETCHGL_FLOAT;       // --fetch-gl-value 0|1|2 and the VGL_FETCHGL_* mode it selects
     int device_inflate = 0;            // --device-inflate 1: a BGZF input is inflated on the first device of the run
     int device_input = 0;              // --device-input 1: the sample columns of the input VCF text parsed on the first device of the run
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
@@ -82,8 +85,15 @@ static const char USAGE[] =
     "                   --discordance-gq 0|3|4|5|6 [0: gtDiscordance's -doGQ layout of that file: 0 one line per sample, 3 / 4 counts by GQ\n"
     "                   over all samples, 5 / 6 by sample and GQ (7 and 8 equal 6 here: every call has a GQ)]\n"
     "                   --records 0|1 [1; 0: no record file is opened and no FORMAT array, text or encoded record crosses the link: only the\n"
-    "                   discordance table comes back.  Needs --gt-discordance 1; refused with -printPileup 1, -printTruth 1, -doGVCF 1 and\n"
-    "                   the per-read listings]\n"
+    "                   discordance table (--gt-discordance 1) and / or the fetched GLs (--fetch-gl XY) come back.  Needs one of the two;\n"
+    "                   refused with -printPileup 1, -printTruth 1, -doGVCF 1 and the per-read listings]\n"
+    "                   --fetch-gl XY [off; X, Y of A, C, G, T, < (the unobserved allele <*> / <NON_REF>): what misc/fetchGl -gt XY prints for the\n"
+    "                   run's record file is written to <prefix>.fetchgl.csv -- per record that has both alleles, POS and the GL of genotype XY\n"
+    "                   of every sample (%f, MISSING for a sample without reads), formatted on the device that simulated the tile.  Works with\n"
+    "                   every output mode, --device-* path, --devices, --rng-mode, --gt-discordance and --records 0; refused with --depth inf,\n"
+    "                   -doGVCF 1 and -addGL 0]\n"
+    "                   --fetch-gl-value 0|1|2 [0: the value the tool would read from the file this run writes -- -O v / -O z: the 6 digits of\n"
+    "                   the VCF text read back as a float, -O u / -O b: the simulated float; 1: the former; 2: the latter.  Needs --fetch-gl]\n"
     "                   --device-input 0|1 [0: the genotype columns of the input VCF are parsed on the host; 1: on the first GPU of --device /\n"
     "                   --devices: the host reads the file, finds the lines and parses their first nine columns, the text goes up in batches of\n"
     "                   --tile-sites lines and one packed byte per sample comes back.  A line outside the plain grammar (GT alleles of '.' or\n"
@@ -182,6 +192,8 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--gt-discordance") a.gt_disc = I(v);
         else if (f == "--discordance-gq") a.disc_gq = I(v);
         else if (f == "--records") a.records = I(v);
+        else if (f == "--fetch-gl") { a.fetch = true; a.fetch_gl = v; }
+        else if (f == "--fetch-gl-value") { a.fetch_value_given = true; a.fetch_value = I(v); }
         else if (f == "--device-input") a.device_input = I(v);
         else if (f == "--device-inflate") a.device_inflate = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
@@ -198,8 +210,22 @@ static Args parse_args(int argc, char** argv) {
     if (a.disc_gq != 0 && (a.disc_gq < 3 || a.disc_gq > 6)) die("[Bad argument value: '--discordance-gq %d'] Allowed values are 0, 3, 4, 5, 6", a.disc_gq);
     if (a.disc_gq != 0 && !a.gt_disc) die("--discordance-gq %d selects the layout of --gt-discordance 1's file: add --gt-discordance 1.", a.disc_gq);
     if (a.gt_disc && a.depth_inf) die("--gt-discordance 1 is not supported with --depth inf (no tile is simulated: every call would be the truth).");
+    // one genotype's GLs (checked before any GPU work: nothing is written)
+    if (a.fetch) {
+        static const char letters[] = "ACGT<";
+        const char* x = a.fetch_gl.size() == 2 ? strchr(letters, a.fetch_gl[0]) : nullptr;
+        const char* y = a.fetch_gl.size() == 2 ? strchr(letters, a.fetch_gl[1]) : nullptr;
+        if (!x || !y || !*x || !*y) die("[Bad argument value: '--fetch-gl %s'] A genotype is two of A, C, G, T, < (the unobserved allele).", a.fetch_gl.c_str());
+        a.fetch_a = (int)(x - letters); a.fetch_b = (int)(y - letters);
+        range(a.fetch_value, 0, 2, "--fetch-gl-value");
+        if (a.depth_inf) die("--fetch-gl %s is not supported with --depth inf (no tile is simulated).", a.fetch_gl.c_str());
+        if (a.do_gvcf) die("--fetch-gl %s is not supported with -doGVCF 1 (block records).", a.fetch_gl.c_str());
+        if (!a.add_gl) die("--fetch-gl %s with -addGL 0: Could not read GL tag.", a.fetch_gl.c_str());
+        const bool text_file = a.output_mode == "v" || a.output_mode == "z";
+        a.fetch_mode = a.fetch_value == 1 || (a.fetch_value == 0 && text_file) ? VGL_FETCHGL_TEXT : VGL_FETCHGL_FLOAT;
+    } else if (a.fetch_value_given) die("--fetch-gl-value %d selects the values of --fetch-gl XY's file: add --fetch-gl XY.", a.fetch_value);
     if (!a.records) {
-        if (!a.gt_disc) die("--records 0 writes no record file: it needs --gt-discordance 1, whose table is then the run's only output.");
+        if (!a.gt_disc && !a.fetch) die("--records 0 writes no record file: it needs --gt-discordance 1 or --fetch-gl XY, whose file is then the run's only output.");
         if (a.print_pileup) die("--records 0 is not supported with -printPileup 1 (the pileup is a listing of every read).");
         if (a.print_truth) die("--records 0 is not supported with -printTruth 1 (the truth file is a record file).");
         if (a.do_gvcf) die("--records 0 is not supported with -doGVCF 1 (gVCF blocks are records).");

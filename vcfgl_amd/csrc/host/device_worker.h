@@ -30,6 +30,7 @@ struct DeviceWorker {
             if (B) {
                 if (t_first < 0.0) t_first = now_s();
                 if (P.device_pileup && vgl_ctx_pileup_next(ctx, &B->pt) != VGL_OK) die("%s", vgl_last_error());   // (a side channel of the tile call below)
+                if (P.fetch && vgl_ctx_fetchgl_next(ctx, &B->ft) != VGL_OK) die("%s", vgl_last_error());               // (likewise)
                 int rc = VGL_OK;
                 switch (P.path) {
                 case ARRAYS: rc = vgl_simulate_tile_async(ctx, B->t0, B->ns, B->gt.data(), &B->o, &ticket); break;
@@ -45,6 +46,7 @@ struct DeviceWorker {
                 if (P.path == TEXT && !hs) text_bytes += (double)prev->toff[prev->ns];
                 if (P.path == GVCF) text_bytes += (double)prev->g.text_needed;
                 if (P.device_pileup) text_bytes += (double)prev->pt.text_needed;
+                if (P.fetch) text_bytes += (double)prev->ft.text_needed;
                 tiles += 1; sites += prev->ns; t_last = now_s();
                 { std::lock_guard<std::mutex> lk(prev->m); prev->done = true; }
                 prev->cv.notify_all();

@@ -18,6 +18,7 @@ struct RunPlan {
     bool stream = false;                      // --device-stream 1: records assembled and compressed where the tile was simulated
     bool device_pileup = false;               // --device-pileup 1: the pileup's sample columns come from the device
     bool rec0 = false;                        // --records 0: no record file, no FORMAT array back; the tiles are simulated and tallied
+    bool fetch = false;                       // --fetch-gl XY: one genotype's GL of every tile comes back as CSV text
     bool want_dp = false, want_errp = false, dump_reads = false, dump_pick = false;
     bool host_pileup = false;                 // -printPileup 1 without it: the lines are formatted on the host from the read dump
 };
@@ -49,6 +50,11 @@ static RunPlan make_plan(const Args& a, const vgl_params& p, int N, int enc_thre
         P.TS = std::max(1, std::min(P.TS, (int)((64u << 20) / ((size_t)1024 * (size_t)std::max(N, 1)) + 1)));
     else if (P.device_pileup) {                                  // the pileup text of a tile: at most 256 MiB per ring entry (two per device)
         const int64_t per_site = vgl_pileup_bound(N, 1, P.pile_cap);
+        P.TS = std::max(1, (int)std::min<int64_t>(P.TS, (int64_t)(256u << 20) / std::max<int64_t>(per_site, 1)));
+    }
+    P.fetch = a.fetch;
+    if (P.fetch) {                                               // the fetched text of a tile: at most 256 MiB per ring entry, as the pileup's
+        const int64_t per_site = vgl_fetchgl_bound(N, 1);
         P.TS = std::max(1, (int)std::min<int64_t>(P.TS, (int64_t)(256u << 20) / std::max<int64_t>(per_site, 1)));
     }
     // ---- devices: one context and one host thread per GPU; tiles are dealt to them round robin and come back to the writer
@@ -110,6 +116,7 @@ struct TileBufs {
     std::vector<int32_t> contig; std::vector<int64_t> pos0;
     PBuf<int32_t> gitems, fdp, fpl, ldp, lpl; PBuf<int64_t> boff; vgl_gvcf_tile g;
     PBuf<uint8_t> ptext; PBuf<int64_t> poff; vgl_pileup_tile pt;      // --device-pileup 1: the tile's pileup columns and site offsets
+    PBuf<uint8_t> ftext; PBuf<int64_t> foff; vgl_fetchgl_tile ft;     // --fetch-gl XY: the tile's CSV columns and site offsets
     vgl_tile_out o;
     std::mutex m; std::condition_variable cv; bool done = false;
 
@@ -120,8 +127,14 @@ struct TileBufs {
         const size_t TS = (size_t)P.TS, N = (size_t)P.N, A = (size_t)P.A, G = (size_t)P.G, E = TS * N;
         meta.resize(TS); gt.resize(E);
         st.resize(TS, device); na.resize(TS, device); nobs.resize(TS, device); a2b.resize(TS * 5, device);
-        memset(&o, 0, sizeof o); memset(&pt, 0, sizeof pt); memset(&g, 0, sizeof g);
+        memset(&o, 0, sizeof o); memset(&pt, 0, sizeof pt); memset(&g, 0, sizeof g); memset(&ft, 0, sizeof ft);
         o.site_status = st.data(); o.n_alleles = na.data(); o.n_alleles_obs = nobs.data(); o.alleles2acgt = a2b.data();
+        if (P.fetch) {
+            const int64_t cap = vgl_ctx_fetchgl_bound(ctx, P.TS);
+            if (cap < 0) die("--fetch-gl: %s", vgl_last_error());
+            ftext.resize((size_t)std::max<int64_t>(cap, 1), device); foff.resize(TS + 1, device);
+            ft.text = ftext.data(); ft.text_cap = cap; ft.offsets = foff.data();
+        }
         if (P.rec0) return;                                      // (the per-site status and alleles above: a few bytes per site, for the run's summary)
         idp.resize(TS, device); o.info_dp = idp.data();         // also tells which sites reach the read loop (TSV dumps)
         if (a.add_info_ad) { iad.resize(TS * A, device); o.info_ad = iad.data(); }

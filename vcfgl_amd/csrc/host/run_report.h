@@ -114,6 +114,8 @@ static void verbose_report(const Args& a, const RunPlan& P, const std::vector<vg
                 P.devices[d], W.tiles, W.sites, gb, dt > 0 ? dt : 0.0, dt > 0 ? gb / dt : 0.0, dt > 0 ? (double)W.sites * N / dt : 0.0,
                 (double)ci.workspace_bytes / 1e9, ci.sample_lean, ci.fused, ci.fused_split);
     }
+    if (P.fetch) fprintf(stderr, "[fetch-gl] --fetch-gl %s (%s values): %ld lines written, %ld sites without the genotype\n", a.fetch_gl.c_str(),
+                         a.fetch_mode == VGL_FETCHGL_TEXT ? "VCF text" : "simulated float", w.n_fetch_lines, w.n_fetch_absent);
     const double* t = w.timer.t;
     fprintf(stderr, "\n[timing] read input %.3f s, decode sites %.3f s, device context(s) %.3f s, waiting for the device(s) (simulation incl. PCIe, overlapped with the writer) %.3f s, encode %.3f s, write/compress %.3f s, tile buffers %.3f s, teardown %.3f s, pileup %.3f s\n",
             t[StageTimer::READ], t[StageTimer::SITES], t[StageTimer::CONTEXT], t[StageTimer::DEVICE_WAIT], t[StageTimer::ENCODE], t[StageTimer::WRITE], t[StageTimer::TILE_BUFFERS],
@@ -137,6 +139,7 @@ static void finish_run(const Args& a, const RunPlan& P, RunLog& runlog, const si
     std::vector<std::string> files;
     if (!P.rec0) files.push_back("-> Simulation output file: " + a.out_prefix + P.ext);
     if (a.gt_disc) files.push_back("-> Genotype discordance file: " + a.out_prefix + ".discordance.tsv");
+    if (a.fetch) files.push_back("-> Fetched genotype likelihoods file: " + a.out_prefix + ".fetchgl.csv");
     if (a.print_pileup) files.push_back("-> Pileup output file: " + a.out_prefix + ".pileup.gz");
     if (a.print_truth) files.push_back("-> True genotypes output file: " + a.out_prefix + ".truth" + P.ext);
     if (a.print_bpe) files.push_back("-> Base pick error output: stdout");

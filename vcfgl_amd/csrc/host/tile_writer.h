@@ -19,6 +19,7 @@ struct TileWriter {
     vsink::Sink out;
     FILE* pile_fp = nullptr; vsink::Bgzf pile;            // the reference writes the pileup through htslib's BGZF (vcfgl.cpp:1776-1783)
     GvcfBlocker gv;
+    FILE* fetch_fp = nullptr; std::string fetch_buf; long n_fetch_lines = 0, n_fetch_absent = 0;      // --fetch-gl XY: <prefix>.fetchgl.csv
     std::vector<std::string> enc; std::string line, tsv;
     long n_out = 0, n_skipped = 0;
     int n_fmt = 0;                                              // FORMAT fields of a simulated record
@@ -41,6 +42,7 @@ struct TileWriter {
             for (int k = 0; k < 7; k++) { ids[k] = on[k] ? out.key_id(keys[k]) : 0; n_fmt += on[k] ? 1 : 0; }
             for (vgl_ctx* ctx : ctxs) if (vgl_ctx_bcf_keys(ctx, ids, 7) != VGL_OK) die("--device-bcf 1: %s", vgl_last_error());
         }
+        if (P.fetch) { fetch_fp = fopen((a.out_prefix + ".fetchgl.csv").c_str(), "wb"); if (!fetch_fp) die("Could not open file: %s.fetchgl.csv", a.out_prefix.c_str()); }
         if (a.print_pileup) {
             pile_fp = fopen((a.out_prefix + ".pileup.gz").c_str(), "wb"); if (!pile_fp) die("Could not open pileup output");
             pile.open(pile_fp, 1, P.bgzf_dev);
@@ -248,6 +250,21 @@ struct TileWriter {
         timer.carve(StageTimer::PILEUP, now_s() - t_pile);          // --verbose 1: the pileup's own stage, out of write/compress
     }
 
+    // --fetch-gl XY: "POS," here, the values and the newline from the device; a record without the genotype has no line
+    void fetch_lines(const TileBufs& B) {
+        fetch_buf.clear();
+        char hb[32];
+        for (int i = 0; i < B.ns; i++) {
+            const int64_t b = B.foff[i], e = B.foff[i + 1];
+            if (e <= b) { if (B.st[i] >= 0) n_fetch_absent++; continue; }
+            snprintf(hb, sizeof hb, "%ld,", B.meta[i].pos0 + 1); fetch_buf += hb;
+            fetch_buf.append((const char*)B.ftext.data() + b, (size_t)(e - b));
+            n_fetch_lines++;
+        }
+        if (!fetch_buf.empty() && fwrite(fetch_buf.data(), 1, fetch_buf.size(), fetch_fp) != fetch_buf.size()) die("Could not write file: %s.fetchgl.csv", a.out_prefix.c_str());
+    }
+    void close_fetch() { if (fetch_fp && fclose(fetch_fp) != 0) die("Could not write file: %s.fetchgl.csv", a.out_prefix.c_str()); fetch_fp = nullptr; }
+
     bool skipped(const TileBufs& B, int i) { if (B.st[i] >= 0) return false; n_skipped++; return true; }
 
     // -doGVCF 1 on the host: write_record_values (vcfgl.cpp:167-206) carries the open block from record to record (and from tile to
@@ -309,6 +326,7 @@ struct TileWriter {
             if (skipped(B, i)) continue;
             if (a.do_gvcf && P.path != GVCF) host_gvcf_site(B, i);   // (plain records, device gVCF: written below)
         }
+        if (P.fetch) fetch_lines(B);
         if (P.rec0) return;                                      // (no listing, no pileup, no record: the sites were counted)
         if (P.path == GVCF) write_gvcf_tile(B);
         if (!a.do_gvcf) write_records(B);

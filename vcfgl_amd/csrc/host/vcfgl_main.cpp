@@ -106,6 +106,7 @@ int main(int argc, char** argv) {
     timer.restart();
     for (int d = 0; d < P.D; d++) if (vgl_ctx_create(&p, P.devices[d], P.TS, &ctxs[d]) != VGL_OK) die("%s", vgl_last_error());
     if (a.gt_disc) for (vgl_ctx* ctx : ctxs) if (vgl_ctx_discordance(ctx, 1) != VGL_OK) die("--gt-discordance 1: %s", vgl_last_error());
+    if (P.fetch) for (vgl_ctx* ctx : ctxs) if (vgl_ctx_fetchgl(ctx, a.fetch_a, a.fetch_b, a.fetch_mode) != VGL_OK) die("--fetch-gl %s: %s", a.fetch_gl.c_str(), vgl_last_error());
     timer.lap(StageTimer::CONTEXT);
     TileWriter w(a, P, vcf, timer);
     w.open(ctxs);
@@ -119,6 +120,7 @@ int main(int argc, char** argv) {
     if (!P.rec0) w.out.close();
     if (a.print_truth) truth_sink.close();
     if (a.gt_disc) write_discordance(a, vcf, ctxs);
+    w.close_fetch();
     timer.lap(StageTimer::WRITE);
     if (w.pile_fp) { w.pile.close(); fclose(w.pile_fp); }
     // contexts and page-locked buffers are not torn down one by one (0.06 s): the process ends below with _exit(), after the run

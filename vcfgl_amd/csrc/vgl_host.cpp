@@ -239,8 +239,15 @@ struct vgl_ctx {
         // copies the text back, which knows its size
         vgl_pileup_tile* pile = nullptr; int32_t pile_qc = -1;
         uint8_t* d_ptext = nullptr; int64_t d_ptext_bytes = 0; int64_t* d_poff = nullptr; void* d_pws = nullptr; int64_t d_pws_bytes = 0;
+        // vgl_ctx_fetchgl_next: one genotype's GL of the tile as CSV text, formatted on the device (vgl_fetchgl.hip) from its GL planes --
+        // kept on the device whether or not the caller asks for them; vgl_tile_wait copies the text back, which knows its size
+        vgl_fetchgl_tile* fetch = nullptr;
+        uint8_t* d_ftext = nullptr; int64_t d_ftext_bytes = 0; int64_t* d_foff = nullptr; void* d_fws = nullptr; int64_t d_fws_bytes = 0;
     } slot[2];
     vgl_pileup_tile* pile_next = nullptr;                           // vgl_ctx_pileup_next: taken by the next tile call
+    // vgl_ctx_fetchgl: the requested alleles (0 .. 4; fetch_a < 0: off) and value mode; vgl_ctx_fetchgl_next: taken by the next tile call
+    int32_t fetch_a = -1, fetch_b = -1, fetch_mode = 0;
+    vgl_fetchgl_tile* fetch_next = nullptr;
     // vgl_ctx_bcf_keys: the text / gVCF tile calls deliver BCF typed vectors (vgl_bcf.hip) instead of text; dictionary ids of
     // DP, GL, PL, GP, AD, ADF, ADR
     bool bcf = false; int32_t bcf_keys[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -381,7 +388,8 @@ extern "C" int vgl_ctx_destroy(vgl_ctx* c) {
         if (S.busy && S.ev_copied) (void)hipEventSynchronize(S.ev_copied);
         for (void* q : S.d_out) if (q) (void)hipFree(q);
         void* dq[] = {S.d_gt, S.d_reads_out, S.d_errp_out, S.d_pick_out, S.d_text, S.d_toff, S.d_tws, S.d_contig, S.d_pos0, S.d_dps, S.d_items,
-                      S.d_counts, S.d_bdp, S.d_bpl, S.d_bna, S.d_bst, S.d_rst, S.d_edge, S.d_gws, S.d_btext, S.d_boff, S.d_ptext, S.d_poff, S.d_pws};
+                      S.d_counts, S.d_bdp, S.d_bpl, S.d_bna, S.d_bst, S.d_rst, S.d_edge, S.d_gws, S.d_btext, S.d_boff, S.d_ptext, S.d_poff, S.d_pws,
+                      S.d_ftext, S.d_foff, S.d_fws};
         for (void* q : dq) if (q) (void)hipFree(q);
         if (S.h_gt) (void)hipHostFree(S.h_gt);
         void* hq[] = {S.h_counts, S.h_contig, S.h_pos0};
@@ -1415,6 +1423,38 @@ static int enqueue_pileup(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites, con
                                   S.d_ptext, S.pile->text_cap, S.d_poff, S.d_pws, S.d_pws_bytes, c->s_compute);
 }
 
+// ---- one genotype's GL of a context's tiles as CSV text (vgl_fetchgl.hip) ----------------------------------------------------------
+extern "C" int vgl_ctx_fetchgl(vgl_ctx* c, int32_t a, int32_t b, int32_t value_mode) {
+    if (!c) return fail(VGL_E_ARG, "vgl_ctx_fetchgl: null context");
+    for (const auto& S : c->slot) if (S.busy) return fail(VGL_E_ARG, "vgl_ctx_fetchgl: a tile of the context is in flight");
+    if (a < 0) { c->fetch_a = c->fetch_b = -1; c->fetch_next = nullptr; return VGL_OK; }
+    if (a > 4 || b < 0 || b > 4) return fail(VGL_E_ARG, "vgl_ctx_fetchgl: alleles are 0 .. 4 (A, C, G, T, unobserved)");
+    if (value_mode != VGL_FETCHGL_FLOAT && value_mode != VGL_FETCHGL_TEXT) return fail(VGL_E_ARG, "vgl_ctx_fetchgl: value_mode must be VGL_FETCHGL_FLOAT or VGL_FETCHGL_TEXT");
+    if (!c->p.add_gl) return fail(VGL_E_ARG, "vgl_ctx_fetchgl: the context computes no GL (add_gl = 0)");
+    c->fetch_a = a; c->fetch_b = b; c->fetch_mode = value_mode;
+    return VGL_OK;
+}
+
+extern "C" int64_t vgl_ctx_fetchgl_bound(const vgl_ctx* c, int32_t n_sites) {
+    if (!c || n_sites < 0) return -1;
+    return vgl_fetchgl_bound(c->dp.n_samples, n_sites);
+}
+
+extern "C" int vgl_ctx_fetchgl_next(vgl_ctx* c, vgl_fetchgl_tile* p) {
+    if (!c) return fail(VGL_E_ARG, "null ctx");
+    if (p && c->fetch_a < 0) return fail(VGL_E_ARG, "vgl_ctx_fetchgl_next: no genotype is set (vgl_ctx_fetchgl)");
+    if (p && (!p->offsets || p->text_cap < 0 || (p->text_cap > 0 && !p->text))) return fail(VGL_E_ARG, "vgl_ctx_fetchgl_next: null text or offsets");
+    c->fetch_next = p;
+    return VGL_OK;
+}
+
+// the formatter on the slot's device planes (compute stream): text into d_ftext, site offsets into d_foff
+static int enqueue_fetchgl(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites) {
+    return vgl_fetchgl_format_device(c->device, c->dp.n_samples, n_sites, c->dp.G, c->dp.out_layout, (const int32_t*)S.d_out[0], (const int32_t*)S.d_out[1],
+                                     (const int8_t*)S.d_out[3], (const float*)S.d_out[11], c->fetch_a, c->fetch_b, c->fetch_mode, S.d_ftext,
+                                     S.fetch->text_cap, S.d_foff, S.d_fws, S.d_fws_bytes, c->s_compute);
+}
+
 // Host buffers in, host buffers out, asynchronously: the tile's kernels are enqueued on the context's compute stream, the copies of
 // its tags back to the host on its copy stream behind them; with two tiles in flight the copies of tile t overlap the kernels of
 // tile t + 1.  Destination buffers from vgl_host_alloc() (pinned) are written by DMA directly; pageable ones work, more slowly.
@@ -1435,6 +1475,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
         if (S.gvcf) text_mask |= 1u << 10 | 1u << 12;                  // (the blocker reads FORMAT/DP and PL)
     }
     if (S.pile) text_mask |= 1u << 10;                                  // (the pileup formatter reads FORMAT/DP)
+    if (S.fetch) text_mask |= 1u << 11;                                 // (the fetch-GL formatter reads FORMAT/GL)
     S.dev_fields = 0;
     for (int f = 0; f < N_FIELDS; f++) {
         void* host = *(void**)((char*)o + FIELDS[f].off);
@@ -1516,9 +1557,26 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
             S.d_ptext_bytes = S.pile->text_cap;
         }
     }
+    if (S.fetch) {
+        const int64_t ws = vgl_fetchgl_workspace_bytes((int32_t)N, c->max_sites);
+        if (S.d_fws_bytes < ws) {
+            if (S.d_fws) (void)hipFree(S.d_fws);
+            S.d_fws = nullptr; S.d_fws_bytes = 0;
+            HIPCHK(hipMalloc(&S.d_fws, (size_t)(ws ? ws : 1)));
+            S.d_fws_bytes = ws;
+        }
+        if (!S.d_foff) HIPCHK(hipMalloc((void**)&S.d_foff, sizeof(int64_t) * ((size_t)c->max_sites + 1)));
+        if (S.d_ftext_bytes < S.fetch->text_cap || !S.d_ftext) {
+            if (S.d_ftext) (void)hipFree(S.d_ftext);
+            S.d_ftext = nullptr; S.d_ftext_bytes = 0;
+            HIPCHK(hipMalloc((void**)&S.d_ftext, (size_t)(S.fetch->text_cap ? S.fetch->text_cap : 1)));
+            S.d_ftext_bytes = S.fetch->text_cap;
+        }
+    }
     int rc = vgl_simulate_tile_device(c, site0, n_sites, S.d_gt, &d, c->s_compute);
     if (rc) return rc;
     if (S.pile && (rc = enqueue_pileup(c, S, n_sites, d)) != VGL_OK) return rc;
+    if (S.fetch && (rc = enqueue_fetchgl(c, S, n_sites)) != VGL_OK) return rc;
     // this tile's device error flags, then a clean word for the next tile
     HIPCHK(hipMemcpyAsync(S.h_flag, c->d_errflag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute));
     HIPCHK(hipMemsetAsync(c->d_errflag, 0, sizeof(uint32_t), c->s_compute));
@@ -1537,6 +1595,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     if (S.text) HIPCHK(hipMemcpyAsync(S.h_toff, S.d_toff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, c->s_copy));
     if (S.gvcf && (rc = copy_gvcf_small(c, S, n_sites, c->s_copy)) != VGL_OK) return rc;
     if (S.pile) HIPCHK(hipMemcpyAsync(S.pile->offsets, S.d_poff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, c->s_copy));
+    if (S.fetch) HIPCHK(hipMemcpyAsync(S.fetch->offsets, S.d_foff, sizeof(int64_t) * ((size_t)n_sites + 1), hipMemcpyDeviceToHost, c->s_copy));
     HIPCHK(hipEventRecord(S.ev_copied, c->s_copy));
     return VGL_OK;
 }
@@ -1553,6 +1612,8 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     if (!c || !o || !ticket) return fail(VGL_E_ARG, "null argument");
     vgl_pileup_tile* const pile = c->pile_next;                     // (taken by this call, whether it succeeds or not)
     c->pile_next = nullptr;
+    vgl_fetchgl_tile* const fetch = c->fetch_next;                  // (likewise)
+    c->fetch_next = nullptr;
     if (gq) {
         const vgl_gvcf_tile* g = gq->g;
         if (!g || !g->items || !g->record_offsets || !g->block_offsets || g->text_cap < 0 || (g->text_cap > 0 && !g->text) || gq->n_dps < 0 ||
@@ -1582,13 +1643,15 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     S.text_dev = want_text && c->text_dev;
     S.gvcf = gq != nullptr; S.h_gv = gq ? gq->g : nullptr;
     S.pile = pile;
-    if (pile) { const int rc = pileup_qual_char(c, &S.pile_qc); if (rc != VGL_OK) { S.pile = nullptr; return rc; } }
+    S.fetch = fetch;
+    if (pile) { const int rc = pileup_qual_char(c, &S.pile_qc); if (rc != VGL_OK) { S.pile = nullptr; S.fetch = nullptr; return rc; } }
     if (gq) S.dps.assign(gq->dps, gq->dps + gq->n_dps);
-    if ((want_text || gq || pile) && !c->s_text) HIPCHK(hipStreamCreateWithFlags(&c->s_text, hipStreamNonBlocking));
+    if ((want_text || gq || pile || fetch) && !c->s_text) HIPCHK(hipStreamCreateWithFlags(&c->s_text, hipStreamNonBlocking));
     if (n_sites == 0) {
         if (want_text) toff[0] = 0;
         if (gq) { gq->g->record_offsets[0] = 0; gq->g->block_offsets[0] = 0; }
         if (pile) pile->offsets[0] = 0;
+        if (fetch) fetch->offsets[0] = 0;
         HIPCHK(hipEventRecord(S.ev_copied, c->s_copy));
     } else {
         const int rc = enqueue_host_tile(c, S, site0, n_sites, gt, o, gq ? gq->contig : nullptr, gq ? gq->pos0 : nullptr);
@@ -1676,8 +1739,13 @@ static int deep_rerun_text(vgl_ctx* c, vgl_ctx::HostSlot& S) {
         if (rc == VGL_OK) rc = vgl_ctx_check(c->deep, c->s_compute);
         if (rc != VGL_OK) return rc;                                 // (a draw beyond VGL_READ_CAP_MAX reads: VGL_E_CAPACITY after all)
     }
-    const int rc = S.gvcf ? enqueue_gvcf(c, S, S.n_sites) : enqueue_text(c, S, S.n_sites);
+    const int rc = S.gvcf ? enqueue_gvcf(c, S, S.n_sites) : S.text ? enqueue_text(c, S, S.n_sites) : VGL_OK;
     if (rc != VGL_OK) return rc;
+    if (S.fetch) {                                                   // fetched again from the rerun's values: the first run's text is never delivered
+        const int r2 = enqueue_fetchgl(c, S, S.n_sites);
+        if (r2 != VGL_OK) return r2;
+        HIPCHK(hipMemcpyAsync(S.fetch->offsets, S.d_foff, sizeof(int64_t) * ((size_t)S.n_sites + 1), hipMemcpyDeviceToHost, c->s_compute));
+    }
     for (int f = 0; f < N_FIELDS; f++) {
         void* host = *(void**)((char*)&S.o + FIELDS[f].off);
         if (host) HIPCHK(hipMemcpyAsync(host, S.d_out[f], field_count(c, FIELDS[f].kind, (size_t)S.n_sites) * FIELDS[f].esz, hipMemcpyDeviceToHost, c->s_compute));
@@ -1708,6 +1776,22 @@ static int finish_gvcf(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     return VGL_OK;
 }
 
+// fetch-GL: the text crosses the link (only the bytes produced)
+static int finish_fetchgl(vgl_ctx* c, vgl_ctx::HostSlot& S) {
+    vgl_fetchgl_tile* p = S.fetch;
+    if (S.n_sites == 0) { p->text_needed = 0; return VGL_OK; }
+    const int64_t total = p->offsets[S.n_sites];
+    p->text_needed = total;
+    if (total < 0 || total > p->text_cap)
+        return fail(VGL_E_CAPACITY, "the tile's fetch-GL text needs %lld bytes, text_cap is %lld (text_needed holds the size; vgl_ctx_fetchgl_bound bounds it)",
+                    (long long)total, (long long)p->text_cap);
+    if (total > 0) {
+        HIPCHK(hipMemcpyAsync(p->text, S.d_ftext, (size_t)total, hipMemcpyDeviceToHost, c->s_text));
+        HIPCHK(hipStreamSynchronize(c->s_text));
+    }
+    return VGL_OK;
+}
+
 // pileup: the text crosses the link (only the bytes produced); offsets[n_sites] = -1: a dp beyond the dump's capacity
 static int finish_pileup(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     vgl_pileup_tile* p = S.pile;
@@ -1735,7 +1819,7 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
     int rc2 = VGL_OK;
     if (S.pile && S.n_sites == 0) S.pile->text_needed = 0;
     if ((*S.h_flag & VGL_DEVERR_CAPACITY) && S.n_sites > 0) {
-        const bool dev_text = S.text || S.gvcf;
+        const bool dev_text = S.text || S.gvcf || S.fetch;               // (formatted from the slot's device planes: the rerun fills those)
         const int rc = dev_text ? deep_rerun_text(c, S) : deep_rerun(c, S);
         if (rc != VGL_E_CAPACITY && (rc != VGL_OK || !dev_text)) return rc;      // done (or failed for another reason, reported as such)
         if (rc == VGL_E_CAPACITY) return flags_to_rc(c, *S.h_flag);
@@ -1743,8 +1827,9 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
         const int rc = flags_to_rc(c, *S.h_flag);
         if (rc != VGL_OK) return rc;
         if (S.pile && (rc2 = finish_pileup(c, S)) != VGL_OK) return rc2;
-        if (!(S.text || S.gvcf)) return VGL_OK;
     }
+    if (S.fetch && (rc2 = finish_fetchgl(c, S)) != VGL_OK) return rc2;
+    if (!(S.text || S.gvcf)) return VGL_OK;
     if (S.gvcf) return finish_gvcf(c, S);
     // text: only the bytes the tile produced cross the link
     const int64_t total = S.h_toff[S.n_sites];

@@ -121,3 +121,15 @@ def tiles(sites: List[Site], max_sites: int):
     for i in range(0, len(sites), max_sites):
         chunk = sites[i:i + max_sites]
         yield i, np.stack([s.gt for s in chunk]) if chunk else np.zeros((0, 0), np.uint8)
+
+
+def fetch_gl_csv(sim, sites: List[Site], genotype: str, value_mode: int, max_sites: Optional[int] = None, site0: int = 0) -> bytes:
+    """The <prefix>.fetchgl.csv of a run over `sites` (vcfgl_hip --fetch-gl XY): per record of the output file that has both alleles,
+    "POS,gl_0,...,gl_{N-1}" with the GL of genotype XY, formatted on the device (Simulator.fetch_gl; vcfgl_amd.fetchgl)."""
+    sim.fetch_gl(genotype, value_mode=value_mode)
+    out = []
+    for i, gt in tiles(sites, max_sites or sim.max_sites_per_tile):
+        _, f = sim.simulate_fetched(site0 + i, gt, fields=["site_status", "n_alleles", "alleles2acgt"])
+        out.append(f.lines([s.pos0 + 1 for s in sites[i:i + gt.shape[0]]]))
+    sim.fetch_gl(None)
+    return b"".join(out)

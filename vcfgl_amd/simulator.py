@@ -25,6 +25,29 @@ def pack_gt(a0, a1):
     return (lo | (hi << 4)).astype(np.uint8)
 
 
+class FetchedGl:
+    """One tile's fetched GL (vgl_fetchgl_tile): `text` holds `needed` bytes after vgl_tile_wait, `offsets[i]` is where site i's text
+    starts (a site without a line has length 0)."""
+
+    def __init__(self, n_sites, text_cap):
+        self.n_sites = n_sites
+        self.buf = np.zeros(max(int(text_cap), 1), dtype=np.uint8)
+        self.offsets = np.zeros(n_sites + 1, dtype=np.int64)
+        self.req = _abi.FetchGlTile(self.buf.ctypes.data, int(text_cap), self.offsets.ctypes.data, -1)
+
+    @property
+    def needed(self):
+        return int(self.req.text_needed)
+
+    @property
+    def text(self):
+        return self.buf[:max(self.needed, 0)].tobytes()
+
+    def lines(self, pos):
+        from .fetchgl import lines
+        return lines(pos, self.text, self.offsets)
+
+
 class Simulator:
     """One vgl_ctx.  `simulate(site0, gt)` takes host numpy GT bytes [n_sites][n_samples];
     `simulate_device(site0, gt_tensor, tile, stream)` takes torch device tensors."""
@@ -108,6 +131,31 @@ class Simulator:
         t = np.zeros(table_len(self.n_samples), dtype=np.int64)
         self._check(self.lib.vgl_ctx_discordance_read(self.ctx, t.ctypes.data, 1 if reset else 0))
         return t
+
+    def fetch_gl(self, a, b=None, value_mode=_abi.FETCHGL_FLOAT):
+        """vgl_ctx_fetchgl: sets the genotype whose GL `fetch_next` / `simulate_fetched` hand back as CSV text (vcfgl_amd.fetchgl).
+        a, b: allele codes 0 .. 4, or a = a two-letter string such as "AC" or "A<"; a = None or negative switches it off."""
+        if isinstance(a, str):
+            from .fetchgl import allele_codes
+            a, b = allele_codes(a)
+        if a is None or a < 0:
+            a, b = -1, -1
+        self._check(self.lib.vgl_ctx_fetchgl(self.ctx, a, b, value_mode))
+
+    def fetch_next(self, n_sites, text_cap=None):
+        """vgl_ctx_fetchgl_next: the next tile submitted through vgl_simulate_tile / _async / _text_async / _gvcf_async is also fetched.
+        Returns the FetchedGl that vgl_tile_wait fills; keep it alive until then."""
+        if text_cap is None:
+            text_cap = self.lib.vgl_ctx_fetchgl_bound(self.ctx, n_sites)
+        f = FetchedGl(n_sites, text_cap)
+        self._check(self.lib.vgl_ctx_fetchgl_next(self.ctx, C.byref(f.req)))
+        return f
+
+    def simulate_fetched(self, site0, gt, fields=None, text_cap=None):
+        """`simulate` with the tile's fetched GL: (tile, FetchedGl).  fields may leave out "gl": the context keeps it on the device."""
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        f = self.fetch_next(gt.shape[0], text_cap)
+        return self.simulate(site0, gt, fields=fields), f
 
     def close(self):
         if getattr(self, "ctx", None):
