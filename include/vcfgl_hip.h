@@ -58,6 +58,8 @@ extern "C" {
 #define VGL_E_ADJQ         (-7)  /* --adjust-qs 1|2 met a read without a valid adjusted quality score: error probability
                                     exactly 0 or 1, or a negative adjusted score (the reference exits on
                                     ASSERT(adjqScore_i != -1), vcfgl.cpp:558, and ASSERT(qs >= 0 ...), gl_methods.cpp:101) */
+#define VGL_E_SETAL        (-8)  /* vgl_ctx_set_alleles: a site's target list names an allele its record does not have (misc/setAlleles
+                                    reads uninitialised memory there); vgl_last_error() names the absolute site */
 
 /* ---- per-site status (reference: return value of simulate_record_values) ------------- */
 #define VGL_SITE_OK            0
@@ -848,6 +850,54 @@ VGL_API int vgl_fetchgl_format_device(int32_t device, int32_t n_samples, int32_t
 VGL_API int vgl_ctx_fetchgl(vgl_ctx* ctx, int32_t a, int32_t b, int32_t value_mode);
 VGL_API int64_t vgl_ctx_fetchgl_bound(const vgl_ctx* ctx, int32_t n_sites);
 VGL_API int vgl_ctx_fetchgl_next(vgl_ctx* ctx, vgl_fetchgl_tile* p);
+
+/* ---- a prescribed REF/ALT list for every record, on the device (ABI 7, additive: the version stays 7) ------------------------------
+ * What the reference's misc/setAlleles does to a record file, done to the arrays of a tile before any writer reads them.  For a site
+ * with site_status >= 0 and its target entry -- 8 bytes: [n_alleles_new (2 .. 5), a0 .. a4 as 0 .. 4 (A, C, G, T, the unobserved
+ * allele <*> / <NON_REF>; -1 behind the count), 2 pad bytes] --
+ *   old2new[a]      the index of old allele a (alleles2acgt) in the new list, or -1;
+ *   oldgt2newgt[g]  bcf_alleles2gt(old2new[a1], old2new[a2]) for g = a2 (a2 + 1) / 2 + a1 when both are >= 0
+ *   qs              new[old2new[a]] = old[a]; entries behind the new count keep what they held
+ *   gl, pl, gp      per sample new[oldgt2newgt[g]] = old[g], then: GL -- a NaN among the new values: the sample is missing and stays as
+ *                   it is; otherwise the float maximum is subtracted.  PL -- VGL_INT32_MISSING among them: missing; otherwise
+ *                   (int32)((float)pl - (float)min).  GP -- a NaN: missing; otherwise each value is divided by the float sum taken in
+ *                   ascending genotype order (IEEE division, no fused operation)
+ *   pl_u8           the same selection; a sample is missing iff fmt_dp == 0 (255 is also a capped value), otherwise v - min
+ *   n_alleles, alleles2acgt   the target's, written last
+ * VGL_LAYOUT_PLANES: planes g >= nGenotypes_new(site) get the missing value (0x7F800001, VGL_INT32_MISSING, 255).
+ * VGL_LAYOUT_SAMPLE_MAJOR: the record's array shrinks to n_samples * nGenotypes_new(site) values at the head of its slab; what lies
+ * behind it is unspecified.  Nothing else is touched: DP, I16, n_alleles_obs and the AD tags keep the old alleles (the tool leaves AD,
+ * ADF and ADR with the old count -- a malformed record; vgl_ctx_set_alleles refuses a context that writes them).
+ * A target that is not a list of 2 .. 5 distinct alleles all of which the record has is REFUSED (the tool reads uninitialised memory
+ * for an absent allele): the site's arrays are left as they are and the smallest such site index is stored into *bad_site.
+ *   vgl_setal_workspace_bytes  device workspace of a call (-1 for a negative argument).  Pure host arithmetic.
+ *   vgl_setal_apply_device     every pointer is device memory of `device`.  targets [n_sites][8] (int8), site_status [n_sites],
+ *                              n_alleles [n_sites] and alleles2acgt [n_sites][5] (read and written), qs [n_sites][max_alleles] or NULL,
+ *                              fmt_dp [n_sites][n_samples] (needed with pl_u8), gl / pl / gp / pl_u8 in `layout` with max_genotypes
+ *                              (1 .. 15) planes per site, each may be NULL.  bad_site: one int32 the CALLER sets to INT32_MAX (or any
+ *                              value >= n_sites) beforehand; the call lowers it (atomic minimum) to the first refused site of the
+ *                              tile, counted from 0.  Work is enqueued on `hip_stream`; the call returns without synchronising.
+ *                              VGL_E_ARG for a bad count, layout, a NULL among the required pointers, pl_u8 without fmt_dp or a
+ *                              workspace smaller than vgl_setal_workspace_bytes.
+ *   vgl_ctx_set_alleles        `table` is host memory, n_sites entries for the absolute sites first_site .. first_site + n_sites - 1; it
+ *                              is validated (VGL_E_ARG for a count outside 2 .. 5, an allele outside 0 .. 4 or a duplicate) and copied
+ *                              to the device.  NULL switches the feature off.  Call it while no tile of the context is in flight.
+ *                              Every tile then submitted by vgl_simulate_tile, vgl_simulate_tile_async or _text_async (text, BCF
+ *                              vectors and the record streams built from them alike) is relabelled behind its likelihood kernels
+ *                              and before any copy-back, formatter or encoder; a tile with a site outside the table returns
+ *                              VGL_E_ARG at submit.  A tile that is run again on the sibling context after a deep draw is relabelled
+ *                              from the rerun's values.  A refused site: VGL_E_SETAL from vgl_tile_wait, vgl_last_error() names the
+ *                              absolute site.  VGL_E_ARG when the context has add_fmt_ad, add_info_ad, an ADF / ADR flag or do_gvcf
+ *                              set; vgl_simulate_tile_gvcf_async returns VGL_E_ARG while a table is set.
+ *                              vgl_simulate_tile_device has no hook: its caller holds the tile's device arrays and calls
+ *                              vgl_setal_apply_device on them.  The discordance tally and the fetch-GL side channel of a context see
+ *                              the tile as simulated / as relabelled respectively; composing them is not specified. */
+VGL_API int64_t vgl_setal_workspace_bytes(int32_t n_samples, int32_t n_sites, int32_t max_genotypes);
+VGL_API int vgl_setal_apply_device(int32_t device, int32_t n_samples, int32_t n_sites, int32_t max_genotypes, int32_t max_alleles, int32_t layout,
+                                   const int8_t* targets, const int32_t* site_status, int32_t* n_alleles, int8_t* alleles2acgt, float* qs,
+                                   const int32_t* fmt_dp, float* gl, int32_t* pl, float* gp, uint8_t* pl_u8, int32_t* bad_site,
+                                   void* workspace, int64_t workspace_bytes, void* hip_stream);
+VGL_API int vgl_ctx_set_alleles(vgl_ctx* ctx, const int8_t* table, int64_t first_site, int64_t n_sites);
 
 #ifdef __cplusplus
 }

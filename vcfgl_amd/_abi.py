@@ -10,6 +10,7 @@ ABI_VERSION = 7
 
 VGL_OK = 0
 VGL_E_ARG, VGL_E_NODEVICE, VGL_E_NOMEM, VGL_E_CAPACITY, VGL_E_UNSUPPORTED, VGL_E_QSBIN, VGL_E_ADJQ = -1, -2, -3, -4, -5, -6, -7
+VGL_E_SETAL = -8
 VGL_SITE_OK, VGL_SITE_SKIP_INVAR, VGL_SITE_SKIP_EMPTY, VGL_SITE_NO_READS = 0, -3, -4, 1
 VGL_RNG_TILE, VGL_RNG_SERIAL = 0, 1
 VGL_BETA_RAND48, VGL_BETA_STD = 0, 1
@@ -105,6 +106,7 @@ EXPORTS = [
     "vgl_inflate_host_create", "vgl_inflate_host_submit", "vgl_inflate_host_wait", "vgl_inflate_host_destroy",
     "vgl_fetchgl_bound", "vgl_fetchgl_workspace_bytes", "vgl_fetchgl_format_device",
     "vgl_ctx_fetchgl", "vgl_ctx_fetchgl_bound", "vgl_ctx_fetchgl_next",
+    "vgl_setal_workspace_bytes", "vgl_setal_apply_device", "vgl_ctx_set_alleles",
 ]
 # value modes of the fetch-GL formatter (VGL_FETCHGL_*): the simulated float, or the float its VCF text reads back as
 FETCHGL_FLOAT, FETCHGL_TEXT = 0, 1
@@ -313,6 +315,10 @@ def load_library(hooks=False):
     lib.vgl_ctx_fetchgl_bound.restype = C.c_int64
     lib.vgl_ctx_fetchgl_bound.argtypes = [C.c_void_p, C.c_int32]
     lib.vgl_ctx_fetchgl_next.argtypes = [C.c_void_p, C.POINTER(FetchGlTile)]
+    lib.vgl_setal_workspace_bytes.restype = C.c_int64
+    lib.vgl_setal_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.vgl_setal_apply_device.argtypes = [C.c_int32] * 6 + [C.c_void_p] * 12 + [C.c_int64, C.c_void_p]
+    lib.vgl_ctx_set_alleles.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

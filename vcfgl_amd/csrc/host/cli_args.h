@@ -23,6 +23,7 @@ struct Args {
     bool fetch = false, fetch_value_given = false;   // --fetch-gl XY: one genotype's GL per site and sample, <prefix>.fetchgl.csv (misc/fetchGl)
     std::string fetch_gl; int fetch_a = -1, fetch_b = -1;      // the two alleles as 0 .. 4 (A, C, G, T, <*>)
     int fetch_value = 0, fetch_mode = VGL_FETCHGL_FLOAT;       // --fetch-gl-value 0|1|2 and the VGL_FETCHGL_* mode it selects
+    std::string set_alleles_fn;        // --set-alleles FILE: every record gets the REF/ALT list of its line (misc/setAlleles), relabelled on the device
     int device_inflate = 0;            // --device-inflate 1: a BGZF input is inflated on the first device of the run
     int device_input = 0;              // --device-input 1: the sample columns of the input VCF text parsed on the first device of the run
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
@@ -94,6 +95,12 @@ static const char USAGE[] =
     "                   -doGVCF 1 and -addGL 0]\n"
     "                   --fetch-gl-value 0|1|2 [0: the value the tool would read from the file this run writes -- -O v / -O z: the 6 digits of\n"
     "                   the VCF text read back as a float, -O u / -O b: the simulated float; 1: the former; 2: the latter.  Needs --fetch-gl]\n"
+    "                   --set-alleles FILE [off; what misc/setAlleles -a FILE does to the run's record file, done on the device before any record\n"
+    "                   is written: line i of FILE (REF<TAB>ALT[,ALT...], 1 to 4 ALTs of A, C, G, T and the run's unobserved allele) is the allele\n"
+    "                   list of the i-th record; QS, GL, PL and GP are re-indexed to it and renormalised.  Every allele of a line must be one of\n"
+    "                   its record's (else the run stops, naming the site).  Works with every output mode, --device-text / -bcf / -stream / -bgzf,\n"
+    "                   --devices, --rng-mode, -printTruth and -printPileup (unchanged files); refused with --depth inf, -doGVCF 1,\n"
+    "                   --rm-empty-sites 1, --rm-invar-sites with 4, the AD / ADF / ADR tags, --gt-discordance 1, --fetch-gl and --records 0]\n"
     "                   --device-input 0|1 [0: the genotype columns of the input VCF are parsed on the host; 1: on the first GPU of --device /\n"
     "                   --devices: the host reads the file, finds the lines and parses their first nine columns, the text goes up in batches of\n"
     "                   --tile-sites lines and one packed byte per sample comes back.  A line outside the plain grammar (GT alleles of '.' or\n"
@@ -194,6 +201,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--records") a.records = I(v);
         else if (f == "--fetch-gl") { a.fetch = true; a.fetch_gl = v; }
         else if (f == "--fetch-gl-value") { a.fetch_value_given = true; a.fetch_value = I(v); }
+        else if (f == "--set-alleles") a.set_alleles_fn = v;
         else if (f == "--device-input") a.device_input = I(v);
         else if (f == "--device-inflate") a.device_inflate = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
@@ -224,6 +232,19 @@ static Args parse_args(int argc, char** argv) {
         const bool text_file = a.output_mode == "v" || a.output_mode == "z";
         a.fetch_mode = a.fetch_value == 1 || (a.fetch_value == 0 && text_file) ? VGL_FETCHGL_TEXT : VGL_FETCHGL_FLOAT;
     } else if (a.fetch_value_given) die("--fetch-gl-value %d selects the values of --fetch-gl XY's file: add --fetch-gl XY.", a.fetch_value);
+    // a prescribed allele list per record (checked before any GPU work: nothing is written)
+    if (!a.set_alleles_fn.empty()) {
+        const char* fn = a.set_alleles_fn.c_str();
+        if (a.depth_inf) die("--set-alleles %s is not supported with --depth inf (no tile is simulated: the records carry no likelihoods to relabel).", fn);
+        if (a.do_gvcf) die("--set-alleles %s is not supported with -doGVCF 1 (a block record stands for many sites).", fn);
+        if (a.rm_empty) die("--set-alleles %s is not supported with --rm-empty-sites 1 (the device decides which sites become records: the record index of a line is not known ahead).", fn);
+        if (a.rm_invar & 4) die("--set-alleles %s is not supported with --rm-invar-sites %d (bit 4: the device decides which sites become records: the record index of a line is not known ahead).", fn, a.rm_invar);
+        if (a.add_fmt_ad || a.add_info_ad || a.add_fmt_adf || a.add_info_adf || a.add_fmt_adr || a.add_info_adr)
+            die("--set-alleles %s is not supported with the AD / ADF / ADR tags (misc/setAlleles leaves them with the old allele count: a malformed record).", fn);
+        if (a.gt_disc) die("--set-alleles %s is not supported with --gt-discordance 1 (composing the two is not implemented).", fn);
+        if (a.fetch) die("--set-alleles %s is not supported with --fetch-gl %s (composing the two is not implemented).", fn, a.fetch_gl.c_str());
+        if (!a.records) die("--set-alleles %s is not supported with --records 0 (it changes the record file, and none is written).", fn);
+    }
     if (!a.records) {
         if (!a.gt_disc && !a.fetch) die("--records 0 writes no record file: it needs --gt-discordance 1 or --fetch-gl XY, whose file is then the run's only output.");
         if (a.print_pileup) die("--records 0 is not supported with -printPileup 1 (the pileup is a listing of every read).");

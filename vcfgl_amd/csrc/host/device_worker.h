@@ -42,7 +42,9 @@ struct DeviceWorker {
                 if (rc != VGL_OK) die("%s", vgl_last_error());
             }
             if (prev) {
-                if (vgl_tile_wait(ctx, prev_ticket) != VGL_OK) die("%s", vgl_last_error());
+                const int wrc = vgl_tile_wait(ctx, prev_ticket);
+                if (wrc == VGL_E_SETAL) die("--set-alleles: %s.  Every allele of a line must be one of its record's alleles.", vgl_last_error());
+                if (wrc != VGL_OK) die("%s", vgl_last_error());
                 if (P.path == TEXT && !hs) text_bytes += (double)prev->toff[prev->ns];
                 if (P.path == GVCF) text_bytes += (double)prev->g.text_needed;
                 if (P.device_pileup) text_bytes += (double)prev->pt.text_needed;

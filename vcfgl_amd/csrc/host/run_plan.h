@@ -19,6 +19,7 @@ struct RunPlan {
     bool device_pileup = false;               // --device-pileup 1: the pileup's sample columns come from the device
     bool rec0 = false;                        // --records 0: no record file, no FORMAT array back; the tiles are simulated and tallied
     bool fetch = false;                       // --fetch-gl XY: one genotype's GL of every tile comes back as CSV text
+    bool setal = false;                       // --set-alleles FILE: every context relabels its tiles from the file's table
     bool want_dp = false, want_errp = false, dump_reads = false, dump_pick = false;
     bool host_pileup = false;                 // -printPileup 1 without it: the lines are formatted on the host from the read dump
 };
@@ -52,7 +53,7 @@ static RunPlan make_plan(const Args& a, const vgl_params& p, int N, int enc_thre
         const int64_t per_site = vgl_pileup_bound(N, 1, P.pile_cap);
         P.TS = std::max(1, (int)std::min<int64_t>(P.TS, (int64_t)(256u << 20) / std::max<int64_t>(per_site, 1)));
     }
-    P.fetch = a.fetch;
+    P.fetch = a.fetch; P.setal = !a.set_alleles_fn.empty();
     if (P.fetch) {                                               // the fetched text of a tile: at most 256 MiB per ring entry, as the pileup's
         const int64_t per_site = vgl_fetchgl_bound(N, 1);
         P.TS = std::max(1, (int)std::min<int64_t>(P.TS, (int64_t)(256u << 20) / std::max<int64_t>(per_site, 1)));

@@ -13,15 +13,16 @@
 //   * -printTruth 1: the decoded input records (incl. exploded ones) as <prefix>.truth.vcf
 // CPU simulation path here.  Input: VCF text, gzip / bgzip'd VCF, BCF (raw or BGZF).
 // The units, each a header beside this file: host_util.h (exit, clock, number text), cli_args.h, vcf_input.h, sites.h, gvcf_blocker.h,
-// out_header.h, run_plan.h (RunPlan, TileBufs), device_worker.h, tile_writer.h, run_report.h, depth_inf.h, self_test.h.
+// out_header.h, run_plan.h (RunPlan, TileBufs), device_worker.h, tile_writer.h, run_report.h, depth_inf.h, self_test.h, set_alleles.h.
 #include "depth_inf.h"
 #include "self_test.h"
+#include "set_alleles.h"
 
 // ---- the tile ring: produce (decode sites, hand the tile to its device) up to R tiles ahead, write in order.  Returns the number of sites.
 // An entry's buffers are page-locked when the entry is first used (about 0.04 s per 250 MB): the second entry of a device is
 // prepared while the device already works on the first tile
 static size_t run_ring(const Args& a, const RunPlan& P, SiteStream& stream, const std::vector<vgl_ctx*>& ctxs, std::vector<std::unique_ptr<TileBufs>>& ring,
-                       const std::vector<std::unique_ptr<DeviceWorker>>& workers, TileWriter& w) {
+                       const std::vector<std::unique_ptr<DeviceWorker>>& workers, TileWriter& w, const size_t setal_lines) {
     const size_t R = (size_t)P.R, D = (size_t)P.D;
     StageTimer& timer = w.timer;
     size_t n_sites_total = 0, produced = 0, consumed = 0;
@@ -50,6 +51,8 @@ static size_t run_ring(const Args& a, const RunPlan& P, SiteStream& stream, cons
                 B.contig[i] = last_id; B.pos0[i] = B.meta[i].pos0;
             }
             n_sites_total += (size_t)B.ns;
+            if (P.setal && n_sites_total > setal_lines)
+                die("--set-alleles %s has %zu lines but the run has more records: one line per record is needed.", a.set_alleles_fn.c_str(), setal_lines);
             if (P.host_pileup) memset(B.reads.data(), 0xFF, (size_t)P.pile_cap * B.ns * P.N);
             workers[B.dev]->push(&B);
             produced++;
@@ -82,6 +85,7 @@ int main(int argc, char** argv) {
         const int k = gzread(fp, magic, 3); gzclose(fp);
         if (k == 3 && !memcmp(magic, "BCF", 3)) die("--device-input 1 is not supported with BCF input (its genotypes are binary already: there is no text to parse).");
     }
+    const std::vector<int8_t> setal_table = a.set_alleles_fn.empty() ? std::vector<int8_t>() : read_set_alleles(a);   // (a bad file: before any file of the run exists)
     RunLog runlog; runlog.open(a);
     StageTimer timer;
     const int enc_threads = encode_threads(a);
@@ -107,6 +111,8 @@ int main(int argc, char** argv) {
     for (int d = 0; d < P.D; d++) if (vgl_ctx_create(&p, P.devices[d], P.TS, &ctxs[d]) != VGL_OK) die("%s", vgl_last_error());
     if (a.gt_disc) for (vgl_ctx* ctx : ctxs) if (vgl_ctx_discordance(ctx, 1) != VGL_OK) die("--gt-discordance 1: %s", vgl_last_error());
     if (P.fetch) for (vgl_ctx* ctx : ctxs) if (vgl_ctx_fetchgl(ctx, a.fetch_a, a.fetch_b, a.fetch_mode) != VGL_OK) die("--fetch-gl %s: %s", a.fetch_gl.c_str(), vgl_last_error());
+    const size_t setal_lines = setal_table.size() / 8;
+    if (P.setal) for (vgl_ctx* ctx : ctxs) if (vgl_ctx_set_alleles(ctx, setal_table.data(), 0, (int64_t)setal_lines) != VGL_OK) die("--set-alleles %s: %s", a.set_alleles_fn.c_str(), vgl_last_error());
     timer.lap(StageTimer::CONTEXT);
     TileWriter w(a, P, vcf, timer);
     w.open(ctxs);
@@ -114,7 +120,9 @@ int main(int argc, char** argv) {
     std::vector<std::unique_ptr<TileBufs>> ring(P.R);
     std::vector<std::unique_ptr<DeviceWorker>> workers(P.D);
     for (int d = 0; d < P.D; d++) workers[d].reset(new DeviceWorker(P, ctxs[d], w.hstream[d], a.gvcf_dps));
-    const size_t n_sites_total = run_ring(a, P, stream, ctxs, ring, workers, w);
+    const size_t n_sites_total = run_ring(a, P, stream, ctxs, ring, workers, w, setal_lines);
+    if (P.setal && n_sites_total != setal_lines)
+        die("--set-alleles %s has %zu lines but the run has %zu records: one line per record is needed.", a.set_alleles_fn.c_str(), setal_lines, n_sites_total);
     w.flush_gvcf();
     timer.restart();
     if (!P.rec0) w.out.close();

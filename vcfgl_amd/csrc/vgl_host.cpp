@@ -243,11 +243,17 @@ struct vgl_ctx {
         // kept on the device whether or not the caller asks for them; vgl_tile_wait copies the text back, which knows its size
         vgl_fetchgl_tile* fetch = nullptr;
         uint8_t* d_ftext = nullptr; int64_t d_ftext_bytes = 0; int64_t* d_foff = nullptr; void* d_fws = nullptr; int64_t d_fws_bytes = 0;
+        // vgl_ctx_set_alleles: the tile's arrays are relabelled on the device (vgl_setal.hip) behind its likelihood kernels; d_sbad / h_sbad
+        // (pinned) hold the first refused site of the tile, counted from its first site (>= n_sites: none)
+        bool setal = false; int32_t* d_sbad = nullptr; int32_t* h_sbad = nullptr; void* d_sws = nullptr; int64_t d_sws_bytes = 0;
     } slot[2];
     vgl_pileup_tile* pile_next = nullptr;                           // vgl_ctx_pileup_next: taken by the next tile call
     // vgl_ctx_fetchgl: the requested alleles (0 .. 4; fetch_a < 0: off) and value mode; vgl_ctx_fetchgl_next: taken by the next tile call
     int32_t fetch_a = -1, fetch_b = -1, fetch_mode = 0;
     vgl_fetchgl_tile* fetch_next = nullptr;
+    // vgl_ctx_set_alleles: the target entries (8 bytes each) of the absolute sites setal_first .. setal_first + setal_n - 1 on the device;
+    // shared with the sibling context `deep` (setal_shared there: not its to free)
+    int8_t* d_setal = nullptr; int64_t setal_first = 0, setal_n = 0; bool setal_shared = false;
     // vgl_ctx_bcf_keys: the text / gVCF tile calls deliver BCF typed vectors (vgl_bcf.hip) instead of text; dictionary ids of
     // DP, GL, PL, GP, AD, ADF, ADR
     bool bcf = false; int32_t bcf_keys[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -384,13 +390,15 @@ extern "C" int vgl_ctx_destroy(vgl_ctx* c) {
     if (c->d_disc_dp) (void)hipFree(c->d_disc_dp);
     if (c->d_disc_pl) (void)hipFree(c->d_disc_pl);
     if (c->d_disc_table && !c->disc_shared) (void)hipFree(c->d_disc_table);
+    if (c->d_setal && !c->setal_shared) (void)hipFree(c->d_setal);
     for (auto& S : c->slot) {
         if (S.busy && S.ev_copied) (void)hipEventSynchronize(S.ev_copied);
         for (void* q : S.d_out) if (q) (void)hipFree(q);
         void* dq[] = {S.d_gt, S.d_reads_out, S.d_errp_out, S.d_pick_out, S.d_text, S.d_toff, S.d_tws, S.d_contig, S.d_pos0, S.d_dps, S.d_items,
                       S.d_counts, S.d_bdp, S.d_bpl, S.d_bna, S.d_bst, S.d_rst, S.d_edge, S.d_gws, S.d_btext, S.d_boff, S.d_ptext, S.d_poff, S.d_pws,
-                      S.d_ftext, S.d_foff, S.d_fws};
+                      S.d_ftext, S.d_foff, S.d_fws, S.d_sbad, S.d_sws};
         for (void* q : dq) if (q) (void)hipFree(q);
+        if (S.h_sbad) (void)hipHostFree(S.h_sbad);
         if (S.h_gt) (void)hipHostFree(S.h_gt);
         void* hq[] = {S.h_counts, S.h_contig, S.h_pos0};
         for (void* q : hq) if (q) (void)hipHostFree(q);
@@ -1126,6 +1134,8 @@ extern "C" int vgl_ctx_discordance_read(vgl_ctx* c, int64_t* host_table, int32_t
 // the sibling context of a deep tile counts into its parent's table
 static void deep_share_disc(vgl_ctx* c) {
     c->deep->disc = c->disc; c->deep->disc_shared = true; c->deep->d_disc_table = c->d_disc_table;
+    // (and relabels from its parent's target table: vgl_ctx_set_alleles)
+    c->deep->d_setal = c->d_setal; c->deep->setal_first = c->setal_first; c->deep->setal_n = c->setal_n; c->deep->setal_shared = true;
 }
 
 extern "C" int vgl_ctx_check(vgl_ctx* c, void* stream) {
@@ -1455,6 +1465,64 @@ static int enqueue_fetchgl(vgl_ctx* c, vgl_ctx::HostSlot& S, int32_t n_sites) {
                                      S.fetch->text_cap, S.d_foff, S.d_fws, S.d_fws_bytes, c->s_compute);
 }
 
+// ---- a prescribed REF/ALT list for the records of a context's tiles (vgl_setal.hip) -------------------------------------------------
+extern "C" int vgl_ctx_set_alleles(vgl_ctx* c, const int8_t* table, int64_t first_site, int64_t n_sites) {
+    if (!c) return fail(VGL_E_ARG, "vgl_ctx_set_alleles: null context");
+    for (const auto& S : c->slot) if (S.busy) return fail(VGL_E_ARG, "vgl_ctx_set_alleles: a tile of the context is in flight");
+    HIPCHK(hipSetDevice(c->device));
+    if (!table) {
+        if (c->d_setal && !c->setal_shared) (void)hipFree(c->d_setal);
+        c->d_setal = nullptr; c->setal_first = c->setal_n = 0; c->setal_shared = false;
+        if (c->deep) { c->deep->d_setal = nullptr; c->deep->setal_n = 0; }
+        return VGL_OK;
+    }
+    const vgl_params& p = c->p;
+    if (p.add_fmt_ad || p.add_info_ad || p.add_fmt_adf || p.add_info_adf || p.add_fmt_adr || p.add_info_adr)
+        return fail(VGL_E_ARG, "vgl_ctx_set_alleles: the context writes AD / ADF / ADR tags, which keep the old alleles (misc/setAlleles leaves them stale)");
+    if (p.do_gvcf) return fail(VGL_E_ARG, "vgl_ctx_set_alleles: not supported with do_gvcf (block records)");
+    if (first_site < 0 || n_sites < 0) return fail(VGL_E_ARG, "vgl_ctx_set_alleles: negative first_site or n_sites");
+    for (int64_t i = 0; i < n_sites; i++) {
+        const int8_t* e = table + i * 8;
+        if (e[0] < 2 || e[0] > 5) return fail(VGL_E_ARG, "vgl_ctx_set_alleles: site %lld has %d alleles (2 .. 5)", (long long)(first_site + i), (int)e[0]);
+        for (int j = 0; j < e[0]; j++) {
+            if (e[1 + j] < 0 || e[1 + j] > 4) return fail(VGL_E_ARG, "vgl_ctx_set_alleles: site %lld: allele %d is not 0 .. 4", (long long)(first_site + i), (int)e[1 + j]);
+            for (int k = 0; k < j; k++) if (e[1 + k] == e[1 + j]) return fail(VGL_E_ARG, "vgl_ctx_set_alleles: site %lld names an allele twice", (long long)(first_site + i));
+        }
+    }
+    if (c->d_setal && !c->setal_shared) (void)hipFree(c->d_setal);
+    c->d_setal = nullptr; c->setal_n = 0; c->setal_shared = false;
+    HIPCHK(hipMalloc((void**)&c->d_setal, (size_t)(n_sites ? n_sites * 8 : 8)));
+    if (n_sites) HIPCHK(hipMemcpy(c->d_setal, table, (size_t)n_sites * 8, hipMemcpyHostToDevice));
+    c->setal_first = first_site; c->setal_n = n_sites;
+    if (c->deep) deep_share_disc(c);
+    return VGL_OK;
+}
+
+// the relabelling of a tile's device arrays `d` (compute stream); the first refused site of the tile into S.h_sbad
+static int enqueue_setal(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, int32_t n_sites, const vgl_tile_out& d, hipStream_t st) {
+    const int32_t N = c->dp.n_samples;
+    const int64_t ws = vgl_setal_workspace_bytes(N, c->max_sites, c->dp.G);
+    if (S.d_sws_bytes < ws) {
+        if (S.d_sws) (void)hipFree(S.d_sws);
+        S.d_sws = nullptr; S.d_sws_bytes = 0;
+        HIPCHK(hipMalloc(&S.d_sws, (size_t)ws));
+        S.d_sws_bytes = ws;
+    }
+    if (!S.d_sbad) HIPCHK(hipMalloc((void**)&S.d_sbad, sizeof(int32_t)));
+    if (!S.h_sbad) HIPCHK(hipHostMalloc((void**)&S.h_sbad, sizeof(int32_t), hipHostMallocDefault));
+    HIPCHK(hipMemsetAsync(S.d_sbad, 0x7F, sizeof(int32_t), st));
+    const int rc = vgl_setal_apply_device(c->device, N, n_sites, c->dp.G, c->dp.A, c->dp.out_layout, c->d_setal + (site0 - c->setal_first) * 8, d.site_status, d.n_alleles,
+                                          d.alleles2acgt, d.qs, d.fmt_dp, d.gl, d.pl, d.gp, d.pl_u8, S.d_sbad, S.d_sws, S.d_sws_bytes, st);
+    if (rc != VGL_OK) return rc;
+    HIPCHK(hipMemcpyAsync(S.h_sbad, S.d_sbad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    return VGL_OK;
+}
+static int setal_rc(vgl_ctx::HostSlot& S) {
+    if (!S.setal || !S.h_sbad || *S.h_sbad < 0 || *S.h_sbad >= S.n_sites) return VGL_OK;
+    return fail(VGL_E_SETAL, "site %lld: the target allele list names an allele the record does not have (misc/setAlleles is undefined there)",
+                (long long)(S.site0 + *S.h_sbad));
+}
+
 // Host buffers in, host buffers out, asynchronously: the tile's kernels are enqueued on the context's compute stream, the copies of
 // its tags back to the host on its copy stream behind them; with two tiles in flight the copies of tile t overlap the kernels of
 // tile t + 1.  Destination buffers from vgl_host_alloc() (pinned) are written by DMA directly; pageable ones work, more slowly.
@@ -1476,6 +1544,8 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     }
     if (S.pile) text_mask |= 1u << 10;                                  // (the pileup formatter reads FORMAT/DP)
     if (S.fetch) text_mask |= 1u << 11;                                 // (the fetch-GL formatter reads FORMAT/GL)
+    if (S.setal && (o->pl_u8 || (text_mask >> 17 & 1u))) text_mask |= 1u << 10;    // (the one-byte PL is relabelled by FORMAT/DP == 0)
+    if (S.setal) text_mask |= 1u << 0 | 1u << 1 | 1u << 3;
     S.dev_fields = 0;
     for (int f = 0; f < N_FIELDS; f++) {
         void* host = *(void**)((char*)o + FIELDS[f].off);
@@ -1575,6 +1645,7 @@ static int enqueue_host_tile(vgl_ctx* c, vgl_ctx::HostSlot& S, int64_t site0, in
     }
     int rc = vgl_simulate_tile_device(c, site0, n_sites, S.d_gt, &d, c->s_compute);
     if (rc) return rc;
+    if (S.setal && (rc = enqueue_setal(c, S, site0, n_sites, d, c->s_compute)) != VGL_OK) return rc;
     if (S.pile && (rc = enqueue_pileup(c, S, n_sites, d)) != VGL_OK) return rc;
     if (S.fetch && (rc = enqueue_fetchgl(c, S, n_sites)) != VGL_OK) return rc;
     // this tile's device error flags, then a clean word for the next tile
@@ -1627,6 +1698,10 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     if (want_text && c->p.out_layout != VGL_LAYOUT_SAMPLE_MAJOR) return fail(VGL_E_ARG, "vgl_simulate_tile_text_async: the context needs out_layout = VGL_LAYOUT_SAMPLE_MAJOR");
     if (n_sites < 0 || n_sites > c->max_sites) return fail(VGL_E_ARG, "n_sites %d exceeds max_sites_per_tile %d", n_sites, c->max_sites);
     if (n_sites > 0 && !gt) return fail(VGL_E_ARG, "null gt");
+    if (c->d_setal && gq) return fail(VGL_E_ARG, "vgl_simulate_tile_gvcf_async: not supported while vgl_ctx_set_alleles is set");
+    if (c->d_setal && n_sites > 0 && (site0 < c->setal_first || site0 + n_sites > c->setal_first + c->setal_n))
+        return fail(VGL_E_ARG, "the tile's sites %lld .. %lld are not all inside vgl_ctx_set_alleles' table (%lld .. %lld)", (long long)site0, (long long)(site0 + n_sites - 1),
+                    (long long)c->setal_first, (long long)(c->setal_first + c->setal_n - 1));
     HIPCHK(hipSetDevice(c->device));
     const int k = c->next_slot;
     vgl_ctx::HostSlot& S = c->slot[k];
@@ -1644,6 +1719,7 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     S.gvcf = gq != nullptr; S.h_gv = gq ? gq->g : nullptr;
     S.pile = pile;
     S.fetch = fetch;
+    S.setal = c->d_setal != nullptr && n_sites > 0;
     if (pile) { const int rc = pileup_qual_char(c, &S.pile_qc); if (rc != VGL_OK) { S.pile = nullptr; S.fetch = nullptr; return rc; } }
     if (gq) S.dps.assign(gq->dps, gq->dps + gq->n_dps);
     if ((want_text || gq || pile || fetch) && !c->s_text) HIPCHK(hipStreamCreateWithFlags(&c->s_text, hipStreamNonBlocking));
@@ -1739,6 +1815,13 @@ static int deep_rerun_text(vgl_ctx* c, vgl_ctx::HostSlot& S) {
         if (rc == VGL_OK) rc = vgl_ctx_check(c->deep, c->s_compute);
         if (rc != VGL_OK) return rc;                                 // (a draw beyond VGL_READ_CAP_MAX reads: VGL_E_CAPACITY after all)
     }
+    if (S.setal) {                                                   // relabelled again from the rerun's values
+        vgl_tile_out d;
+        memset(&d, 0, sizeof d);
+        for (int f = 0; f < N_FIELDS; f++) if (S.dev_fields >> f & 1u) *(void**)((char*)&d + FIELDS[f].off) = S.d_out[f];
+        const int r2 = enqueue_setal(c, S, S.site0, S.n_sites, d, c->s_compute);
+        if (r2 != VGL_OK) return r2;
+    }
     const int rc = S.gvcf ? enqueue_gvcf(c, S, S.n_sites) : S.text ? enqueue_text(c, S, S.n_sites) : VGL_OK;
     if (rc != VGL_OK) return rc;
     if (S.fetch) {                                                   // fetched again from the rerun's values: the first run's text is never delivered
@@ -1755,7 +1838,7 @@ static int deep_rerun_text(vgl_ctx* c, vgl_ctx::HostSlot& S) {
     if (S.gvcf) { const int r2 = copy_gvcf_small(c, S, S.n_sites, c->s_compute); if (r2 != VGL_OK) return r2; }
     HIPCHK(hipStreamSynchronize(c->s_compute));
     c->deep_runs++;
-    return VGL_OK;
+    return setal_rc(S);
 }
 
 // gVCF tile: counts into the caller's struct; the record text, then the block text behind it, cross the link (only the bytes produced)
@@ -1826,6 +1909,7 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
     } else {
         const int rc = flags_to_rc(c, *S.h_flag);
         if (rc != VGL_OK) return rc;
+        if ((rc2 = setal_rc(S)) != VGL_OK) return rc2;
         if (S.pile && (rc2 = finish_pileup(c, S)) != VGL_OK) return rc2;
     }
     if (S.fetch && (rc2 = finish_fetchgl(c, S)) != VGL_OK) return rc2;

@@ -1,0 +1,95 @@
+"""A prescribed REF/ALT list for every record, applied on the device (vgl_setal.hip; include/vcfgl_hip.h, "a prescribed REF/ALT list"):
+what the reference's misc/setAlleles does to a record file, done to a tile's arrays before any writer reads them.
+
+`read_tsv` reads the tool's allele file (one `REF<TAB>ALT[,ALT...]` line per record), `build_table` turns its lines into the 8-byte
+target entries of the ABI, `apply_into` runs the kernels on device tensors.  `Simulator.set_alleles(table)` relabels every tile of a
+simulator.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+
+LETTERS = "ACGT"
+UNOBSERVED = 4
+MAX_ALTS = 4
+NO_SITE = 0x7FFFFFFF
+
+
+def parse_line(line, nonref_name="<*>", where="line"):
+    """'A\\tC,<*>' -> (0, 1, 4).  nonref_name is the run's own spelling of the unobserved allele; the other spelling is an error."""
+    cols = line.rstrip("\r\n").split("\t")
+    if len(cols) != 2 or not cols[0] or not cols[1]:
+        raise ValueError("%s: expected REF<TAB>ALT[,ALT...]: %r" % (where, line))
+    names = [cols[0]] + cols[1].split(",")
+    if len(names) - 1 > MAX_ALTS:
+        raise ValueError("%s: more than %d ALT alleles: %r" % (where, MAX_ALTS, line))
+    codes = []
+    for nm in names:
+        if nm in LETTERS and len(nm) == 1:
+            c = LETTERS.index(nm)
+        elif nm == nonref_name:
+            c = UNOBSERVED
+        elif nm in ("<*>", "<NON_REF>"):
+            raise ValueError("%s: the unobserved allele of this run is spelled %s, not %s" % (where, nonref_name, nm))
+        else:
+            raise ValueError("%s: unknown allele %r (A, C, G, T or %s)" % (where, nm, nonref_name))
+        if c in codes:
+            raise ValueError("%s: allele %s is named twice: %r" % (where, nm, line))
+        codes.append(c)
+    return tuple(codes)
+
+
+def read_tsv(path, nonref_name="<*>"):
+    """the allele lists of the file, one tuple of codes (0 .. 4) per line"""
+    with open(path) as f:
+        return [parse_line(ln, nonref_name, "%s:%d" % (path, k + 1)) for k, ln in enumerate(f)]
+
+
+def build_table(targets):
+    """[(0, 1, 4), ...] -> int8 [n][8]: [count, a0 .. a4 (-1 behind the count), 0, 0]"""
+    t = np.zeros((len(targets), 8), np.int8)
+    t[:, 1:6] = -1
+    for i, codes in enumerate(targets):
+        codes = [int(c) for c in codes]
+        if not 2 <= len(codes) <= 5 or any(c < 0 or c > 4 for c in codes) or len(set(codes)) != len(codes):
+            raise ValueError("site %d: a target is 2 .. 5 distinct alleles of 0 .. 4: %r" % (i, codes))
+        t[i, 0] = len(codes)
+        t[i, 1:1 + len(codes)] = codes
+    return t
+
+
+def workspace_bytes(n_samples, n_sites, max_genotypes, lib=None):
+    lib = lib or _abi.load_library()
+    return lib.vgl_setal_workspace_bytes(n_samples, n_sites, max_genotypes)
+
+
+def apply_into(targets, site_status, n_alleles, alleles2acgt, n_samples, qs=None, fmt_dp=None, gl=None, pl=None, gp=None, pl_u8=None,
+               bad_site=None, workspace=None, max_genotypes=10, max_alleles=4, layout=_abi.VGL_LAYOUT_PLANES, stream=None, lib=None):
+    """Relabels one tile in place: device tensors targets (int8 [n_sites][8]), site_status / n_alleles (int32 [n_sites]), alleles2acgt
+    (int8 [n_sites][5]), and whichever of qs, gl, pl, gp, pl_u8 are given (pl_u8 needs fmt_dp).  Asynchronous on `stream`; returns
+    (bad_site, workspace): bad_site is an int32 tensor of one element, NO_SITE or the first refused site of the tile."""
+    import torch
+    lib = lib or _abi.load_library()
+    n_sites = int(site_status.numel())
+    d = site_status.device
+    if bad_site is None:
+        bad_site = torch.full((1,), NO_SITE, dtype=torch.int32, device=d)
+    need = lib.vgl_setal_workspace_bytes(n_samples, n_sites, max_genotypes)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=d)
+    want = {"qs": torch.float32, "fmt_dp": torch.int32, "gl": torch.float32, "pl": torch.int32, "gp": torch.float32, "pl_u8": torch.uint8}
+    given = {"qs": qs, "fmt_dp": fmt_dp, "gl": gl, "pl": pl, "gp": gp, "pl_u8": pl_u8}
+    for k, t in given.items():
+        if t is not None and t.dtype != want[k]:
+            raise ValueError("%s must be %s" % (k, want[k]))
+    if targets.dtype != torch.int8 or targets.numel() != n_sites * 8:
+        raise ValueError("targets is int8 [n_sites][8]")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    rc = lib.vgl_setal_apply_device(d.index or 0, n_samples, n_sites, max_genotypes, max_alleles, layout, targets.data_ptr(), site_status.data_ptr(),
+                                    n_alleles.data_ptr(), alleles2acgt.data_ptr(), ptr(qs), ptr(fmt_dp), ptr(gl), ptr(pl), ptr(gp), ptr(pl_u8),
+                                    bad_site.data_ptr(), workspace.data_ptr(), workspace.numel(), C.c_void_p(stream) if stream else None)
+    if rc != _abi.VGL_OK:
+        raise RuntimeError("vgl_setal_apply_device: %d: %s" % (rc, lib.vgl_last_error().decode()))
+    return bad_site, workspace

@@ -157,6 +157,21 @@ class Simulator:
         f = self.fetch_next(gt.shape[0], text_cap)
         return self.simulate(site0, gt, fields=fields), f
 
+    def set_alleles(self, table, first_site=0):
+        """vgl_ctx_set_alleles: every tile submitted by `simulate` from now on gets the REF/ALT list of its sites from `table` (what
+        misc/setAlleles does to the record file; vcfgl_amd.setalleles).  table: a list of allele-code tuples such as (0, 1, 4), or
+        the int8 [n][8] array of `setalleles.build_table`, for the absolute sites first_site, first_site + 1, ...; None switches
+        it off.  A site whose list names an allele the record does not have makes `simulate` raise VglError(VGL_E_SETAL)."""
+        if table is None:
+            self._check(self.lib.vgl_ctx_set_alleles(self.ctx, None, 0, 0))
+            return
+        from .setalleles import build_table
+        t = table if isinstance(table, np.ndarray) else build_table(table)
+        t = np.ascontiguousarray(t, dtype=np.int8)
+        if t.ndim != 2 or t.shape[1] != 8:
+            raise ValueError("table is int8 [n_sites][8]")
+        self._check(self.lib.vgl_ctx_set_alleles(self.ctx, t.ctypes.data, int(first_site), t.shape[0]))
+
     def close(self):
         if getattr(self, "ctx", None):
             self.lib.vgl_ctx_destroy(self.ctx)
