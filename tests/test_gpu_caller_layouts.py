@@ -1,6 +1,6 @@
 """vgl_params.layout is public ABI: a caller may pass its own block, off[4] and qs_read_stride (include/vcfgl_hip.h, vgl_rng_layout).
 The library derives from it k_sitebase's power table, the per-sample jump table, qs_read_tab (J^(stride r)), the 52-bit split
-stepping of k_sample<0>, k_redo, k_tail and the sibling context of the deep re-run (vgl_host.cpp, "rand48 addressing"); every other
+stepping of k_sample<0>, k_redo, k_tail and the sibling context of the deep re-run (vcfgl_amd/csrc/hostlib/plan.h, "rand48 addressing", and the jump tables of hostlib/tables.h); every other
 test runs these at the default layout only -- one stride (32) and one family of blocks.  Here every build that reads the layout in
 code of its own runs under caller layouts and must equal the oracle bit for bit (test_gpu_parity.assert_parity), at a small site0
 and within the last 100 sites the layout can address (vgl_rng_tile_max_sites).
