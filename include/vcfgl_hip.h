@@ -750,6 +750,53 @@ VGL_API int vgl_vcfin_host_submit(vgl_vcfin_host* h, const uint8_t* text, int64_
 VGL_API int vgl_vcfin_host_wait(vgl_vcfin_host* h, int32_t ticket, const uint8_t** gt, const int32_t** allelesum, const int32_t** status);
 VGL_API int vgl_vcfin_host_destroy(vgl_vcfin_host* h);
 
+/* ---- the FORMAT/GT vectors of BCF records decoded on the device (ABI 7, additive: the version stays 7) ------------------------------
+ * The counterpart of vgl_vcfin_* for the binary format; the host program's BCF reader is the specification.  A record's GT field is
+ * n_samples vectors of n values of one BCF integer type (1 = int8, 2 = int16, 3 = int32; little endian), back to back: its slice of
+ * n_samples * n * width bytes starts at gt_begin, at any alignment.  Values are sign-extended; E is the type's end-of-vector value
+ * (0x81, 0x8001, 0x80000001), M its missing value (0x80, 0x8000, 0x80000000).  Per sample, from its first two values v0, v1 (later
+ * values do not matter):
+ *      a0 = -1 if v0 == E, else (v0 >> 1) - 1;    a1 = a0 if n == 1 or v1 == E;  a1 = -1 if v0 == E;  else a1 = (v1 >> 1) - 1
+ *   plain record  the type is 1, 2 or 3, n >= 1, n_alleles is in 1 .. 5 (allele_map has five entries), and every used value -- v0,
+ *                 and v1 when n >= 2 and v0 != E -- is E or a value >= 0 whose allele index is below n_alleles.  The record gets status
+ *                 VGL_BCFIN_OK, gt_out[record][s] = (b1 << 4) | b0 with b = allele_map[record][a] & 0xF (0xF for a == -1), and
+ *                 allelesum_out[record] = the sum of the non-negative a.
+ *   any other     M, another negative value, an allele index >= n_alleles, a type that is no integer type, n < 1, n_alleles outside
+ *                 1 .. 5: status VGL_BCFIN_HOST, the record's row and sum are unspecified and the caller decodes the record itself.
+ * The kernel reads no byte outside a record's slice and writes no byte outside its row, whatever the bytes hold.
+ *   vgl_bcfin_workspace_bytes  bytes of device workspace vgl_bcfin_decode_device needs (-1 for bad arguments).  Pure host arithmetic.
+ *   vgl_bcfin_decode_device    every pointer is device memory of `device`: gt [gt_bytes], gt_begin (int64), gt_type, gt_n and n_alleles
+ *                              (int32) per record, allele_map int8 [n_records][5].  The slices of the records with an integer type and
+ *                              n >= 1 are compared with gt_bytes by a small kernel whose one word the call waits for: gt_begin < 0 or
+ *                              gt_begin + n_samples * n * width > gt_bytes returns VGL_E_ARG before the decoder is launched (which
+ *                              clamps all the same).  The decode itself is enqueued on `hip_stream` and not waited for.
+ *   vgl_bcfin_host_create      for a program without HIP of its own: batches of records from host memory, decoded on `device`, with
+ *                              page-locked staging and device buffers owned by the handle for two batches of at most max_records
+ *                              records and max_gt_bytes bytes of GT slices each, on one stream.
+ *   vgl_bcfin_host_submit      src [src_bytes] is host memory that holds the records (a whole file, say) and gt_begin the offsets of
+ *                              their GT slices in it; ONLY the slices are copied into the handle's staging, back to back -- what lies
+ *                              between them is not sent up.  Enqueues copy, decode and copy back and returns at once with a ticket:
+ *                              one batch is on the device while the caller prepares the next.  A third submit before a wait fails with
+ *                              VGL_E_ARG, and so does a slice outside src or slices of more than max_gt_bytes (nothing is enqueued).
+ *   vgl_bcfin_host_wait        blocks until the ticket's results are in host memory: gt [n_records][n_samples], allelesum [n_records],
+ *                              status [n_records], owned by the handle and valid until the second submit after this one.  A ticket is
+ *                              waited for once (VGL_E_ARG otherwise).
+ * No HIP device: VGL_E_NODEVICE from vgl_bcfin_decode_device and vgl_bcfin_host_create. */
+#define VGL_BCFIN_OK    0
+#define VGL_BCFIN_HOST  1
+typedef struct vgl_bcfin_host vgl_bcfin_host;
+VGL_API int64_t vgl_bcfin_workspace_bytes(int32_t n_samples, int32_t n_records);
+VGL_API int vgl_bcfin_decode_device(int32_t device, const uint8_t* gt, int64_t gt_bytes, int32_t n_records, const int64_t* gt_begin,
+                                    const int32_t* gt_type, const int32_t* gt_n, const int32_t* n_alleles, const int8_t* allele_map,
+                                    int32_t n_samples, uint8_t* gt_out, int32_t* allelesum_out, int32_t* status_out, void* workspace,
+                                    void* hip_stream);
+VGL_API int vgl_bcfin_host_create(int32_t device, int32_t n_samples, int32_t max_records, int64_t max_gt_bytes, vgl_bcfin_host** out);
+VGL_API int vgl_bcfin_host_submit(vgl_bcfin_host* h, const uint8_t* src, int64_t src_bytes, int32_t n_records, const int64_t* gt_begin,
+                                  const int32_t* gt_type, const int32_t* gt_n, const int32_t* n_alleles, const int8_t* allele_map,
+                                  int32_t* ticket);
+VGL_API int vgl_bcfin_host_wait(vgl_bcfin_host* h, int32_t ticket, const uint8_t** gt, const int32_t** allelesum, const int32_t** status);
+VGL_API int vgl_bcfin_host_destroy(vgl_bcfin_host* h);
+
 /* ---- BGZF input inflated on the device (ABI 7, additive: the version stays 7) -------------------------------------------------------
  * The counterpart of vgl_bgzf_compress_device: a BGZF stream (SAMv1 4.1: independent gzip members of at most 64 KiB, each with its
  * size in a 'BC' extra subfield) is inflated one member per workgroup, RFC 1951 complete (stored, fixed and dynamic blocks, any

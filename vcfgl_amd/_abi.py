@@ -107,11 +107,15 @@ EXPORTS = [
     "vgl_fetchgl_bound", "vgl_fetchgl_workspace_bytes", "vgl_fetchgl_format_device",
     "vgl_ctx_fetchgl", "vgl_ctx_fetchgl_bound", "vgl_ctx_fetchgl_next",
     "vgl_setal_workspace_bytes", "vgl_setal_apply_device", "vgl_ctx_set_alleles",
+    "vgl_bcfin_workspace_bytes", "vgl_bcfin_decode_device",
+    "vgl_bcfin_host_create", "vgl_bcfin_host_submit", "vgl_bcfin_host_wait", "vgl_bcfin_host_destroy",
 ]
 # value modes of the fetch-GL formatter (VGL_FETCHGL_*): the simulated float, or the float its VCF text reads back as
 FETCHGL_FLOAT, FETCHGL_TEXT = 0, 1
 # status of a line from the device parser (VGL_VCFIN_*): parsed, or left to the caller's own parser
 VCFIN_OK, VCFIN_HOST = 0, 1
+# status of a BCF record from the device's GT decoder (VGL_BCFIN_*): decoded, or left to the caller's own decoder
+BCFIN_OK, BCFIN_HOST = 0, 1
 # status of a BGZF member from the device inflater (VGL_INFLATE_*): inflated to its exact end, or left to the caller's own inflater
 INFLATE_OK, INFLATE_HOST = 0, 1
 # cells of the discordance table (VGL_DISC_*): cell[sample][6][128] by GQ, callmis[sample], sites[2]
@@ -319,6 +323,15 @@ def load_library(hooks=False):
     lib.vgl_setal_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.vgl_setal_apply_device.argtypes = [C.c_int32] * 6 + [C.c_void_p] * 12 + [C.c_int64, C.c_void_p]
     lib.vgl_ctx_set_alleles.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+    lib.vgl_bcfin_workspace_bytes.restype = C.c_int64
+    lib.vgl_bcfin_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.vgl_bcfin_decode_device.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vgl_bcfin_host_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]
+    lib.vgl_bcfin_host_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.c_int32)]
+    lib.vgl_bcfin_host_wait.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.vgl_bcfin_host_destroy.argtypes = [C.c_void_p]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

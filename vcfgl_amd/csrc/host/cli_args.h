@@ -26,6 +26,7 @@ struct Args {
     std::string set_alleles_fn;        // --set-alleles FILE: every record gets the REF/ALT list of its line (misc/setAlleles), relabelled on the device
     int device_inflate = 0;            // --device-inflate 1: a BGZF input is inflated on the first device of the run
     int device_input = 0;              // --device-input 1: the sample columns of the input VCF text parsed on the first device of the run
+    int device_bcf_input = 0;          // --device-bcf-input 1: the GT vectors of the input BCF's records decoded on the first device of the run
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -106,6 +107,13 @@ static const char USAGE[] =
     "                   --tile-sites lines and one packed byte per sample comes back.  A line outside the plain grammar (GT alleles of '.' or\n"
     "                   one or two digits, at most two of them) is parsed by the host as with 0.  Same output either way; VCF text input only\n"
     "                   (BCF input is refused), refused with --depth inf; a run without a GPU fails instead of falling back]\n"
+    "                   --device-bcf-input 0|1 [0: the genotypes of a BCF input are decoded on one host thread; 1: on the first GPU of --device /\n"
+    "                   --devices: the host reads the header, walks the records, decodes their shared blocks on the --encode-threads threads\n"
+    "                   and finds each record's GT values, only those bytes go up in batches of --tile-sites records and one packed byte per\n"
+    "                   sample comes back.  A record with a missing-value sentinel, a negative value or an allele index beyond its alleles is\n"
+    "                   decoded by the host as with 0, and a damaged file is read by the host as with 0.  Same output either way (-printTruth 1\n"
+    "                   builds its GT text on the host as before); BCF input only, raw or BGZF (works with --device-inflate 1), refused with\n"
+    "                   --depth inf; a run without a GPU fails instead of falling back]\n"
     "                   --device-inflate 0|1 [0: the input is read and inflated by zlib on one host thread; 1: a BGZF input (bgzip'd VCF text, compressed\n"
     "                   BCF) is read as it lies in the file and its members are inflated on the first GPU of --device / --devices, 512 members\n"
     "                   a batch.  A file that is not BGZF (plain text, gzip) and a file with a member the device does not take to its exact end\n"
@@ -204,6 +212,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--set-alleles") a.set_alleles_fn = v;
         else if (f == "--device-input") a.device_input = I(v);
         else if (f == "--device-inflate") a.device_inflate = I(v);
+        else if (f == "--device-bcf-input") a.device_bcf_input = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -256,6 +265,8 @@ static Args parse_args(int argc, char** argv) {
     }
     range(a.device_input, 0, 1, "--device-input");
     if (a.device_input == 1 && a.depth_inf) die("--device-input 1 is not supported with --depth inf (no device is used).");
+    range(a.device_bcf_input, 0, 1, "--device-bcf-input");
+    if (a.device_bcf_input == 1 && a.depth_inf) die("--device-bcf-input 1 is not supported with --depth inf (no device is used).");
     range(a.device_inflate, 0, 1, "--device-inflate");
     if (a.device_inflate == 1 && a.depth_inf) die("--device-inflate 1 is not supported with --depth inf (no device is used).");
     if (a.device_stream == 1 && a.depth_inf) die("--device-stream 1 is not supported with --depth inf (no tile is simulated).");

@@ -124,6 +124,10 @@ static void verbose_report(const Args& a, const RunPlan& P, const std::vector<vg
     fprintf(stderr, "[input] --device-input %d: %ld lines parsed on the device, %ld of them again on the host, %.3f GB of text sent up; file read %.3f s, line scan %.3f s, fixed columns %.3f s, device parse and wait %.3f s, host %s %.3f s\n",
             a.device_input, in_stats.lines_dev, a.device_input ? in_stats.lines_host : 0L, in_stats.text_up / 1e9, in_stats.t_read, in_stats.t_scan, in_stats.t_fixed,
             in_stats.t_dev, a.device_input ? "re-parse" : "parse", in_stats.t_host);
+    if (a.device_bcf_input)
+        fprintf(stderr, "[input] --device-bcf-input 1: %ld records decoded on the device, %ld of them again on the host, %.3f GB of genotype bytes sent up; %s%s; header and record chain %.3f s, shared blocks %.3f s, device decode and wait %.3f s, host GT loop %.3f s\n",
+                in_stats.bcf_dev, in_stats.bcf_host, in_stats.gt_up / 1e9, in_stats.bcf_fallback ? "the host read the file: " : "no fallback",
+                in_stats.bcf_fallback ? in_stats.bcf_fallback : "", in_stats.bt_scan, in_stats.bt_shared, in_stats.bt_dev, in_stats.bt_host);
     if (!a.device_inflate) fprintf(stderr, "[input] --device-inflate 0: the host read the file (zlib)\n");
     else fprintf(stderr, "[input] --device-inflate 1: %ld members inflated on the device, %lld compressed bytes sent up, %lld inflated bytes received, %s%s; inflate stage %.3f s of file read %.3f s\n",
                  in_stats.members_dev, (long long)in_stats.inflate_up, (long long)in_stats.inflate_down, in_stats.fallback ? "the host read the file (zlib): " : "no fallback",

@@ -44,12 +44,15 @@ static int run_hook(int argc, char** argv) {
         return 0;
     }
     if (argc == 5 && !strcmp(argv[1], "--dump-gt")) {
-        // test hook of the input parser: --dump-gt <file> <source 0|1> <device-input 0|1> prints per record line "pos status allelesum row":
+        // test hook of the input parser: --dump-gt <file> <source 0|1> <mode 0|1|2|3> prints per record line "pos status allelesum row":
         // the row make_site hands to the tile calls in hex, the status of the line (VGL_VCFIN_*: 1 = outside the device parser's plain
-        // grammar), through the host parser (0, no GPU needed) or the device parser (1)
+        // grammar), through the host parser (0, no GPU needed) or the device parser (1).  For a BCF file: 2 decodes its GT vectors on the
+        // device (--device-bcf-input 1), 3 on the host with the status the device would give (VGL_BCFIN_*, from the shared per-sample
+        // rule; no GPU needed); with 0 a BCF record has no status (-1)
         Args a; a.source = atoi(argv[3]);
-        InputOpt opt; opt.device_input = atoi(argv[4]); opt.source = a.source; opt.classify = true; opt.tile_sites = 256;
-        if (a.source < 0 || a.source > 1 || opt.device_input < 0 || opt.device_input > 1) die("--dump-gt <file> <source 0|1> <device-input 0|1>");
+        const int mode = atoi(argv[4]);
+        if (a.source < 0 || a.source > 1 || mode < 0 || mode > 3) die("--dump-gt <file> <source 0|1> <mode 0|1|2|3>");
+        InputOpt opt; opt.device_input = mode == 1; opt.device_bcf_input = mode == 2; opt.source = a.source; opt.classify = true; opt.classify_bcf = mode == 3; opt.tile_sites = 256;
         Vcf vcf = read_vcf(argv[2], false, 4, opt);
         const int N = (int)vcf.samples.size();
         if (N <= 0) die("no samples in %s", argv[2]);

@@ -1,7 +1,9 @@
 // vcf_input.h -- input side of the host program: VCF text, gzip / bgzip'd VCF or BCF (raw or BGZF) -> Vcf; --device-input 1 and
-// --device-inflate 1 hand the sample columns / the BGZF members to the first device of the run
+// --device-inflate 1 hand the sample columns / the BGZF members to the first device of the run, --device-bcf-input 1 the GT vectors of BCF records
 #pragma once
+#include <atomic>
 #include "cli_args.h"
+#include "../vgl_bcfin_core.h"
 
 // ---------------------------------------------------------------------------------------
 struct Rec {
@@ -11,21 +13,26 @@ struct Rec {
     std::vector<int8_t> gt;            // 2 per sample, allele index or -1
     std::vector<std::string> gt_str;   // GT tokens as written in the input (for -printTruth)
     char ref_char;
-    const uint8_t* dev_row = nullptr;  // --device-input 1: the packed row the device parsed (Vcf::gt_rows), gt stays empty
+    const uint8_t* dev_row = nullptr;  // --device-input 1 / --device-bcf-input 1: the packed row the device made (Vcf::gt_rows), gt stays empty
     int32_t dev_sum = 0;               //                   and its allele sum
-    int8_t in_status = -1;             // --dump-gt: VGL_VCFIN_OK / VGL_VCFIN_HOST of the line
+    int8_t in_status = -1;             // --dump-gt: VGL_VCFIN_OK / VGL_VCFIN_HOST of the line (VGL_BCFIN_* of a BCF record)
 };
 
 // --device-input: how read_vcf is to parse the sample columns, and what it did (the [input] line of --verbose 1)
 struct InputOpt {
     int device_input = 0, source = 0, device = 0, tile_sites = 4096; bool classify = false;
     int device_inflate = 0;                                  // --device-inflate 1: a BGZF file's members are inflated on `device`
+    int device_bcf_input = 0;                                // --device-bcf-input 1: the GT vectors of BCF records are decoded on `device`
+    bool classify_bcf = false;                               // --dump-gt FILE SOURCE 3: read_bcf also notes the status the device would give each record
     std::function<vgl_inflate_host*()> inflater;            // the host object, created beside the file read (waits for its creation; dies without a device)
 };
 struct InputStats {
     double t_read = 0, t_scan = 0, t_fixed = 0, t_dev = 0, t_host = 0; long lines_dev = 0, lines_host = 0; int64_t text_up = 0;
     // --device-inflate 1: members inflated on the device, compressed bytes sent up, inflated bytes received, why zlib read the file after all
     long members_dev = 0; int64_t inflate_up = 0, inflate_down = 0; const char* fallback = nullptr; double t_inflate = 0;
+    // --device-bcf-input 1: records decoded on the device, those of them decoded again on the host, GT bytes sent up, why read_bcf read the
+    // file after all; header and record chain, shared blocks, device decode and wait, host GT loop
+    long bcf_dev = 0, bcf_host = 0; int64_t gt_up = 0; const char* bcf_fallback = nullptr; double bt_scan = 0, bt_shared = 0, bt_dev = 0, bt_host = 0;
 };
 
 struct Vcf {
@@ -33,35 +40,41 @@ struct Vcf {
     std::vector<std::string> samples;
     std::map<std::string, long> contig_len;
     std::vector<Rec> recs;
-    std::vector<uint8_t> gt_rows;      // --device-input 1: one row of packed true genotypes per record line (Rec::dev_row points here)
+    std::vector<uint8_t> gt_rows;      // --device-input 1 / --device-bcf-input 1: one row of packed true genotypes per record (Rec::dev_row points here)
 };
 
 // ---------------------------------------------------------------------------------------
 // BCF 2.x input (raw or BGZF; zlib reads the gzip members): header text, then records decoded back
 // into the same Rec the text reader fills -- QUAL / FILTER / INFO as VCF text, GT as allele indices.
+// The reader is four parts -- bcf_header, bcf_scan_record, bcf_shared, bcf_formats (+ bcf_gt) -- that read_bcf calls back to back
+// and --device-bcf-input 1 calls apart (read_bcf_device).
+struct BcfSoftFail {};                 // what a soft cursor throws where a hard one exits
+struct BcfDict { std::map<int, std::string> dict, contig; std::map<std::string, int> info_is_flag; };
+// a cursor over the file's bytes (it owns nothing: one per thread)
 struct BcfIn {
-    std::vector<uint8_t> buf; size_t off = 0;
-    std::map<int, std::string> dict, contig; std::map<std::string, int> info_is_flag;
-    uint32_t u32() { if (off + 4 > buf.size()) die("truncated BCF record"); uint32_t v; memcpy(&v, &buf[off], 4); off += 4; return v; }
+    const uint8_t* buf = nullptr; size_t size = 0, off = 0;
+    bool soft = false;                 // --device-bcf-input 1 looks at the file before it decides who reads it: nothing exits
+    template <class... A> [[noreturn]] void fail(const char* fmt, A... a) const { if (soft) throw BcfSoftFail(); die(fmt, a...); }
+    uint32_t u32() { if (off + 4 > size) fail("truncated BCF record"); uint32_t v; memcpy(&v, buf + off, 4); off += 4; return v; }
     void typed(int& type, int& n) {
-        if (off >= buf.size()) die("truncated BCF record");
+        if (off >= size) fail("truncated BCF record");
         const uint8_t b = buf[off++]; type = b & 15; n = b >> 4;
-        if (n == 15) { int t2, n2; typed(t2, n2); std::vector<int32_t> v; ints(t2, n2, v); if (v.empty() || v[0] < 0) die("bad BCF vector length"); n = v[0]; }
+        if (n == 15) { int t2, n2; typed(t2, n2); std::vector<int32_t> v; ints(t2, n2, v); if (v.empty() || v[0] < 0) fail("bad BCF vector length"); n = v[0]; }
     }
     void ints(int type, int n, std::vector<int32_t>& out) {          // missing -> INT32_MIN, end-of-vector -> INT32_MIN + 1
         const int w = type == 1 ? 1 : type == 2 ? 2 : type == 3 ? 4 : 0;
-        if (!w) die("BCF: integer vector expected (type %d)", type);
-        if (off + (size_t)w * n > buf.size()) die("truncated BCF record");
+        if (!w) fail("BCF: integer vector expected (type %d)", type);
+        if (off + (size_t)w * n > size) fail("truncated BCF record");
         out.clear();
         for (int i = 0; i < n; i++, off += w) {
             int32_t v;
             if (w == 1) { const int8_t x = (int8_t)buf[off]; v = x == -128 ? INT32_MIN : x == -127 ? INT32_MIN + 1 : x; }
-            else if (w == 2) { int16_t x; memcpy(&x, &buf[off], 2); v = x == -32768 ? INT32_MIN : x == -32767 ? INT32_MIN + 1 : x; }
-            else memcpy(&v, &buf[off], 4);
+            else if (w == 2) { int16_t x; memcpy(&x, buf + off, 2); v = x == -32768 ? INT32_MIN : x == -32767 ? INT32_MIN + 1 : x; }
+            else memcpy(&v, buf + off, 4);
             out.push_back(v);
         }
     }
-    std::string str(int n) { if (off + n > buf.size()) die("truncated BCF record"); std::string r((const char*)&buf[off], n); off += n; return r; }
+    std::string str(int n) { if (off + n > size) fail("truncated BCF record"); std::string r((const char*)buf + off, n); off += n; return r; }
     static std::string attr(const std::string& h, const char* key) {
         const std::string k = std::string(key) + "=";
         size_t a = h.find("<" + k); if (a == std::string::npos) a = h.find("," + k); if (a == std::string::npos) return "";
@@ -69,19 +82,23 @@ struct BcfIn {
         return h.substr(a, h.find_first_of(",>", a) - a);
     }
 };
+// where a record lies: its shared block (behind the two lengths), its per-sample block, the next record
+struct BcfRecAt { size_t shared = 0, shared_end = 0, rec_end = 0; };
+// where a record's GT values lie: N vectors of n values of BCF type `type`, from offset `begin` of the file's bytes
+struct BcfGtAt { int64_t begin = -1; int type = 0, n = 0; };
 
-static Vcf read_bcf(std::vector<uint8_t>&& raw, bool keep_gt_text) {
-    BcfIn in; in.buf = std::move(raw);
-    if (in.buf.size() < 9 || memcmp(in.buf.data(), "BCF\2", 4) != 0) die("not a BCF2 file");
+// part 1: the header -> the dictionaries, Vcf::header / samples / contig_len; the cursor is left at the first record
+static void bcf_header(BcfIn& in, BcfDict& d, Vcf& v) {
+    if (in.size < 9 || memcmp(in.buf, "BCF\2", 4) != 0) in.fail("not a BCF2 file");
     in.off = 5;
     const uint32_t l_text = in.u32();
-    if (in.off + l_text > in.buf.size()) die("truncated BCF header");
-    std::string text((const char*)&in.buf[in.off], l_text); in.off += l_text;
+    if (in.off + l_text > in.size) in.fail("truncated BCF header");
+    std::string text((const char*)in.buf + in.off, l_text); in.off += l_text;
     while (!text.empty() && (text.back() == '\0' || text.back() == '\n')) text.pop_back();
-    Vcf v; std::vector<std::string> lines, f; split(text, '\n', lines);
+    std::vector<std::string> lines, f; split(text, '\n', lines);
     int nd = 0, nc = 0; bool have_pass = false;
     for (const std::string& h : lines) if (h.compare(0, 10, "##FILTER=<") == 0 && BcfIn::attr(h, "ID") == "PASS") have_pass = true;
-    if (!have_pass) { in.dict[0] = "PASS"; nd = 1; }
+    if (!have_pass) { d.dict[0] = "PASS"; nd = 1; }
     for (const std::string& h : lines) {
         if (h.compare(0, 2, "##") != 0) { if (!h.empty() && h[0] == '#') { split(h, '\t', f); for (size_t i = 9; i < f.size(); i++) v.samples.push_back(f[i]); } continue; }
         v.header.push_back(h);
@@ -91,76 +108,126 @@ static Vcf read_bcf(std::vector<uint8_t>&& raw, bool keep_gt_text) {
         const std::string id = BcfIn::attr(h, "ID"), idx_s = BcfIn::attr(h, "IDX");
         if (ctg) {
             const int idx = idx_s.empty() ? nc : atoi(idx_s.c_str());
-            in.contig[idx] = id; nc = std::max(nc, idx + 1);
+            d.contig[idx] = id; nc = std::max(nc, idx + 1);
             const std::string len = BcfIn::attr(h, "length"); v.contig_len[id] = len.empty() ? -1 : atol(len.c_str());
             continue;
         }
         int idx = -1;
-        for (auto& kv : in.dict) if (kv.second == id) idx = kv.first;
+        for (auto& kv : d.dict) if (kv.second == id) idx = kv.first;
         if (idx < 0) idx = idx_s.empty() ? nd : atoi(idx_s.c_str());
-        in.dict[idx] = id; nd = std::max(nd, idx + 1);
-        if (inf) in.info_is_flag[id] = BcfIn::attr(h, "Type") == "Flag";
+        d.dict[idx] = id; nd = std::max(nd, idx + 1);
+        if (inf) d.info_is_flag[id] = BcfIn::attr(h, "Type") == "Flag";
     }
-    const size_t N = v.samples.size();
+}
+
+// part 2: the two lengths in front of a record; the cursor is left at the shared block
+static void bcf_scan_record(BcfIn& in, BcfRecAt& at) {
+    const uint32_t l_shared = in.u32(), l_indiv = in.u32();
+    at.shared = in.off; at.shared_end = in.off + l_shared; at.rec_end = in.off + (size_t)l_shared + l_indiv;
+    if (at.rec_end > in.size) in.fail("truncated BCF record");
+}
+
+// part 3: the shared block at the cursor -> Rec; n_fmt = the number of FORMAT fields that follow
+static void bcf_shared(BcfIn& in, const BcfDict& d, const BcfRecAt& at, const size_t N, Rec& r, int& n_fmt) {
     std::vector<int32_t> iv; int type, n;
-    while (in.off < in.buf.size()) {
-        const uint32_t l_shared = in.u32(), l_indiv = in.u32();
-        const size_t rec_end = in.off + (size_t)l_shared + l_indiv, shared_end = in.off + l_shared;
-        if (rec_end > in.buf.size()) die("truncated BCF record");
-        Rec r;
-        const int32_t chrom = (int32_t)in.u32(); r.pos0 = (int32_t)in.u32(); (void)in.u32();
-        const uint32_t qual = in.u32(), nai = in.u32(), nfs = in.u32();
-        const int n_allele = nai >> 16, n_info = nai & 0xFFFF, n_fmt = nfs >> 24; const size_t n_sample = nfs & 0xFFFFFF;
-        if (!in.contig.count(chrom)) die("BCF record with an undefined contig index %d", chrom);
-        if (n_sample != N) die("Record at position %ld has %zu samples, the header names %zu samples.", r.pos0 + 1, n_sample, N);
-        r.chrom = in.contig[chrom];
-        if (qual == VGL_FLOAT_MISSING_BITS) r.qual = "."; else { float q; memcpy(&q, &qual, 4); put_float(r.qual, q); }
-        in.typed(type, n); r.id = (type == 7) ? in.str(n) : "."; if (r.id.empty()) r.id = ".";
-        for (int i = 0; i < n_allele; i++) { in.typed(type, n); if (type != 7) die("BCF: allele string expected"); r.alleles.push_back(in.str(n)); }
-        if (r.alleles.empty() || r.alleles[0].empty()) die("Empty REF at position %ld.", r.pos0 + 1);
-        r.ref_char = r.alleles[0][0];
+    const int32_t chrom = (int32_t)in.u32(); r.pos0 = (int32_t)in.u32(); (void)in.u32();
+    const uint32_t qual = in.u32(), nai = in.u32(), nfs = in.u32();
+    const int n_allele = nai >> 16, n_info = nai & 0xFFFF; const size_t n_sample = nfs & 0xFFFFFF;
+    n_fmt = nfs >> 24;
+    const auto ctg = d.contig.find(chrom);
+    if (ctg == d.contig.end()) in.fail("BCF record with an undefined contig index %d", chrom);
+    if (n_sample != N) in.fail("Record at position %ld has %zu samples, the header names %zu samples.", r.pos0 + 1, n_sample, N);
+    r.chrom = ctg->second;
+    if (qual == VGL_FLOAT_MISSING_BITS) r.qual = "."; else { float q; memcpy(&q, &qual, 4); put_float(r.qual, q); }
+    in.typed(type, n); r.id = (type == 7) ? in.str(n) : "."; if (r.id.empty()) r.id = ".";
+    for (int i = 0; i < n_allele; i++) { in.typed(type, n); if (type != 7) in.fail("BCF: allele string expected"); r.alleles.push_back(in.str(n)); }
+    if (r.alleles.empty() || r.alleles[0].empty()) in.fail("Empty REF at position %ld.", r.pos0 + 1);
+    r.ref_char = r.alleles[0][0];
+    in.typed(type, n);
+    if (type == 0 || n == 0) r.filt = ".";
+    else { in.ints(type, n, iv); for (size_t i = 0; i < iv.size(); i++) { if (i) r.filt += ';'; const auto k = d.dict.find(iv[i]); if (k == d.dict.end()) in.fail("BCF: undefined FILTER index"); r.filt += k->second; } }
+    for (int i = 0; i < n_info; i++) {
+        in.typed(type, n); in.ints(type, n, iv);
+        const auto k = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
+        if (k == d.dict.end()) in.fail("BCF: undefined INFO key");
+        if (!r.info.empty()) r.info += ';';
+        r.info += k->second;
         in.typed(type, n);
-        if (type == 0 || n == 0) r.filt = "."; else { in.ints(type, n, iv); for (size_t i = 0; i < iv.size(); i++) { if (i) r.filt += ';'; if (!in.dict.count(iv[i])) die("BCF: undefined FILTER index"); r.filt += in.dict[iv[i]]; } }
-        for (int i = 0; i < n_info; i++) {
-            in.typed(type, n); in.ints(type, n, iv);
-            if (iv.empty() || !in.dict.count(iv[0])) die("BCF: undefined INFO key");
-            const std::string key = in.dict[iv[0]];
-            if (!r.info.empty()) r.info += ';';
-            r.info += key;
-            in.typed(type, n);
-            if (type == 0 || n == 0) continue;                              // flag
-            r.info += '=';
-            if (type == 7) r.info += in.str(n);
-            else if (type == 5) { for (int k = 0; k < n; k++) { const uint32_t b = in.u32(); if (b == 0x7F800002u) continue; if (k) r.info += ','; float x; memcpy(&x, &b, 4); put_float(r.info, x); } }
-            else { in.ints(type, n, iv); bool first = true; for (int32_t x : iv) { if (x == INT32_MIN + 1) continue; if (!first) r.info += ','; first = false; put_int(r.info, x); } }
+        if (type == 0 || n == 0) continue;                              // flag
+        r.info += '=';
+        if (type == 7) r.info += in.str(n);
+        else if (type == 5) { for (int j = 0; j < n; j++) { const uint32_t b = in.u32(); if (b == 0x7F800002u) continue; if (j) r.info += ','; float x; memcpy(&x, &b, 4); put_float(r.info, x); } }
+        else { in.ints(type, n, iv); bool first = true; for (int32_t x : iv) { if (x == INT32_MIN + 1) continue; if (!first) r.info += ','; first = false; put_int(r.info, x); } }
+    }
+    if (r.info.empty()) r.info = ".";
+    if (in.off != at.shared_end) in.fail("BCF record: shared block length mismatch at position %ld", r.pos0 + 1);
+}
+
+// part 4: the GT vectors of N samples at the cursor (n values of `type` each) -> Rec::gt (and the tokens as -printTruth writes them)
+static void bcf_gt(BcfIn& in, const int type, const int n, const size_t N, const bool keep_gt_text, Rec& r) {
+    std::vector<int32_t> iv;
+    for (size_t s = 0; s < N; s++) {
+        in.ints(type, n, iv);
+        int8_t a[2] = {-1, -1}; std::string txt;
+        for (int j = 0; j < n && iv[j] != INT32_MIN + 1; j++) {
+            const int al = (iv[j] >> 1) - 1;
+            if (j < 2) a[j] = (int8_t)al;
+            if (keep_gt_text) { if (j) txt += (iv[j] & 1) ? '|' : '/'; if (al < 0) txt += '.'; else { char t[16]; snprintf(t, sizeof t, "%d", al); txt += t; } }
         }
-        if (r.info.empty()) r.info = ".";
-        if (in.off != shared_end) die("BCF record: shared block length mismatch at position %ld", r.pos0 + 1);
-        bool have_gt = false;
-        r.gt.assign(2 * N, -1);
-        for (int k = 0; k < n_fmt; k++) {
-            in.typed(type, n); in.ints(type, n, iv);
-            if (iv.empty() || !in.dict.count(iv[0])) die("BCF: undefined FORMAT key");
-            const bool is_gt = in.dict[iv[0]] == "GT";
-            in.typed(type, n);
-            const size_t w = type == 1 ? 1 : type == 2 ? 2 : (type == 3 || type == 5) ? 4 : type == 7 ? 1 : 0;
-            if (!is_gt) { if (in.off + w * n * N > in.buf.size()) die("truncated BCF record"); in.off += w * n * N; continue; }
-            have_gt = true;
-            for (size_t s = 0; s < N; s++) {
-                in.ints(type, n, iv);
-                int8_t a[2] = {-1, -1}; std::string txt;
-                for (int j = 0; j < n && iv[j] != INT32_MIN + 1; j++) {
-                    const int al = (iv[j] >> 1) - 1;
-                    if (j < 2) a[j] = (int8_t)al;
-                    if (keep_gt_text) { if (j) txt += (iv[j] & 1) ? '|' : '/'; if (al < 0) txt += '.'; else { char t[16]; snprintf(t, sizeof t, "%d", al); txt += t; } }
-                }
-                if (n == 1 || (n >= 2 && iv[1] == INT32_MIN + 1)) a[1] = a[0];     // haploid call: both alleles, as the text reader does
-                r.gt[2 * s] = a[0]; r.gt[2 * s + 1] = a[1];
-                if (keep_gt_text) r.gt_str.push_back(txt.empty() ? "." : txt);
-            }
+        if (n == 1 || (n >= 2 && iv[1] == INT32_MIN + 1)) a[1] = a[0];     // haploid call: both alleles, as the text reader does
+        r.gt[2 * s] = a[0]; r.gt[2 * s + 1] = a[1];
+        if (keep_gt_text) r.gt_str.push_back(txt.empty() ? "." : txt);
+    }
+}
+
+// the n_fmt FORMAT fields at the cursor: GT is decoded into Rec::gt where it stands (decode) or only found; the others are skipped.
+// where = the last GT field's values
+static void bcf_formats(BcfIn& in, const BcfDict& d, const size_t N, const int n_fmt, const bool decode, const bool keep_gt_text, Rec& r, BcfGtAt& where) {
+    std::vector<int32_t> iv; int type, n;
+    bool have_gt = false;
+    if (decode) r.gt.assign(2 * N, -1);
+    for (int k = 0; k < n_fmt; k++) {
+        in.typed(type, n); in.ints(type, n, iv);
+        const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
+        if (key == d.dict.end()) in.fail("BCF: undefined FORMAT key");
+        const bool is_gt = key->second == "GT";
+        in.typed(type, n);
+        const size_t w = type == 1 ? 1 : type == 2 ? 2 : (type == 3 || type == 5) ? 4 : type == 7 ? 1 : 0;
+        if (!is_gt) { if (in.off + w * n * N > in.size) in.fail("truncated BCF record"); in.off += w * n * N; continue; }
+        if (!decode && have_gt) in.fail("BCF: a second GT field");                       // (soft cursors only: the hard reader decodes both)
+        have_gt = true;
+        where.begin = (int64_t)in.off; where.type = type; where.n = n;
+        if (decode) { bcf_gt(in, type, n, N, keep_gt_text, r); continue; }
+        // found only: what decoding N vectors would exit on is a failure here too
+        if (N > 0 && (type < 1 || type > 3)) in.fail("BCF: integer vector expected (type %d)", type);
+        if (in.off + w * n * N > in.size) in.fail("truncated BCF record");
+        in.off += w * n * N;
+    }
+    if (!have_gt) in.fail("Could not find GT tag at position %ld.", r.pos0 + 1);
+}
+
+static bool allele_table(const Rec& r, const int source, int8_t ra[5]);
+
+// classify_source >= 0 (--dump-gt FILE SOURCE 3): every record also gets the status the device decoder would give it, from the shared
+// per-sample rule (vgl_bcfin_core.h) on the host
+static Vcf read_bcf(std::vector<uint8_t>&& raw, bool keep_gt_text, const int classify_source = -1) {
+    BcfDict d; BcfIn in; in.buf = raw.data(); in.size = raw.size();
+    Vcf v;
+    bcf_header(in, d, v);
+    const size_t N = v.samples.size();
+    std::vector<uint8_t> row(classify_source >= 0 ? N : 0);
+    while (in.off < in.size) {
+        BcfRecAt at; BcfGtAt gt; int n_fmt;
+        bcf_scan_record(in, at);
+        Rec r;
+        bcf_shared(in, d, at, N, r, n_fmt);
+        bcf_formats(in, d, N, n_fmt, true, keep_gt_text, r, gt);
+        if (classify_source >= 0) {
+            int8_t ra[5]; int32_t sum;
+            r.in_status = (int8_t)(allele_table(r, classify_source, ra)
+                                       ? vgl_bcfin::record(in.buf + gt.begin, gt.type, gt.n, (int)r.alleles.size(), ra, (int64_t)N, row.data(), &sum) : VGL_BCFIN_HOST);
         }
-        if (!have_gt) die("Could not find GT tag at position %ld.", r.pos0 + 1);
-        in.off = rec_end;
+        in.off = at.rec_end;
         v.recs.push_back(std::move(r));
     }
     return v;
@@ -349,6 +416,106 @@ static void parse_lines_device(const uint8_t* raw, const std::vector<std::pair<c
     st.t_host = now_s() - t0;
 }
 
+// --device-bcf-input 1: the header and the l_shared / l_indiv chain on one thread, then per record on `threads` host threads the shared
+// block -> Rec and a walk over the FORMAT field headers that finds GT's values; only those slices are copied into the staging
+// (vgl_bcfin_host_*: the other FORMAT fields never cross the link), in batches of at most tile_sites records, batch b submitted before
+// batch b - 1 is retired.  Rows go to Vcf::gt_rows / Rec::dev_row / dev_sum, which make_site copies.  A record the device hands back
+// (VGL_BCFIN_HOST) or whose alleles allele_table refuses gets the host's own GT loop, bcf_gt -- the exits of make_site stay what they
+// are.  false, with the reason in st.bcf_fallback and v as it was, when the file holds anything read_bcf exits on (or a second GT field,
+// or more records than an int counts): read_bcf then reads the whole file, so that its messages and their order are those of
+// --device-bcf-input 0.
+static bool read_bcf_device(const std::vector<uint8_t>& raw, const bool keep_gt_text, const int threads, const InputOpt& opt, Vcf& v, InputStats& st) {
+    double t0 = now_s();
+    BcfDict d; BcfIn in; in.buf = raw.data(); in.size = raw.size(); in.soft = true;
+    std::vector<BcfRecAt> at;
+    auto give_up = [&](const char* why) { v = Vcf(); st.bcf_fallback = why; return false; };
+    try {
+        bcf_header(in, d, v);
+        while (in.off < in.size) { BcfRecAt a; bcf_scan_record(in, a); at.push_back(a); in.off = a.rec_end; }
+    } catch (const BcfSoftFail&) { return give_up("the header or the chain of record lengths is damaged"); }
+    const size_t N = v.samples.size();
+    if (N == 0 || N > (size_t)INT32_MAX) return give_up("the header names no sample");
+    if (at.size() > (size_t)INT32_MAX) return give_up("more records than one run counts");
+    const int n = (int)at.size();
+    st.bt_scan = now_s() - t0; t0 = now_s();
+    v.recs.resize((size_t)n);
+    std::vector<BcfGtAt> gt((size_t)n);
+    std::vector<int8_t> amap((size_t)n * 5);
+    std::vector<uint8_t> sent((size_t)n, 0);
+    std::atomic<bool> failed(false);
+    vsink::parallel_for(n, threads, [&](int i) {
+        if (failed.load(std::memory_order_relaxed)) return;
+        BcfIn c = in; c.off = at[i].shared;
+        Rec& r = v.recs[i];
+        try { int n_fmt; bcf_shared(c, d, at[i], N, r, n_fmt); bcf_formats(c, d, N, n_fmt, false, false, r, gt[i]); }
+        catch (const BcfSoftFail&) { failed.store(true, std::memory_order_relaxed); return; }
+        sent[i] = allele_table(r, opt.source, &amap[(size_t)i * 5]) ? 1 : 0;
+    });
+    if (failed.load()) return give_up("a record holds what the host reader exits on");
+    st.bt_shared = now_s() - t0; t0 = now_s();
+    auto slice_bytes = [&](int i) { const int w = vgl_bcfin::width(gt[i].type); return (w && gt[i].n >= 1) ? (int64_t)N * gt[i].n * w : (int64_t)0; };
+    const int TS = std::max(1, opt.tile_sites);
+    const int nb = (n + TS - 1) / TS;
+    struct Batch { std::vector<int> idx; int64_t bytes = 0; };      // the sent records among TS consecutive ones, and their GT bytes
+    std::vector<Batch> batches((size_t)nb);
+    int64_t max_bytes = 1; int max_recs = 1;
+    for (int b = 0; b < nb; b++) {
+        Batch& B = batches[b];
+        for (int i = b * TS; i < std::min(n, (b + 1) * TS); i++) if (sent[i]) { B.idx.push_back(i); B.bytes += slice_bytes(i); }
+        max_bytes = std::max(max_bytes, B.bytes); max_recs = std::max(max_recs, (int)B.idx.size());
+    }
+    v.gt_rows.resize((size_t)n * N);
+    std::vector<int> again;                                          // records whose GT the host decodes: handed back, or never sent
+    for (int i = 0; i < n; i++) if (!sent[i]) again.push_back(i);
+    vgl_bcfin_host* h = nullptr;
+    if (vgl_bcfin_host_create(opt.device, (int32_t)N, max_recs, max_bytes, &h) != VGL_OK) die("--device-bcf-input 1: %s", vgl_last_error());
+    std::vector<int64_t> bb[2]; std::vector<int32_t> bt[2], bn[2], ba[2]; std::vector<int8_t> bm[2];
+    int32_t ticket[2] = {-1, -1};
+    auto submit = [&](int b) {
+        const Batch& B = batches[b]; const int k = b & 1; const size_t m = B.idx.size();
+        bb[k].resize(m); bt[k].resize(m); bn[k].resize(m); ba[k].resize(m); bm[k].resize(m * 5);
+        for (size_t j = 0; j < m; j++) {
+            const int i = B.idx[j];
+            bb[k][j] = gt[i].begin; bt[k][j] = gt[i].type; bn[k][j] = gt[i].n; ba[k][j] = (int32_t)v.recs[i].alleles.size(); memcpy(&bm[k][j * 5], &amap[(size_t)i * 5], 5);
+        }
+        if (vgl_bcfin_host_submit(h, raw.data(), (int64_t)raw.size(), (int32_t)m, bb[k].data(), bt[k].data(), bn[k].data(), ba[k].data(), bm[k].data(), &ticket[k]) != VGL_OK)
+            die("--device-bcf-input 1: %s", vgl_last_error());
+        st.gt_up += B.bytes; st.bcf_dev += (long)m;
+    };
+    auto retire = [&](int b) {
+        const Batch& B = batches[b];
+        const uint8_t* rows; const int32_t* sums; const int32_t* status;
+        if (vgl_bcfin_host_wait(h, ticket[b & 1], &rows, &sums, &status) != VGL_OK) die("--device-bcf-input 1: %s", vgl_last_error());
+        for (size_t j = 0; j < B.idx.size(); j++) {
+            const int i = B.idx[j];
+            if (status[j] != VGL_BCFIN_OK) { again.push_back(i); st.bcf_host++; continue; }
+            uint8_t* dst = &v.gt_rows[(size_t)i * N];
+            memcpy(dst, rows + j * N, N);
+            v.recs[i].dev_row = dst; v.recs[i].dev_sum = sums[j]; v.recs[i].in_status = VGL_BCFIN_OK;
+        }
+    };
+    for (int b = 0; b < nb; b++) { submit(b); if (b > 0) retire(b - 1); }
+    if (nb > 0) retire(nb - 1);
+    vgl_bcfin_host_destroy(h);
+    st.bt_dev = now_s() - t0; t0 = now_s();
+    // today's loop for the records left to the host; with -printTruth 1 also for the others: the GT tokens are built on the host as
+    // with --device-bcf-input 0 (the flag does not make that faster)
+    BcfIn hard = in; hard.soft = false;
+    vsink::parallel_for((int)again.size(), threads, [&](int k) {
+        const int i = again[k]; Rec& r = v.recs[i];
+        BcfIn c = hard; c.off = (size_t)gt[i].begin;
+        r.gt.assign(2 * N, -1); bcf_gt(c, gt[i].type, gt[i].n, N, keep_gt_text, r); r.in_status = VGL_BCFIN_HOST;
+    });
+    if (keep_gt_text) vsink::parallel_for(n, threads, [&](int i) {
+        Rec& r = v.recs[i];
+        if (!r.dev_row) return;
+        BcfIn c = hard; c.off = (size_t)gt[i].begin;
+        r.gt.assign(2 * N, -1); bcf_gt(c, gt[i].type, gt[i].n, N, true, r); r.gt.clear(); r.gt.shrink_to_fit();
+    });
+    st.bt_host = now_s() - t0;
+    return true;
+}
+
 // keep_gt_text: the GT tokens as written are needed only by -printTruth.  The (decompressed) file is read whole,
 // the header lines are taken in order and the record lines are parsed on `threads` threads.
 // --device-inflate 1: the file as it lies on the disk, its members listed by vgl_bgzf_index and inflated on the device in batches of
@@ -422,9 +589,16 @@ static Vcf read_vcf(const std::string& fn, bool keep_gt_text, int threads, const
     if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) {
         if (opt.device_input) die("--device-input 1 is not supported with BCF input (its genotypes are binary already: there is no text to parse).");
         st.t_read = now_s() - t0;
+        if (opt.device_bcf_input) {
+            Vcf v;
+            const bool done = read_bcf_device(raw, keep_gt_text, threads, opt, v, st);
+            if (stats) *stats = st;
+            if (done) return v;
+        }
         if (stats) *stats = st;
-        return read_bcf(std::move(raw), keep_gt_text);
+        return read_bcf(std::move(raw), keep_gt_text, opt.classify_bcf ? opt.source : -1);
     }
+    if (opt.device_bcf_input) die("--device-bcf-input 1 needs BCF input (the genotype columns of VCF text are what --device-input 1 parses).");
     st.t_read = now_s() - t0; t0 = now_s();
     Vcf v;
     std::vector<std::string> f;
@@ -500,7 +674,7 @@ static Vcf read_input(const Args& a, const int threads, InputStats& stats) {
         if (inflater_rc != VGL_OK || !inflater) die("--device-inflate 1: %s", inflater_err.c_str());
         return inflater;
     };
-    in_opt.device_input = a.device_input; in_opt.source = a.source; in_opt.device = warm_dev; in_opt.tile_sites = a.tile_sites > 0 ? a.tile_sites : 4096;
+    in_opt.device_input = a.device_input; in_opt.device_bcf_input = a.device_bcf_input; in_opt.source = a.source; in_opt.device = warm_dev; in_opt.tile_sites = a.tile_sites > 0 ? a.tile_sites : 4096;
     Vcf vcf = read_vcf(a.in_fn, a.print_truth != 0, threads, in_opt, &stats);
     if (hip_warm.joinable()) hip_warm.join();
     if (inflater) vgl_inflate_host_destroy(inflater);

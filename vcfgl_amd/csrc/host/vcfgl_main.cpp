@@ -79,11 +79,13 @@ int main(int argc, char** argv) {
     const int hook_rc = run_hook(argc, argv);
     if (hook_rc != NOT_A_HOOK) return hook_rc;
     Args a = parse_args(argc, argv);
-    if (a.device_input) {                                       // (checked before any file of the run exists, the .arg file included)
+    if (a.device_input || a.device_bcf_input) {                 // (checked before any file of the run exists, the .arg file included)
         gzFile fp = gzopen(a.in_fn.c_str(), "r"); char magic[3] = {0, 0, 0};
         if (!fp) die("Could not open file: %s", a.in_fn.c_str());
         const int k = gzread(fp, magic, 3); gzclose(fp);
-        if (k == 3 && !memcmp(magic, "BCF", 3)) die("--device-input 1 is not supported with BCF input (its genotypes are binary already: there is no text to parse).");
+        const bool bcf = k == 3 && !memcmp(magic, "BCF", 3);
+        if (a.device_input && bcf) die("--device-input 1 is not supported with BCF input (its genotypes are binary already: there is no text to parse).");
+        if (a.device_bcf_input && !bcf) die("--device-bcf-input 1 needs BCF input (the genotype columns of VCF text are what --device-input 1 parses).");
     }
     const std::vector<int8_t> setal_table = a.set_alleles_fn.empty() ? std::vector<int8_t>() : read_set_alleles(a);   // (a bad file: before any file of the run exists)
     RunLog runlog; runlog.open(a);
