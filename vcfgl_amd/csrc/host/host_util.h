@@ -41,6 +41,12 @@ static std::atomic<bool> g_dying{false};
 
 static double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
+// Batches through a handle that holds two at a time (vgl_*_host_*): submit 0; submit 1, retire 0; ...; retire the last
+template <typename Submit, typename Retire> static void two_in_flight(int64_t n_batches, Submit submit, Retire retire) {
+    for (int64_t b = 0; b < n_batches; b++) { submit(b); if (b > 0) retire(b - 1); }
+    if (n_batches > 0) retire(n_batches - 1);
+}
+
 static void split(const std::string& s, char c, std::vector<std::string>& out) {
     out.clear(); size_t b = 0;
     while (true) { size_t e = s.find(c, b); if (e == std::string::npos) { out.push_back(s.substr(b)); break; } out.push_back(s.substr(b, e - b)); b = e + 1; }

@@ -399,8 +399,7 @@ static void parse_lines_device(const uint8_t* raw, const std::vector<std::pair<c
             v.recs[i].dev_row = dst; v.recs[i].dev_sum = sums[j]; v.recs[i].in_status = VGL_VCFIN_OK;
         }
     };
-    for (int b = 0; b < nb; b++) { submit(b); if (b > 0) retire(b - 1); }
-    if (nb > 0) retire(nb - 1);
+    two_in_flight(nb, submit, retire);
     vgl_vcfin_host_destroy(h);
     st.t_dev = now_s() - t0; t0 = now_s();
     st.lines_host = (long)again.size();
@@ -494,8 +493,7 @@ static bool read_bcf_device(const std::vector<uint8_t>& raw, const bool keep_gt_
             v.recs[i].dev_row = dst; v.recs[i].dev_sum = sums[j]; v.recs[i].in_status = VGL_BCFIN_OK;
         }
     };
-    for (int b = 0; b < nb; b++) { submit(b); if (b > 0) retire(b - 1); }
-    if (nb > 0) retire(nb - 1);
+    two_in_flight(nb, submit, retire);
     vgl_bcfin_host_destroy(h);
     st.bt_dev = now_s() - t0; t0 = now_s();
     // today's loop for the records left to the host; with -printTruth 1 also for the others: the GT tokens are built on the host as
@@ -558,9 +556,7 @@ static bool inflate_on_device(const std::string& fn, const InputOpt& opt, std::v
             die("--device-inflate 1: %s", vgl_last_error());
         st.inflate_up += hi - lo;
     };
-    if (n_batches > 0) submit(0);
-    for (int64_t b = 0; b < n_batches; b++) {
-        if (b + 1 < n_batches) submit(b + 1);
+    auto retire = [&](int64_t b) {
         const uint8_t* out; int64_t out_n; const int32_t* status;
         if (vgl_inflate_host_wait(h, ticket[b & 1], &out, &out_n, &status) != VGL_OK) die("--device-inflate 1: %s", vgl_last_error());
         const int64_t m0 = b * INFLATE_BATCH, m1 = std::min(n, m0 + INFLATE_BATCH);
@@ -568,7 +564,8 @@ static bool inflate_on_device(const std::string& fn, const InputOpt& opt, std::v
         if (out_at + out_n > total) die("--device-inflate 1: a batch returned more bytes than its members' ISIZE fields hold");
         if (out_n > 0) memcpy(raw.data() + out_at, out, (size_t)out_n);
         out_at += out_n; st.inflate_down += out_n; st.members_dev += (long)(m1 - m0);
-    }
+    };
+    two_in_flight(n_batches, submit, retire);
     st.t_inflate = now_s() - t0;
     if (!ok) { st.fallback = "a member was left to the host (VGL_INFLATE_HOST)"; raw.clear(); return false; }
     return true;

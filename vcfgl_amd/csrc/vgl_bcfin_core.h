@@ -55,6 +55,13 @@ VGL_HD uint32_t map_word(const int8_t* allele_map) {
     return m;
 }
 
+// does the slice of a record with an integer type and n >= 1 lie inside the bytes?  (w = 0 or n < 1: nothing is read, nothing to check)
+VGL_HD bool slice_ok(const int64_t begin, const int w, const int32_t n, const int64_t N, const int64_t gt_bytes) {
+    if (w == 0 || n < 1) return true;
+    if (begin < 0 || begin > gt_bytes) return false;
+    return (gt_bytes - begin) / (N * w) >= (int64_t)n;                 // (N * w <= 2^33: no overflow, whatever n is)
+}
+
 // can a record of this GT type, n values per sample and n_alleles be plain at all?
 VGL_HD bool describable(const int type, const int n, const int n_alleles) { return width(type) != 0 && n >= 1 && n_alleles >= 1 && n_alleles <= 5; }
 

@@ -549,87 +549,3 @@ extern "C" int vgl_bgzf_compress_device(int32_t device, const uint8_t* src, int6
     if (hipGetLastError() != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_compress_device: a launch failed");
     return VGL_OK;
 }
-
-// ---- host batches (vgl_bgzf_host_*): what a program without HIP of its own (the host program) uses -------------------------------
-struct vgl_bgzf_host {
-    int device = 0;
-    int64_t cap = 0, ws_bytes = 0;
-    hipStream_t st = nullptr, cp = nullptr;                 // compression; copies of finished batches back to the host
-    void* ws = nullptr;
-    int64_t* d_n = nullptr; int64_t* h_n = nullptr;
-    struct Slot { uint8_t* d_in = nullptr; uint8_t* d_out = nullptr; uint8_t* h_out = nullptr; int64_t n = 0; hipEvent_t done = nullptr; bool busy = false; } s[2];
-    int next = 0;
-};
-
-extern "C" int vgl_bgzf_host_destroy(vgl_bgzf_host* h) {
-    if (!h) return VGL_OK;
-    (void)hipSetDevice(h->device);
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    if (h->cp) (void)hipStreamSynchronize(h->cp);
-    for (auto& S : h->s) {
-        if (S.d_in) (void)hipFree(S.d_in);
-        if (S.d_out) (void)hipFree(S.d_out);
-        if (S.h_out) (void)hipHostFree(S.h_out);
-        if (S.done) (void)hipEventDestroy(S.done);
-    }
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->d_n) (void)hipFree(h->d_n);
-    if (h->h_n) (void)hipHostFree(h->h_n);
-    if (h->st) (void)hipStreamDestroy(h->st);
-    if (h->cp) (void)hipStreamDestroy(h->cp);
-    delete h;
-    return VGL_OK;
-}
-
-extern "C" int vgl_bgzf_host_create(int32_t device, int64_t max_batch, vgl_bgzf_host** out) {
-    if (!out || max_batch <= 0) return vgl_pack_set_error(VGL_E_ARG, "vgl_bgzf_host_create: bad argument");
-    *out = nullptr;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_create: no HIP device is available");
-    if (device < 0 || device >= nd) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_create: no such device");
-    if (hipSetDevice(device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_create: hipSetDevice failed");
-    vgl_bgzf_host* h = new vgl_bgzf_host;
-    h->device = device; h->cap = max_batch; h->ws_bytes = vgl_bgzf_workspace_bytes(max_batch);
-    const int64_t out_cap = vgl_bgzf_bound(max_batch);
-    bool ok = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&h->cp, hipStreamNonBlocking) == hipSuccess &&
-              hipMalloc(&h->ws, (size_t)h->ws_bytes) == hipSuccess && hipMalloc((void**)&h->d_n, 2 * sizeof(int64_t)) == hipSuccess &&
-              hipHostMalloc((void**)&h->h_n, 2 * sizeof(int64_t), hipHostMallocDefault) == hipSuccess;
-    for (auto& S : h->s)
-        ok = ok && hipMalloc((void**)&S.d_in, (size_t)max_batch) == hipSuccess && hipMalloc((void**)&S.d_out, (size_t)out_cap) == hipSuccess &&
-             hipHostMalloc((void**)&S.h_out, (size_t)out_cap, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&S.done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { vgl_bgzf_host_destroy(h); return vgl_pack_set_error(VGL_E_NOMEM, "vgl_bgzf_host_create: device or page-locked memory could not be allocated"); }
-    *out = h;
-    return VGL_OK;
-}
-
-extern "C" int vgl_bgzf_host_submit(vgl_bgzf_host* h, const uint8_t* src, int64_t n, int32_t* ticket) {
-    if (!h || !ticket || n < 0 || n > h->cap || (n > 0 && !src)) return vgl_pack_set_error(VGL_E_ARG, "vgl_bgzf_host_submit: bad argument");
-    const int k = h->next;
-    auto& S = h->s[k];
-    if (S.busy) return vgl_pack_set_error(VGL_E_ARG, "vgl_bgzf_host_submit: two batches are in flight (vgl_bgzf_host_wait the older one first)");
-    if (hipSetDevice(h->device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_submit: hipSetDevice failed");
-    if (n > 0 && hipMemcpyAsync(S.d_in, src, (size_t)n, hipMemcpyHostToDevice, h->st) != hipSuccess)
-        return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_submit: copy to the device failed");
-    const int rc = vgl_bgzf_compress_device(h->device, S.d_in, n, S.d_out, vgl_bgzf_bound(h->cap), h->d_n + k, h->ws, h->ws_bytes, h->st);
-    if (rc != VGL_OK) return rc;
-    if (hipMemcpyAsync(h->h_n + k, h->d_n + k, sizeof(int64_t), hipMemcpyDeviceToHost, h->st) != hipSuccess || hipEventRecord(S.done, h->st) != hipSuccess)
-        return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_submit: enqueue failed");
-    S.n = n; S.busy = true;
-    *ticket = k;
-    h->next = k ^ 1;
-    return VGL_OK;
-}
-
-extern "C" int vgl_bgzf_host_wait(vgl_bgzf_host* h, int32_t ticket, const uint8_t** out, int64_t* out_n) {
-    if (!h || ticket < 0 || ticket > 1 || !out || !out_n || !h->s[ticket].busy) return vgl_pack_set_error(VGL_E_ARG, "vgl_bgzf_host_wait: bad ticket");
-    auto& S = h->s[ticket];
-    if (hipSetDevice(h->device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_wait: hipSetDevice failed");
-    if (hipEventSynchronize(S.done) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_wait: the compression failed");   // (not the stream: the next batch may run behind it)
-    const int64_t m = h->h_n[ticket];
-    if (m < 0 || m > vgl_bgzf_bound(S.n)) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_wait: compressed size out of range");
-    if (m > 0 && (hipMemcpyAsync(S.h_out, S.d_out, (size_t)m, hipMemcpyDeviceToHost, h->cp) != hipSuccess || hipStreamSynchronize(h->cp) != hipSuccess))
-        return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_bgzf_host_wait: copy back failed");
-    S.busy = false;
-    *out = S.h_out; *out_n = m;
-    return VGL_OK;
-}

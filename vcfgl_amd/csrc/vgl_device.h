@@ -268,6 +268,22 @@ struct VglSerialState {
     uint64_t st_hts;         // htslib's private rand48 stream (hts_drand48), consumed by errmod_cal()'s shuffle at depth > 255
 };
 
+// arguments of k_vcfin_parse, k_bcfin_decode and k_inflate_member (all pointers are device memory)
+struct VglVcfinArgs {
+    const uint8_t* text; int64_t text_bytes; int32_t n_lines, N;
+    const int64_t* line_begin; const int64_t* line_end; const int32_t* gti; const int32_t* n_alleles; const int8_t* allele_map;
+    uint8_t* gt_out; int32_t* allelesum_out; int32_t* status_out;
+};
+struct VglBcfinArgs {
+    const uint8_t* gt; int64_t gt_bytes; int32_t n_records, N;
+    const int64_t* gt_begin; const int32_t* gt_type; const int32_t* gt_n; const int32_t* n_alleles; const int8_t* allele_map;
+    uint8_t* gt_out; int32_t* allelesum_out; int32_t* status_out;
+};
+struct VglInflateArgs {
+    const uint8_t* src; int64_t src_bytes, n_members;
+    const int64_t* begin; const int32_t* csize; const int64_t* out_off; const int32_t* isize;
+    uint8_t* dst; int64_t dst_cap; int32_t* status;
+};
 
 #ifdef __cplusplus
 extern "C" {
@@ -287,6 +303,10 @@ int vgl_launch_fused(const VglDevParams* p, const VglTilePtrs* t, void* stream);
 int vgl_launch_hts_offsets(const VglDevParams* p, const VglTilePtrs* t, struct VglSerialState* st, long long* hts_off, uint64_t* hts_base, void* stream);
 int vgl_launch_scout(const VglDevParams* p, const VglTilePtrs* t, struct VglSerialState* st, void* stream);
 int vgl_launch_sample_serial(const VglDevParams* p, const VglTilePtrs* t, void* stream);
+// vgl_vcfin.hip / vgl_bcfin.hip / vgl_inflate.hip: the kernel alone, for a caller that has checked the ranges on the host (hostlib/batch.h).  0 or -1
+int vgl_launch_vcfin_parse(const struct VglVcfinArgs* a, void* stream);
+int vgl_launch_bcfin_decode(const struct VglBcfinArgs* a, void* stream);
+int vgl_launch_inflate_members(const struct VglInflateArgs* a, void* stream);
 // vgl_betachain.hip
 int vgl_chain_read_offsets(const int32_t* sdp, long long n, long long* roff, long long* total, void* stream);
 long long vgl_chain_snapshots_needed(long long n_words);

@@ -7,6 +7,7 @@
 // One translation unit (static linkage, hidden visibility and inlining span all of it), written as the units of hostlib/:
 //   err.h          the last error text, HIPCHK, the environment hooks
 //   mem.h          owners of device / pinned memory, streams and events
+//   batch.h        the host batches (vgl_bgzf / stream / vcfin / inflate / bcfin _host_*) on those owners
 //   tables.h       the constant tables, built on the host (pure)
 //   plan.h         argument validation and the launch plan (pure)
 //   ctx.h          the context: create, destroy, info, timing
@@ -22,14 +23,17 @@
 
 #include <algorithm>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../../include/vcfgl_hip.h"
 #include "vgl_device.h"
 #include "vgl_inflate_core.h"
+#include "vgl_bcfin_core.h"
 
 #include "hostlib/err.h"
 #include "hostlib/mem.h"
+#include "hostlib/batch.h"
 #include "hostlib/tables.h"
 #include "hostlib/plan.h"
 #include "hostlib/ctx.h"

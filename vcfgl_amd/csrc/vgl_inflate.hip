@@ -1,5 +1,5 @@
-// vgl_inflate.hip -- BGZF input inflated on the device (ABI 7 additions: vgl_inflate_workspace_bytes, vgl_inflate_members_device,
-// vgl_inflate_host_*).  The counterpart of vgl_bgzf.hip: BGZF members are independent gzip members of at most 64 KiB of output, so
+// vgl_inflate.hip -- BGZF input inflated on the device (ABI 7 additions: vgl_inflate_workspace_bytes, vgl_inflate_members_device;
+// vgl_inflate_host_* in hostlib/batch.h launches k_inflate_member through vgl_launch_inflate_members).  The counterpart of vgl_bgzf.hip: BGZF members are independent gzip members of at most 64 KiB of output, so
 // every member is decoded by a workgroup of its own with its output window in LDS.  zlib's inflate is the specification; a member
 // the decoder does not take to its exact end (ISIZE bytes, the trailer's CRC32, the data ending where the trailer begins) gets the
 // status VGL_INFLATE_HOST and the caller inflates it itself.  Nothing is guessed on the device.
@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include "../../include/vcfgl_hip.h"
+#include "vgl_device.h"
 #include "vgl_crc32.hip.h"
 #include "vgl_inflate_core.h"
 
@@ -39,11 +40,7 @@ constexpr int64_t WS_BYTES = 256;          // the flag word of k_inflate_check
 
 __constant__ CrcShifts c_crc_shift = make_crc_shifts();
 
-struct InflateArgs {
-    const uint8_t* src; int64_t src_bytes, n_members;
-    const int64_t* begin; const int32_t* csize; const int64_t* out_off; const int32_t* isize;
-    uint8_t* dst; int64_t dst_cap; int32_t* status;
-};
+using InflateArgs = VglInflateArgs;
 
 __device__ __forceinline__ bool range_bad(const InflateArgs& A, const int64_t b, const int32_t c, const int64_t o, const int32_t n) {
     return b < 0 || c < 0 || b > A.src_bytes || (int64_t)c > A.src_bytes - b || n < 0 || n > 65536 || o < 0 || o > A.dst_cap || (int64_t)n > A.dst_cap - o;
@@ -115,13 +112,13 @@ __global__ void __launch_bounds__(NT) k_inflate_member(const InflateArgs A) {
     }
 }
 
-int launch_members(const InflateArgs& A, hipStream_t st) {
-    const int64_t g = A.n_members < GRID_MAX ? A.n_members : GRID_MAX;
-    hipLaunchKernelGGL(k_inflate_member, dim3((unsigned)g), dim3(NT), 0, st, A);
+}  // namespace
+
+extern "C" int vgl_launch_inflate_members(const VglInflateArgs* a, void* stream) {
+    const int64_t g = a->n_members < GRID_MAX ? a->n_members : GRID_MAX;
+    hipLaunchKernelGGL(k_inflate_member, dim3((unsigned)g), dim3(NT), 0, (hipStream_t)stream, *a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-
-}  // namespace
 
 extern "C" int vgl_pack_set_error(int code, const char* msg);       // vgl_host.cpp: records the message for vgl_last_error()
 
@@ -154,114 +151,6 @@ extern "C" int vgl_inflate_members_device(int32_t device, const uint8_t* src, in
         return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_members_device: the argument check failed to run");
     if (h_flag) return vgl_pack_set_error(VGL_E_ARG, "vgl_inflate_members_device: a member's range lies outside the buffers (0 <= begin, begin + csize <= src_bytes, "
                                                       "0 <= isize <= 65536, 0 <= out_off, out_off + isize <= dst_cap)");
-    if (launch_members(A, st) != 0) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_members_device: the launch failed");
-    return VGL_OK;
-}
-
-// ---- host batches (vgl_inflate_host_*): what a program without HIP of its own (the host program) uses ---------------------------
-struct vgl_inflate_host {
-    int device = 0; int32_t max_members = 0;
-    hipStream_t st = nullptr;
-    struct Slot {
-        uint8_t* h_in = nullptr; uint8_t* d_in = nullptr;          // the members, then begin / out_off (int64) and csize / isize (int32): one copy up
-        uint8_t* h_out = nullptr; uint8_t* d_out = nullptr;        // the inflated bytes, then the statuses: one copy down
-        int32_t n = 0; int64_t out_bytes = 0, off_status = 0; hipEvent_t done = nullptr; bool busy = false;
-    } s[2];
-    int next = 0;
-    int64_t in_bytes = 0, out_bytes = 0;                           // capacity of h_in / d_in and of h_out / d_out
-};
-
-static int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
-extern "C" int vgl_inflate_host_destroy(vgl_inflate_host* h) {
-    if (!h) return VGL_OK;
-    (void)hipSetDevice(h->device);
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    for (auto& S : h->s) {
-        if (S.d_in) (void)hipFree(S.d_in);
-        if (S.d_out) (void)hipFree(S.d_out);
-        if (S.h_in) (void)hipHostFree(S.h_in);
-        if (S.h_out) (void)hipHostFree(S.h_out);
-        if (S.done) (void)hipEventDestroy(S.done);
-    }
-    if (h->st) (void)hipStreamDestroy(h->st);
-    delete h;
-    return VGL_OK;
-}
-
-extern "C" int vgl_inflate_host_create(int32_t device, int32_t max_members, vgl_inflate_host** out) {
-    if (!out || max_members <= 0 || max_members > (1 << 20)) return vgl_pack_set_error(VGL_E_ARG, "vgl_inflate_host_create: bad argument");
-    *out = nullptr;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_host_create: no HIP device is available");
-    if (device < 0 || device >= nd) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_host_create: no such device");
-    if (hipSetDevice(device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_host_create: hipSetDevice failed");
-    vgl_inflate_host* h = new vgl_inflate_host;
-    h->device = device; h->max_members = max_members;
-    const int64_t M = max_members;
-    h->in_bytes = up256(M * 65536) + 2 * up256(M * 8) + 2 * up256(M * 4);       // (a member is at most 65536 bytes either way)
-    h->out_bytes = up256(M * 65536) + up256(M * 4);
-    bool ok = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess;
-    for (auto& S : h->s)
-        ok = ok && hipMalloc((void**)&S.d_in, (size_t)h->in_bytes) == hipSuccess && hipMalloc((void**)&S.d_out, (size_t)h->out_bytes) == hipSuccess &&
-             hipHostMalloc((void**)&S.h_in, (size_t)h->in_bytes, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&S.h_out, (size_t)h->out_bytes, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&S.done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { vgl_inflate_host_destroy(h); return vgl_pack_set_error(VGL_E_NOMEM, "vgl_inflate_host_create: device or page-locked memory could not be allocated"); }
-    *out = h;
-    return VGL_OK;
-}
-
-extern "C" int vgl_inflate_host_submit(vgl_inflate_host* h, const uint8_t* src, int64_t src_bytes, int32_t n_members, const int64_t* begin,
-                                       const int32_t* csize, const int32_t* isize, int32_t* ticket) {
-    if (!h || !ticket || n_members < 0 || n_members > h->max_members || src_bytes < 0 || (n_members > 0 && (!src || !begin || !csize || !isize)))
-        return vgl_pack_set_error(VGL_E_ARG, "vgl_inflate_host_submit: bad argument");
-    int64_t in_sum = 0, out_sum = 0;
-    for (int32_t i = 0; i < n_members; i++) {
-        if (begin[i] < 0 || csize[i] < 0 || csize[i] > 65536 || begin[i] > src_bytes || csize[i] > src_bytes - begin[i] || isize[i] < 0 || isize[i] > 65536)
-            return vgl_pack_set_error(VGL_E_ARG, "vgl_inflate_host_submit: a member's range lies outside src, or its csize or isize is not in 0 .. 65536");
-        in_sum += csize[i]; out_sum += isize[i];
-    }
-    const int k = h->next;
-    auto& S = h->s[k];
-    if (S.busy) return vgl_pack_set_error(VGL_E_ARG, "vgl_inflate_host_submit: two batches are in flight (vgl_inflate_host_wait the older one first)");
-    if (hipSetDevice(h->device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_host_submit: hipSetDevice failed");
-    S.n = n_members; S.out_bytes = out_sum;
-    if (n_members > 0) {
-        // the members are packed back to back into the staging, their arrays behind them: one copy up; bytes and statuses: one copy down.
-        // Once something is enqueued a failure waits for the stream: the staging is read by it
-        const int64_t L = n_members;
-        const int64_t o_b = up256(in_sum), o_o = o_b + up256(L * 8), o_c = o_o + up256(L * 8), o_i = o_c + up256(L * 4);
-        const int64_t in_used = o_i + L * 4;
-        S.off_status = up256(out_sum);
-        const int64_t out_used = S.off_status + L * 4;
-        int64_t* sb = (int64_t*)(S.h_in + o_b); int64_t* so = (int64_t*)(S.h_in + o_o);
-        int64_t at = 0, oat = 0;
-        for (int32_t i = 0; i < n_members; i++) {
-            memcpy(S.h_in + at, src + begin[i], (size_t)csize[i]);
-            sb[i] = at; so[i] = oat; at += csize[i]; oat += isize[i];
-        }
-        memcpy(S.h_in + o_c, csize, (size_t)L * 4); memcpy(S.h_in + o_i, isize, (size_t)L * 4);
-        auto fail = [&](const char* msg) { (void)hipStreamSynchronize(h->st); return vgl_pack_set_error(VGL_E_NODEVICE, msg); };
-        if (hipMemcpyAsync(S.d_in, S.h_in, (size_t)in_used, hipMemcpyHostToDevice, h->st) != hipSuccess) return fail("vgl_inflate_host_submit: copy to the device failed");
-        const InflateArgs A{S.d_in, in_sum, n_members, (const int64_t*)(S.d_in + o_b), (const int32_t*)(S.d_in + o_c), (const int64_t*)(S.d_in + o_o),
-                            (const int32_t*)(S.d_in + o_i), S.d_out, out_sum, (int32_t*)(S.d_out + S.off_status)};
-        if (launch_members(A, h->st) != 0) return fail("vgl_inflate_host_submit: the launch failed");
-        if (hipMemcpyAsync(S.h_out, S.d_out, (size_t)out_used, hipMemcpyDeviceToHost, h->st) != hipSuccess) return fail("vgl_inflate_host_submit: copy back failed");
-    }
-    if (hipEventRecord(S.done, h->st) != hipSuccess) { (void)hipStreamSynchronize(h->st); return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_host_submit: enqueue failed"); }
-    S.busy = true;
-    *ticket = k;
-    h->next = k ^ 1;
-    return VGL_OK;
-}
-
-extern "C" int vgl_inflate_host_wait(vgl_inflate_host* h, int32_t ticket, const uint8_t** out, int64_t* out_bytes, const int32_t** status) {
-    if (!h || ticket < 0 || ticket > 1 || !out || !out_bytes || !status || !h->s[ticket].busy) return vgl_pack_set_error(VGL_E_ARG, "vgl_inflate_host_wait: bad ticket");
-    auto& S = h->s[ticket];
-    if (hipSetDevice(h->device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_host_wait: hipSetDevice failed");
-    if (hipEventSynchronize(S.done) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_host_wait: the batch failed");
-    S.busy = false;
-    *out = S.h_out; *out_bytes = S.out_bytes; *status = (const int32_t*)(S.h_out + S.off_status);
+    if (vgl_launch_inflate_members(&A, st) != 0) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_inflate_members_device: the launch failed");
     return VGL_OK;
 }

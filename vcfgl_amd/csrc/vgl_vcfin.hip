@@ -1,5 +1,5 @@
 // vgl_vcfin.hip -- the sample columns of VCF text parsed on the device (ABI 7 additions: vgl_vcfin_workspace_bytes,
-// vgl_vcfin_parse_device, vgl_vcfin_host_*).  The host program's parse_record + make_site are the specification: per line, the
+// vgl_vcfin_parse_device; vgl_vcfin_host_* in hostlib/batch.h launches k_vcfin_parse through vgl_launch_vcfin_parse).  The host program's parse_record + make_site are the specification: per line, the
 // GT token of every sample column becomes the packed byte (b1 << 4) | b0 that the tile calls take, b = allele_map[a] & 0xF
 // (0xF for a missing allele), and the non-missing allele indices are summed.
 //   token         the gti-th ':'-separated subfield of the column; a column with fewer subfields has none: both alleles missing
@@ -32,11 +32,7 @@ constexpr int LB = 16;                   // bytes per lane and chunk
 constexpr int CHUNK = NT * LB;
 constexpr int64_t WS_BYTES = 256;        // the flag word of k_vcfin_check
 
-struct VcfinArgs {
-    const uint8_t* text; int64_t text_bytes; int32_t n_lines, N;
-    const int64_t* line_begin; const int64_t* line_end; const int32_t* gti; const int32_t* n_alleles; const int8_t* allele_map;
-    uint8_t* gt_out; int32_t* allelesum_out; int32_t* status_out;
-};
+using VcfinArgs = VglVcfinArgs;
 
 __global__ void __launch_bounds__(NT) k_vcfin_check(int32_t n_lines, int64_t text_bytes, const int64_t* __restrict__ lb, const int64_t* __restrict__ le,
                                                     uint32_t* __restrict__ flag) {
@@ -167,12 +163,12 @@ __global__ void __launch_bounds__(NT) k_vcfin_parse(const VcfinArgs A) {
     }
 }
 
-int launch_parse(const VcfinArgs& A, hipStream_t st) {
-    hipLaunchKernelGGL(k_vcfin_parse, dim3((unsigned)A.n_lines), dim3(NT), 0, st, A);
+}  // namespace
+
+extern "C" int vgl_launch_vcfin_parse(const VglVcfinArgs* a, void* stream) {
+    hipLaunchKernelGGL(k_vcfin_parse, dim3((unsigned)a->n_lines), dim3(NT), 0, (hipStream_t)stream, *a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-
-}  // namespace
 
 extern "C" int vgl_pack_set_error(int code, const char* msg);       // vgl_host.cpp: records the message for vgl_last_error()
 
@@ -204,111 +200,6 @@ extern "C" int vgl_vcfin_parse_device(int32_t device, const uint8_t* text, int64
         return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_parse_device: the argument check failed to run");
     if (h_flag) return vgl_pack_set_error(VGL_E_ARG, "vgl_vcfin_parse_device: a line range lies outside the text (0 <= line_begin <= line_end <= text_bytes)");
     VcfinArgs A{text, text_bytes, n_lines, n_samples, line_begin, line_end, gti, n_alleles, allele_map, gt_out, allelesum_out, status_out};
-    if (launch_parse(A, st) != 0) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_parse_device: the launch failed");
-    return VGL_OK;
-}
-
-// ---- host batches (vgl_vcfin_host_*): what a program without HIP of its own (the host program) uses -----------------------------
-struct vgl_vcfin_host {
-    int device = 0; int32_t N = 0, max_lines = 0; int64_t max_text = 0;
-    hipStream_t st = nullptr;
-    struct Slot {
-        uint8_t* h_in = nullptr; uint8_t* d_in = nullptr;          // text, then the five per-line arrays (one copy up)
-        uint8_t* h_out = nullptr; uint8_t* d_out = nullptr;        // rows, sums, statuses (one copy down)
-        int32_t n = 0; hipEvent_t done = nullptr; bool busy = false;
-        int64_t off_sum = 0, off_status = 0;                       // this batch's sums and statuses in h_out / d_out, behind its rows
-    } s[2];
-    int next = 0;
-    int64_t in_bytes = 0, out_bytes = 0;                           // capacity of h_in / d_in and of h_out / d_out
-};
-
-extern "C" int vgl_vcfin_host_destroy(vgl_vcfin_host* h) {
-    if (!h) return VGL_OK;
-    (void)hipSetDevice(h->device);
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    for (auto& S : h->s) {
-        if (S.d_in) (void)hipFree(S.d_in);
-        if (S.d_out) (void)hipFree(S.d_out);
-        if (S.h_in) (void)hipHostFree(S.h_in);
-        if (S.h_out) (void)hipHostFree(S.h_out);
-        if (S.done) (void)hipEventDestroy(S.done);
-    }
-    if (h->st) (void)hipStreamDestroy(h->st);
-    delete h;
-    return VGL_OK;
-}
-
-extern "C" int vgl_vcfin_host_create(int32_t device, int32_t n_samples, int32_t max_lines, int64_t max_text_bytes, vgl_vcfin_host** out) {
-    if (!out || n_samples <= 0 || max_lines <= 0 || max_text_bytes <= 0) return vgl_pack_set_error(VGL_E_ARG, "vgl_vcfin_host_create: bad argument");
-    *out = nullptr;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_host_create: no HIP device is available");
-    if (device < 0 || device >= nd) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_host_create: no such device");
-    if (hipSetDevice(device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_host_create: hipSetDevice failed");
-    vgl_vcfin_host* h = new vgl_vcfin_host;
-    h->device = device; h->N = n_samples; h->max_lines = max_lines; h->max_text = max_text_bytes;
-    auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    const int64_t L = max_lines;
-    h->in_bytes = up(max_text_bytes) + 2 * up(L * 8) + 2 * up(L * 4) + up(L * 5);
-    h->out_bytes = up(L * (int64_t)n_samples) + 2 * up(L * 4);
-    bool ok = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess;
-    for (auto& S : h->s)
-        ok = ok && hipMalloc((void**)&S.d_in, (size_t)h->in_bytes) == hipSuccess && hipMalloc((void**)&S.d_out, (size_t)h->out_bytes) == hipSuccess &&
-             hipHostMalloc((void**)&S.h_in, (size_t)h->in_bytes, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&S.h_out, (size_t)h->out_bytes, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&S.done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { vgl_vcfin_host_destroy(h); return vgl_pack_set_error(VGL_E_NOMEM, "vgl_vcfin_host_create: device or page-locked memory could not be allocated"); }
-    *out = h;
-    return VGL_OK;
-}
-
-extern "C" int vgl_vcfin_host_submit(vgl_vcfin_host* h, const uint8_t* text, int64_t text_bytes, int32_t n_lines, const int64_t* line_begin,
-                                     const int64_t* line_end, const int32_t* gti, const int32_t* n_alleles, const int8_t* allele_map, int32_t* ticket) {
-    if (!h || !ticket || n_lines < 0 || n_lines > h->max_lines || text_bytes < 0 || text_bytes > h->max_text ||
-        (n_lines > 0 && (!text || !line_begin || !line_end || !gti || !n_alleles || !allele_map)))
-        return vgl_pack_set_error(VGL_E_ARG, "vgl_vcfin_host_submit: bad argument");
-    for (int32_t i = 0; i < n_lines; i++)
-        if (line_begin[i] < 0 || line_begin[i] > line_end[i] || line_end[i] > text_bytes)
-            return vgl_pack_set_error(VGL_E_ARG, "vgl_vcfin_host_submit: a line range lies outside the text (0 <= line_begin <= line_end <= text_bytes)");
-    const int k = h->next;
-    auto& S = h->s[k];
-    if (S.busy) return vgl_pack_set_error(VGL_E_ARG, "vgl_vcfin_host_submit: two batches are in flight (vgl_vcfin_host_wait the older one first)");
-    if (hipSetDevice(h->device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_host_submit: hipSetDevice failed");
-    S.n = n_lines;
-    if (n_lines > 0) {
-        // the batch's text and arrays lie back to back in the staging (sized by n_lines) and go up in one copy; rows, sums and
-        // statuses come down in one.  Once something is enqueued a failure waits for the stream: the staging is read by it
-        auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-        const int64_t L = n_lines;
-        const int64_t o_lb = up(text_bytes), o_le = o_lb + up(L * 8), o_gti = o_le + up(L * 8), o_nal = o_gti + up(L * 4), o_map = o_nal + up(L * 4);
-        const int64_t in_used = o_map + L * 5;
-        S.off_sum = up(L * h->N); S.off_status = S.off_sum + up(L * 4);
-        const int64_t out_used = S.off_status + L * 4;
-        memcpy(S.h_in, text, (size_t)text_bytes);
-        memcpy(S.h_in + o_lb, line_begin, (size_t)L * 8); memcpy(S.h_in + o_le, line_end, (size_t)L * 8);
-        memcpy(S.h_in + o_gti, gti, (size_t)L * 4); memcpy(S.h_in + o_nal, n_alleles, (size_t)L * 4);
-        memcpy(S.h_in + o_map, allele_map, (size_t)L * 5);
-        auto fail = [&](const char* msg) { (void)hipStreamSynchronize(h->st); return vgl_pack_set_error(VGL_E_NODEVICE, msg); };
-        if (hipMemcpyAsync(S.d_in, S.h_in, (size_t)in_used, hipMemcpyHostToDevice, h->st) != hipSuccess) return fail("vgl_vcfin_host_submit: copy to the device failed");
-        VcfinArgs A{S.d_in, text_bytes, n_lines, h->N, (const int64_t*)(S.d_in + o_lb), (const int64_t*)(S.d_in + o_le),
-                    (const int32_t*)(S.d_in + o_gti), (const int32_t*)(S.d_in + o_nal), (const int8_t*)(S.d_in + o_map),
-                    S.d_out, (int32_t*)(S.d_out + S.off_sum), (int32_t*)(S.d_out + S.off_status)};
-        if (launch_parse(A, h->st) != 0) return fail("vgl_vcfin_host_submit: the launch failed");
-        if (hipMemcpyAsync(S.h_out, S.d_out, (size_t)out_used, hipMemcpyDeviceToHost, h->st) != hipSuccess) return fail("vgl_vcfin_host_submit: copy back failed");
-    }
-    if (hipEventRecord(S.done, h->st) != hipSuccess) { (void)hipStreamSynchronize(h->st); return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_host_submit: enqueue failed"); }
-    S.busy = true;
-    *ticket = k;
-    h->next = k ^ 1;
-    return VGL_OK;
-}
-
-extern "C" int vgl_vcfin_host_wait(vgl_vcfin_host* h, int32_t ticket, const uint8_t** gt, const int32_t** allelesum, const int32_t** status) {
-    if (!h || ticket < 0 || ticket > 1 || !gt || !allelesum || !status || !h->s[ticket].busy) return vgl_pack_set_error(VGL_E_ARG, "vgl_vcfin_host_wait: bad ticket");
-    auto& S = h->s[ticket];
-    if (hipSetDevice(h->device) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_host_wait: hipSetDevice failed");
-    if (hipEventSynchronize(S.done) != hipSuccess) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_host_wait: the parse failed");
-    S.busy = false;
-    *gt = S.h_out; *allelesum = (const int32_t*)(S.h_out + S.off_sum); *status = (const int32_t*)(S.h_out + S.off_status);
+    if (vgl_launch_vcfin_parse(&A, st) != 0) return vgl_pack_set_error(VGL_E_NODEVICE, "vgl_vcfin_parse_device: the launch failed");
     return VGL_OK;
 }
