@@ -329,7 +329,7 @@ def auto_weights(loop_blocks, freq, bins):
         elif sum(t.startswith("v_fma_f32") for t in valu) >= 8:
             region = "gamma_test"
             w[lab], why[lab] = freq[region], f"bounded gamma test ({freq[region]:.3f} per iteration, measured)"
-        elif "v_log_f32_e32" in toks and any(t.startswith("v_rcp_f32") for t in toks) and "v_cvt_i32_f32_e32" not in toks and len(valu) <= 16:
+        elif "v_log_f32_e32" in toks and "v_cvt_i32_f32_e32" not in toks and len(valu) <= 16:      # (the quotient v / u is formed in front of the block where the gamma step shares it)
             region = "normal_test"
             w[lab], why[lab] = freq[region], f"bounded normal-deviate test ({freq[region]:.3f} per iteration, measured)"
         elif "ds_read_u8" in toks:

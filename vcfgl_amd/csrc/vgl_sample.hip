@@ -134,6 +134,12 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
 #ifndef VGL_POOL_ATTEMPTS
 #define VGL_POOL_ATTEMPTS 2
 #endif
+    // VGL_POOL_HALVES: which float32 builds (without --precise-gl 1) run TWO attempt-and-gamma half-steps per iteration ("two half-steps" below) instead
+    // of the loop of VGL_POOL_ATTEMPTS -- bit 0: LEAN 2 (C3 7.54 -> 6.97 ms), bit 1: LEAN 4 (qsi16 9.02 -> 8.39), bit 2: LEAN 3 (--adjust-qs: no bench
+    // workload runs it, not measured, hence not in the default).  -DVGL_POOL_HALVES=0: the loop of VGL_POOL_ATTEMPTS everywhere (A/B timing: tools/ab_build_seg.sh)
+#ifndef VGL_POOL_HALVES
+#define VGL_POOL_HALVES 3
+#endif
 #ifdef VGL_POOL_F64
     constexpr bool F32 = false;
 #else
@@ -151,6 +157,7 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
     // it.  No base plane, no dense pass; a wavefront's pool of up to 2240 items (depth 30 in one segment) leaves LDS for eight wavefronts per SIMD
     constexpr bool P16 = F32;                                         // (LEAN 2 and LEAN 3 without --precise-gl 1)
     constexpr int ISZ = P16 ? 2 : 4;                                  // bytes of an item's slot
+    constexpr bool HALVES = F32 && !PREC && ((VGL_POOL_HALVES >> (LEAN == 2 ? 0 : (LEAN == 4 ? 1 : 2))) & 1) != 0;
     constexpr bool SLIM = (LEAN == 1 || LEAN == 2);                  // default tag surface: none of the optional per-read state
     constexpr bool DUMP = (LEAN == 0);                               // a per-read dump (reads_out) may be asked for
 #ifdef VGL_TEST_HOOKS
@@ -569,6 +576,7 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                 if constexpr (F32) {
                     // ---- float32 loop (vgl_common.hip.h): same dealing, same hold / period logic; every quantity a float32 built from the
                     // integer state, every comparison against a threshold moved by the float32 error bound, `redo` where a bound cannot tell.
+                    // Two forms of the attempts inside one loop (prefetch, finish block, dealing and period counter are shared): HALVES, below, and
                     // TWO normal-deviate attempts per iteration (VGL_POOL_ATTEMPTS 2): the ratio-of-uniforms sampler rejects 27 % of its
                     // attempts, and an iteration whose attempt is rejected has paid for the gamma step, the dealing and the loop's scalar
                     // bookkeeping for nothing -- measured (round 5): extra vector instructions in this loop cost next to nothing, an
@@ -590,6 +598,126 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                         asm volatile("" : "+v"(goff));
                         const lds_f32* const gc = (const lds_f32*)(uintptr_t)goff;
                         const float ga1 = gc[0], ga2 = gc[1], c015s = gc[2], sure_ms = gc[3];
+                        // operands of this lane's next item (as in the float64 loop), asked for in the middle of the attempt's arithmetic
+                        uint32_t skn = 0;
+                        VglAffine tab_n;
+                        uint64_t base_n;
+                        auto prefetch = [&]() {
+                            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kn));
+#ifdef VGL_POOL_CLAMP_NEXT
+                            const uint32_t kc = (uint32_t)(kn < segT4 ? kn : segT * ISZ);   // l_it[segT] = 0 stands for "none" (a quarter's own limit is another quarter's live item)
+#else
+                            // (round 6: no clamp.  A lane whose claim lies past its items reads whatever 16 bits are there -- another quarter's slot, the table, or
+                            //  beyond the block, which LDS answers with zeros -- and forms a table address of at most 255 x 16 bytes (the table has 256 entries) and an
+                            //  LDS address below 512: nothing of it is used, the lane has no item any more (`have`).  Three vector instructions per iteration less.)
+                            const uint32_t kc = P16 ? (uint32_t)kn : (uint32_t)(kn < segT4 ? kn : segT * ISZ);
+#endif
+                            uint32_t rd16, ow8;
+                            if (P16) {
+                                skn = *(const lds_u16*)(uintptr_t)(576u + kc);                                // owner << 10 | read << 2 | base
+                                asm volatile("" : "+v"(skn));
+                                rd16 = (skn << 2) & 0xFF0u;                                                   // 16 x read: byte offset of its jump
+                                ow8 = (skn >> 7) & 0x1F8u;                                                    // 8 x owner: LDS address of l_stq[owner]
+                            } else {
+                                rd16 = *(const lds_u16*)(uintptr_t)(576u + kc);
+                                ow8 = *(const lds_u16*)(uintptr_t)(578u + kc);
+                                asm volatile("" : "+v"(rd16), "+v"(ow8));
+                            }
+                            tab_n = *(const VglAffine*)((const uint8_t*)P.qs_read_tab + rd16);
+                            base_n = *(__attribute__((address_space(3))) const uint64_t*)(uintptr_t)ow8;
+                        };
+                        // what the finish block takes from the attempts: the read is finished (or goes to k_redo), its two gamma deviates
+                        bool hold, redo, fin;
+                        float fx, fy;
+                        if constexpr (HALVES) {
+                            // ---- two half-steps (VGL_POOL_HALVES): an iteration's fixed price -- sixteen lane flags of scalar bookkeeping, the prefetch, the
+                            // dealing, the finish block -- is paid once for up to TWO gamma deviates, so that a read whose attempts are all accepted (53 %)
+                            // is finished by the iteration that adopted it.
+                            // Half-step 1 is the loop of VGL_POOL_ATTEMPTS 1: normal attempt A on outputs one and two, the gamma step on it with output
+                            // three; both bounded tests, every hold and every source of `redo` live here.  Held: nothing moves; A rejected: the state
+                            // moves past two outputs; gamma step tried: past three, accepted or not.
+                            uint32_t l1, h1, l2, h2, l3, h3;
+                            lcg52_step(s_lo, s_hi, l1, h1);
+                            lcg52_step(l1, h1, l2, h2);
+                            lcg52_step(l2, h2, l3, h3);
+                            const float ufA = pool32_u(lcg52_top32(l1, h1));
+                            const float svA = pool32_sv(lcg52_top32(l2, h2));
+                            const float u2A = pool32_u(lcg52_top32(l3, h3));
+                            const float qA = pool32_q(ufA, svA);
+                            const bool q_lo = qA > VGL_P32_QLO - VGL_P32_QBAND, q_hi = qA > VGL_P32_QHI + VGL_P32_QBAND;
+                            const bool n_amb = have && q_lo && !q_hi;                   // the reference may look at the logarithm test (1.2 % of the attempts)
+                            bool slow_n = false;
+                            hold = n_amb && !full;
+                            redo = false;
+                            const float xnA = svA * __builtin_amdgcn_rcpf(ufA);         // v / u
+                            if (full && __builtin_amdgcn_ballot_w64(n_amb)) {
+                                bool und;
+                                if (DBG) c_ntest++;
+                                slow_n = pool32_normal_slow(xnA, ufA, qA, n_amb, und);
+                                redo = und || (n_amb && dbg_redo_every && (l1 >> 8) % (uint32_t)(dbg_redo_every | (dbg_redo_every == 0)) == 0u);
+                            }
+                            const bool g_try0 = have && !hold && !(q_lo && (q_hi || slow_n));
+                            prefetch();
+                            // gamma step (rng.h:139-145) on A
+                            const float wA = __builtin_fmaf(ga2, xnA, 1.0f);
+                            const float xsqA = xnA * xnA;
+                            const float x4A = xsqA * xsqA;
+                            const bool sureA = (0x1p32f - u2A) >= __builtin_fmaf(x4A, c015s, sure_ms);
+                            const bool in_rangeA = (wA >= 0.5f) && (ufA >= VGL_P32_UMIN);
+                            redo = redo || (g_try0 && !in_rangeA);
+                            const bool g_try = g_try0 && in_rangeA;
+                            const bool g_amb = g_try && !sureA;                         // squeeze and logarithm test in the bounded block (0.2 % of the lanes)
+                            hold = hold || (g_amb && !full);
+                            bool slow_g = false;
+                            if (full && __builtin_amdgcn_ballot_w64(g_amb)) {
+                                bool und;
+                                if (DBG) c_gtest++;
+                                slow_g = pool32_gamma_slow(u2A, ga2 * xnA, ga1, x4A, g_amb, und);
+                                redo = redo || und || (g_amb && dbg_redo_every && (l3 >> 8) % (uint32_t)(dbg_redo_every | (dbg_redo_every == 0)) == 1u);
+                            }
+                            const bool acc1 = g_try && !(g_amb && slow_g) && !hold;
+                            const float val1 = ga1 * ((wA * wA) * wA);
+                            const bool fin1 = (acc1 && stage1) || redo;
+                            s_lo = hold ? s_lo : (g_try0 ? l3 : l2);
+                            s_hi = hold ? s_hi : (g_try0 ? h3 : h2);
+                            gxf = (acc1 && !stage1) ? val1 : gxf;
+                            stage1 = (stage1 != acc1) && !redo;
+                            // Half-step 2, for a lane that is not held and whose read goes on: the next attempt and its gamma step from the state and the
+                            // stage half-step 1 left (hence that stage's constants), committed only where float32 settles both without a bounded test --
+                            // rejected outright by q (past two outputs), or accepted by q alone, in range and surely accepted by the gamma step (past
+                            // three).  Anything else is left alone: the state stays, and the same attempt is the next iteration's half-step 1, which has
+                            // the bounded tests -- as VGL_POOL_ATTEMPTS 2 treats its attempt B inside the logarithm band.
+                            uint32_t goff2 = stage1 ? 528u : 512u;
+                            asm volatile("" : "+v"(goff2));
+                            const lds_f32* const gc2 = (const lds_f32*)(uintptr_t)goff2;
+                            const float gb1 = gc2[0], gb2 = gc2[1], c015s2 = gc2[2], sure_ms2 = gc2[3];
+                            uint32_t m1, n1, m2, n2, m3, n3;
+                            lcg52_step(s_lo, s_hi, m1, n1);
+                            lcg52_step(m1, n1, m2, n2);
+                            lcg52_step(m2, n2, m3, n3);
+                            const float ufB = pool32_u(lcg52_top32(m1, n1));
+                            const float svB = pool32_sv(lcg52_top32(m2, n2));
+                            const float u2B = pool32_u(lcg52_top32(m3, n3));
+                            const float qB = pool32_q(ufB, svB);
+                            const bool run2 = have && !hold && !fin1;
+                            const bool rej2 = run2 && (qB > VGL_P32_QHI + VGL_P32_QBAND);
+                            const float xnB = svB * __builtin_amdgcn_rcpf(ufB);
+                            const float wB = __builtin_fmaf(gb2, xnB, 1.0f);
+                            const float xsqB = xnB * xnB;
+                            const float x4B = xsqB * xsqB;
+                            const bool sureB = (0x1p32f - u2B) >= __builtin_fmaf(x4B, c015s2, sure_ms2);
+                            const bool in_rangeB = (wB >= 0.5f) && (ufB >= VGL_P32_UMIN);
+                            const bool acc2 = run2 && !(qB > VGL_P32_QLO - VGL_P32_QBAND) && in_rangeB && sureB;
+                            const float val2 = gb1 * ((wB * wB) * wB);
+                            s_lo = acc2 ? m3 : (rej2 ? m2 : s_lo);
+                            s_hi = acc2 ? n3 : (rej2 ? n2 : s_hi);
+                            const bool fin2 = acc2 && stage1;
+                            fin = fin1 || fin2;
+                            fx = gxf;                                                   // (the first deviate: this iteration's or an earlier one's)
+                            fy = fin2 ? val2 : val1;
+                            gxf = (acc2 && !stage1) ? val2 : gxf;
+                            stage1 = stage1 != acc2;
+                        } else {       // ---- the loop of VGL_POOL_ATTEMPTS (LEAN 3, --precise-gl 1; body left at the loop's indentation)
                         // normal attempt A (rng.h:72-78): the stream's next two outputs
                         uint32_t l1, h1, l2, h2, l3, h3;
                         lcg52_step(s_lo, s_hi, l1, h1);
@@ -601,8 +729,8 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                         const bool q_lo = qA > VGL_P32_QLO - VGL_P32_QBAND, q_hi = qA > VGL_P32_QHI + VGL_P32_QBAND;
                         bool slow_n = false;
                         const bool n_amb = have && q_lo && !q_hi;                   // the reference may look at the logarithm test (1.2 % of the attempts)
-                        bool hold = n_amb && !full_n;
-                        bool redo = false;
+                        hold = n_amb && !full_n;
+                        redo = false;
                         if (full_n && __builtin_amdgcn_ballot_w64(n_amb)) {
                             bool und;
                             if (DBG) c_ntest++;
@@ -630,29 +758,7 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                         const float u2f = pool32_u(lcg52_top32(l3, h3));
                         const bool g_try0 = have && accA && !hold;
 #endif
-                        // operands of this lane's next item (as in the float64 loop)
-                        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kn));
-#ifdef VGL_POOL_CLAMP_NEXT
-                        const uint32_t kc = (uint32_t)(kn < segT4 ? kn : segT * ISZ);   // l_it[segT] = 0 stands for "none" (a quarter's own limit is another quarter's live item)
-#else
-                        // (round 6: no clamp.  A lane whose claim lies past its items reads whatever 16 bits are there -- another quarter's slot, the table, or
-                        //  beyond the block, which LDS answers with zeros -- and forms a table address of at most 255 x 16 bytes (the table has 256 entries) and an
-                        //  LDS address below 512: nothing of it is used, the lane has no item any more (`have`).  Three vector instructions per iteration less.)
-                        const uint32_t kc = P16 ? (uint32_t)kn : (uint32_t)(kn < segT4 ? kn : segT * ISZ);
-#endif
-                        uint32_t rd16, ow8, skn = 0;
-                        if (P16) {
-                            skn = *(const lds_u16*)(uintptr_t)(576u + kc);                                // owner << 10 | read << 2 | base
-                            asm volatile("" : "+v"(skn));
-                            rd16 = (skn << 2) & 0xFF0u;                                                   // 16 x read: byte offset of its jump
-                            ow8 = (skn >> 7) & 0x1F8u;                                                    // 8 x owner: LDS address of l_stq[owner]
-                        } else {
-                            rd16 = *(const lds_u16*)(uintptr_t)(576u + kc);
-                            ow8 = *(const lds_u16*)(uintptr_t)(578u + kc);
-                            asm volatile("" : "+v"(rd16), "+v"(ow8));
-                        }
-                        const VglAffine tab_n = *(const VglAffine*)((const uint8_t*)P.qs_read_tab + rd16);
-                        const uint64_t base_n = *(__attribute__((address_space(3))) const uint64_t*)(uintptr_t)ow8;
+                        prefetch();
                         // gamma step (rng.h:139-145) on the accepted deviate
                         const float xn = sv * __builtin_amdgcn_rcpf(uf);             // v / u
                         const float w = __builtin_fmaf(ga2, xn, 1.0f);
@@ -685,9 +791,8 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                         s_lo = hold ? s_lo : (g_try0 ? l3 : l2);
                         s_hi = hold ? s_hi : (g_try0 ? h3 : h2);
 #endif
-                        const float val = ga1 * vv;
-                        const bool fin = (acc_g && stage1) || redo;
-                        const float gx_prev = gxf;
+                        fin = (acc_g && stage1) || redo;
+                        fx = gxf; fy = ga1 * vv;
                         if constexpr (PREC) {
                             // the accepted attempt again, in double (rng.h:72-78: u, v = 1.7156 (u' - 0.5), x = v / u; :139-145: w = 1 + a2 x, a1 w^3): its two
                             // uniforms are the generator states the float32 attempt was formed from (A: outputs one and two, B: three and four); every decision
@@ -722,14 +827,15 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                                 } else gxd = vald;
                             }
                         }
-                        gxf = (acc_g && !stage1) ? val : gxf;
+                        gxf = (acc_g && !stage1) ? fy : gxf;
                         stage1 = (stage1 != acc_g) && !redo;
+                        }              // (!HALVES)
                         if (DBG) {
                             const uint64_t fm = __builtin_amdgcn_ballot_w64(fin);
                             c_finb += (fm != 0); c_lfin += (unsigned)__popcll(fm); c_lhold += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(hold));
                         }
                         if (fin) {
-                            const float pf = gx_prev * __builtin_amdgcn_rcpf(gx_prev + val);   // the read's error probability X / (X + Y) (rng.h:438)
+                            const float pf = fx * __builtin_amdgcn_rcpf(fx + fy);   // the read's error probability X / (X + Y) (rng.h:438)
                             if (P16) {
                                 // the read's quality score (vcfgl.cpp:500-523) here, by the lane that finished it: the staged byte into the item's
                                 // slot; bit 8 where the float32 value cannot decide it (the owner hands those reads to k_redo when it stages them)
