@@ -946,6 +946,51 @@ VGL_API int vgl_setal_apply_device(int32_t device, int32_t n_samples, int32_t n_
                                    void* workspace, int64_t workspace_bytes, void* hip_stream);
 VGL_API int vgl_ctx_set_alleles(vgl_ctx* ctx, const int8_t* table, int64_t first_site, int64_t n_sites);
 
+/* ---- the records of --depth inf, on the device (ABI 7, additive: the version stays 7) ----------------------------------------------
+ * simulate_record_true_values (vcfgl.cpp:1089-1262): no read is drawn.  From a tile's packed true genotypes `gt` (one byte per site
+ * and sample, the two bases 0 .. 3 = A, C, G, T in its nibbles, as for vgl_simulate_tile_device):
+ *   the allele list   the four bases by descending allele count over the site's samples, ties in the order A < C < G < T (the
+ *                     reference's insertion sort swaps on strictly greater only); do_unobserved 0 / 1 / 2: the bases that occur,
+ *                     3 / 4 / 5: all four; 1, 2, 4 and 5 append the unobserved allele (4)
+ *   site_status       VGL_SITE_OK;  n_alleles: the length of the list;  n_alleles_obs: the number of bases that occur
+ *   alleles2acgt      the list, -1 behind n_alleles
+ *   gl, gp, pl, pl_u8 per sample and genotype g < nG(site) = n_alleles (n_alleles + 1) / 2: at the sample's true genotype
+ *                     bcf_alleles2gt(index of base 0, index of base 1) GL 0 (bits 0x00000000), GP 1, PL 0; at every other one GL -inf
+ *                     (bits 0xFF800000), GP 0, PL 255.  Each array may be NULL.
+ * VGL_LAYOUT_PLANES: planes g >= nG(site) get the missing value (0x7F800001, VGL_INT32_MISSING, 255).
+ * VGL_LAYOUT_SAMPLE_MAJOR: the record's array is the n_samples * nG(site) values at the head of its slab; nothing behind it is written.
+ * A nibble outside 0 .. 3 makes the site BAD: the smallest such site index is stored into *bad_site; the per-site arrays of a bad
+ * site are written from the nibbles that are valid, its gl / gp / pl / pl_u8 are unspecified.
+ *   vgl_inf_workspace_bytes  device workspace of a call (-1 for a negative argument).  Pure host arithmetic.
+ *   vgl_inf_fill_device      every pointer is device memory of `device`.  gt [n_sites][n_samples]; site_status, n_alleles and
+ *                            n_alleles_obs [n_sites], alleles2acgt [n_sites][5] (all four required); gl / pl / gp / pl_u8 in `layout`
+ *                            with max_genotypes planes per site.  bad_site: one int32 the CALLER sets to INT32_MAX (or any value >=
+ *                            n_sites) beforehand; the call lowers it (atomic minimum) to the first bad site of the tile, counted
+ *                            from 0.  Work is enqueued on `hip_stream`; the call returns without synchronising.  VGL_E_ARG for a bad
+ *                            count, do_unobserved outside 0 .. 5, a max_genotypes / max_alleles pair that do_unobserved does not
+ *                            give (10 / 4 for 0 and 3, else 15 / 5: vgl_max_genotypes, vgl_max_alleles), a bad layout, a NULL among
+ *                            gt, the four per-site arrays and bad_site, or a workspace smaller than vgl_inf_workspace_bytes.
+ *   vgl_ctx_true_values      on != 0: every tile the context is then given through vgl_simulate_tile, _async, _text_async or
+ *                            vgl_simulate_tile_device is filled from its gt as above instead of simulated (do_unobserved, the
+ *                            layout and add_gl / add_gp / add_pl are the context's; no random draw is consumed).  The text formatter,
+ *                            vgl_ctx_bcf_keys, vgl_ctx_text_device and the stream handles work as for a simulated tile, with the
+ *                            FORMAT fields in the reference's order for such records: GL, GP, PL (vcfgl.cpp:1243-1259), for text
+ *                            and BCF vectors alike.  on = 0: the context simulates again, exactly as before.  Call it while no
+ *                            tile of the context is in flight.  VGL_E_ARG when the context's parameters ask for what true values
+ *                            do not define (add_fmt_dp, add_info_dp, an AD / ADF / ADR flag, add_qs, add_i16), or while a
+ *                            discordance tally, a fetch-GL genotype or a set-alleles table is set.  While it is on, VGL_E_ARG from
+ *                            a tile call whose vgl_tile_out has a non-NULL info_dp, info_ad, info_adf, info_adr, qs, i16, fmt_dp,
+ *                            fmt_ad, fmt_adf, fmt_adr, reads, read_errp or site_pick_err, from a tile call with a pileup or
+ *                            fetch-GL tile pending, a tally or a table set, and from vgl_simulate_tile_gvcf_async.  A bad site:
+ *                            VGL_E_ARG from vgl_tile_wait / vgl_ctx_check, vgl_last_error() names the absolute site (the smallest
+ *                            one of the tiles checked).  The sampler's tables and staging the context allocated at creation stay. */
+VGL_API int64_t vgl_inf_workspace_bytes(int32_t n_samples, int32_t n_sites);
+VGL_API int vgl_inf_fill_device(int32_t device, int32_t n_samples, int32_t n_sites, int32_t do_unobserved, int32_t max_genotypes, int32_t max_alleles,
+                                int32_t layout, const uint8_t* gt, int32_t* site_status, int32_t* n_alleles, int32_t* n_alleles_obs, int8_t* alleles2acgt,
+                                float* gl, int32_t* pl, float* gp, uint8_t* pl_u8, int32_t* bad_site, void* workspace, int64_t workspace_bytes,
+                                void* hip_stream);
+VGL_API int vgl_ctx_true_values(vgl_ctx* ctx, int32_t on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,7 @@ EXPORTS = [
     "vgl_setal_workspace_bytes", "vgl_setal_apply_device", "vgl_ctx_set_alleles",
     "vgl_bcfin_workspace_bytes", "vgl_bcfin_decode_device",
     "vgl_bcfin_host_create", "vgl_bcfin_host_submit", "vgl_bcfin_host_wait", "vgl_bcfin_host_destroy",
+    "vgl_inf_workspace_bytes", "vgl_inf_fill_device", "vgl_ctx_true_values",
 ]
 # value modes of the fetch-GL formatter (VGL_FETCHGL_*): the simulated float, or the float its VCF text reads back as
 FETCHGL_FLOAT, FETCHGL_TEXT = 0, 1
@@ -332,6 +333,10 @@ def load_library(hooks=False):
                                           C.c_void_p, C.POINTER(C.c_int32)]
     lib.vgl_bcfin_host_wait.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.vgl_bcfin_host_destroy.argtypes = [C.c_void_p]
+    lib.vgl_inf_workspace_bytes.restype = C.c_int64
+    lib.vgl_inf_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.vgl_inf_fill_device.argtypes = [C.c_int32] * 7 + [C.c_void_p] * 11 + [C.c_int64, C.c_void_p]
+    lib.vgl_ctx_true_values.argtypes = [C.c_void_p, C.c_int32]
     if lib.vgl_abi_version() != ABI_VERSION:
         raise RuntimeError("libvcfgl_hip.so ABI version mismatch")
     _LIB[hooks] = lib

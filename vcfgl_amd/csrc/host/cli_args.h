@@ -27,6 +27,7 @@ struct Args {
     int device_inflate = 0;            // --device-inflate 1: a BGZF input is inflated on the first device of the run
     int device_input = 0;              // --device-input 1: the sample columns of the input VCF text parsed on the first device of the run
     int device_bcf_input = 0;          // --device-bcf-input 1: the GT vectors of the input BCF's records decoded on the first device of the run
+    int device_inf = 0;                // --device-inf 1: the records of --depth inf made on the device(s), through the tile ring and every --device-* path
     double depth = -1.0, error_rate = -1.0, beta_variance = -1.0, gl1_theta = 0.83, adjust_by = 0.499;
     bool have_depth = false, depth_inf = false;
     std::string in_fn, out_prefix = "output", output_mode = "b", depths_fn, qs_bins_fn, command;
@@ -119,6 +120,15 @@ static const char USAGE[] =
     "                   a batch.  A file that is not BGZF (plain text, gzip) and a file with a member the device does not take to its exact end\n"
     "                   are read by zlib as with 0: same bytes either way.  Refused with --depth inf; a run without a GPU fails instead of\n"
     "                   falling back]\n"
+    "                   --device-inf 0|1 [0: the records of --depth inf are written by one host thread, value by value, and no device is used; 1: they are\n"
+    "                   made on the device(s) -- per tile the allele list of every site and GL 0 / GP 1 / PL 0 at each sample's true genotype,\n"
+    "                   -inf / 0 / 255 elsewhere -- and go through the tile ring like simulated records.  Same records either way.  Needs --depth inf\n"
+    "                   and one of -addGL / -addGP / -addPL 1.  With it --device-text, --device-bcf, --device-stream, --device-input,\n"
+    "                   --device-bcf-input, --device-inflate, --devices, --tile-sites and --encode-threads work as for a finite depth (without it\n"
+    "                   --depth inf refuses them); the flags --depth inf ignores on the host (--gl-model, --error-qs, --adjust-qs, --rm-empty-sites,\n"
+    "                   --rng-mode, the DP / AD tags ...) are ignored here too.  Refused with -printPileup 1; --gt-discordance 1, --fetch-gl,\n"
+    "                   --set-alleles, --records 0, -doGVCF 1, --device-gvcf 1 and --device-pileup 1 stay refused with --depth inf; a run without a\n"
+    "                   GPU fails instead of falling back]\n"
     "                   -v --version    -vv    -h --help\n\n";
 
 // the record files' extension: <prefix>.vcf, .vcf.gz or .bcf (the truth file: <prefix>.truth.*)
@@ -213,6 +223,7 @@ static Args parse_args(int argc, char** argv) {
         else if (f == "--device-input") a.device_input = I(v);
         else if (f == "--device-inflate") a.device_inflate = I(v);
         else if (f == "--device-bcf-input") a.device_bcf_input = I(v);
+        else if (f == "--device-inf") a.device_inf = I(v);
         else if (f == "--devices") { a.devices.clear(); for (const char* q = v; *q;) { char* e; const long d = strtol(q, &e, 10); if (e == q || d < 0) die("Could not parse --devices %s", v); a.devices.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') die("Could not parse --devices %s", v); } }
         else die("Unknown argument: %s", argv[i]);
     }
@@ -263,15 +274,24 @@ static Args parse_args(int argc, char** argv) {
             die("--records 0 is not supported with -printBasePickError / -printQsError / -printGlError / -printQScores 1 (per-read listings).");
         a.device_text = a.device_bcf = a.device_gvcf = a.device_stream = a.device_pileup = 0;      // nothing to format, encode or assemble
     }
+    // the records of --depth inf from the device (checked before any GPU work: nothing is written).  --gt-discordance 1, --fetch-gl,
+    // --set-alleles and with them --records 0 are refused with --depth inf above; -doGVCF 1 and --device-gvcf 1 below, flag or no flag
+    range(a.device_inf, 0, 1, "--device-inf");
+    if (a.device_inf) {
+        if (!a.depth_inf) die("--device-inf 1 makes the records of --depth inf on the device: it needs --depth inf (a finite --depth / --depths-file is simulated on the device anyway).");
+        if (!a.add_gl && !a.add_gp && !a.add_pl) die("--device-inf 1 needs at least one of -addGL 1, -addGP 1 and -addPL 1 (with none of them a record has no sample column to make).");
+        if (a.print_pileup) die("--device-inf 1 is not supported with -printPileup 1 (no read is drawn with --depth inf: there is no pileup).");
+    }
+    const bool host_inf = a.depth_inf && !a.device_inf;         // --depth inf on the host: no device is used, no tile is made
     range(a.device_input, 0, 1, "--device-input");
-    if (a.device_input == 1 && a.depth_inf) die("--device-input 1 is not supported with --depth inf (no device is used).");
+    if (a.device_input == 1 && host_inf) die("--device-input 1 is not supported with --depth inf (no device is used).");
     range(a.device_bcf_input, 0, 1, "--device-bcf-input");
-    if (a.device_bcf_input == 1 && a.depth_inf) die("--device-bcf-input 1 is not supported with --depth inf (no device is used).");
+    if (a.device_bcf_input == 1 && host_inf) die("--device-bcf-input 1 is not supported with --depth inf (no device is used).");
     range(a.device_inflate, 0, 1, "--device-inflate");
-    if (a.device_inflate == 1 && a.depth_inf) die("--device-inflate 1 is not supported with --depth inf (no device is used).");
-    if (a.device_stream == 1 && a.depth_inf) die("--device-stream 1 is not supported with --depth inf (no tile is simulated).");
+    if (a.device_inflate == 1 && host_inf) die("--device-inflate 1 is not supported with --depth inf (no device is used).");
+    if (a.device_stream == 1 && host_inf) die("--device-stream 1 is not supported with --depth inf (no tile is simulated).");
     if (a.device_gvcf == 1 && a.depth_inf) die("--device-gvcf 1 is not supported with --depth inf (no tile is simulated).");
-    if (a.device_bcf == 1 && a.depth_inf) die("--device-bcf 1 is not supported with --depth inf (no tile is simulated).");
+    if (a.device_bcf == 1 && host_inf) die("--device-bcf 1 is not supported with --depth inf (no tile is simulated).");
     if (a.depth_inf) {                                                          // io.cpp:781-850, 1011-1018
         if (a.rm_invar & 4) die("[--rm-invar-sites %d] Cannot skip invariable sites when --depth inf is set.", a.rm_invar);
         if (a.do_gvcf) die("[-doGVCF 1] Cannot output gVCF when --depth inf is set.");
@@ -318,7 +338,7 @@ static Args parse_args(int argc, char** argv) {
     if (a.device_text) {                                        // (checked before any GPU work: nothing is written)
         if (a.output_mode != "v" && a.output_mode != "z") die("--device-text 1 formats VCF text: it needs -O v or -O z (found -O %s).", a.output_mode.c_str());
         if (a.do_gvcf) die("--device-text 1 is not supported with -doGVCF 1 (the gVCF blocker reads the FORMAT arrays of every site on the host); use --device-gvcf 1.");
-        if (a.depth_inf) die("--device-text 1 is not supported with --depth inf (no tile is simulated).");
+        if (host_inf) die("--device-text 1 is not supported with --depth inf (no tile is simulated).");
     }
     range(a.device_gvcf, 0, 1, "--device-gvcf");
     if (a.device_gvcf) {                                        // (checked before any GPU work: nothing is written)

@@ -42,7 +42,15 @@ struct DeviceWorker {
                 if (rc != VGL_OK) die("%s", vgl_last_error());
             }
             if (prev) {
-                const int wrc = vgl_tile_wait(ctx, prev_ticket);
+                int wrc = vgl_tile_wait(ctx, prev_ticket);
+                if (wrc == VGL_E_ARG && P.inf) {                         // the library names the site; the writer, in site order, reports its position
+                    for (int i = 0; i < prev->ns && prev->bad_pos < 0; i++)
+                        for (int s = 0; s < P.N; s++) {
+                            const uint8_t b = prev->gt[(size_t)i * P.N + s];
+                            if ((b & 0xF) > 3 || (b >> 4) > 3) { prev->bad_pos = prev->meta[i].pos0 + 1; break; }
+                        }
+                    if (prev->bad_pos >= 0) wrc = VGL_OK;                // (the tile is handed on as done; the writer ends the run when it comes to it)
+                }
                 if (wrc == VGL_E_SETAL) die("--set-alleles: %s.  Every allele of a line must be one of its record's alleles.", vgl_last_error());
                 if (wrc != VGL_OK) die("%s", vgl_last_error());
                 if (P.path == TEXT && !hs) text_bytes += (double)prev->toff[prev->ns];

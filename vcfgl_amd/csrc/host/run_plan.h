@@ -20,6 +20,7 @@ struct RunPlan {
     bool rec0 = false;                        // --records 0: no record file, no FORMAT array back; the tiles are simulated and tallied
     bool fetch = false;                       // --fetch-gl XY: one genotype's GL of every tile comes back as CSV text
     bool setal = false;                       // --set-alleles FILE: every context relabels its tiles from the file's table
+    bool inf = false;                         // --device-inf 1: the contexts fill their tiles from the true genotypes (--depth inf), nothing is simulated
     bool want_dp = false, want_errp = false, dump_reads = false, dump_pick = false;
     bool host_pileup = false;                 // -printPileup 1 without it: the lines are formatted on the host from the read dump
 };
@@ -38,6 +39,22 @@ static vgl_params make_params(const Args& a, int N) {
     return p;
 }
 
+// --device-inf 1: the arguments of the device run.  What run_depth_inf ignores -- the depth, the error and likelihood models, the
+// quality-score adjustments, the DP / AD tags, the per-read listings, the RNG mode, the device's own site filters -- is neutral here,
+// so that the contexts are created without any of it and the plan asks no tile for it.  (The site stream keeps the run's own
+// arguments: --rm-invar-sites 1|2|3 and -explode act there, as on the host path.)
+static Args true_values_args(const Args& a) {
+    Args r = a;
+    r.depth = 1.0; r.depths.clear(); r.depths_fn.clear();
+    r.error_rate = 0.01; r.error_qs = 0; r.beta_variance = -1.0; r.qs_bins.clear(); r.qs_bins_fn.clear();
+    r.gl_model = 2; r.precise_gl = 0; r.adjust_qs = 0; r.i16_mapq = 20;
+    r.rm_invar = 0; r.rm_empty = 0;
+    r.add_fmt_dp = r.add_info_dp = r.add_fmt_ad = r.add_info_ad = r.add_fmt_adf = r.add_info_adf = r.add_fmt_adr = r.add_info_adr = r.add_qs = r.add_i16 = 0;
+    r.print_bpe = r.print_qs_err = r.print_gl_err = r.print_qscores = 0;
+    r.rng_mode = VGL_RNG_TILE; r.beta_sampler = VGL_BETA_RAND48;
+    return r;
+}
+
 static RunPlan make_plan(const Args& a, const vgl_params& p, int N, int enc_threads) {
     RunPlan P;
     P.N = N; P.mode = a.output_mode[0]; P.ext = output_ext(a);
@@ -53,7 +70,7 @@ static RunPlan make_plan(const Args& a, const vgl_params& p, int N, int enc_thre
         const int64_t per_site = vgl_pileup_bound(N, 1, P.pile_cap);
         P.TS = std::max(1, (int)std::min<int64_t>(P.TS, (int64_t)(256u << 20) / std::max<int64_t>(per_site, 1)));
     }
-    P.fetch = a.fetch; P.setal = !a.set_alleles_fn.empty();
+    P.fetch = a.fetch; P.setal = !a.set_alleles_fn.empty(); P.inf = a.device_inf != 0;
     if (P.fetch) {                                               // the fetched text of a tile: at most 256 MiB per ring entry, as the pileup's
         const int64_t per_site = vgl_fetchgl_bound(N, 1);
         P.TS = std::max(1, (int)std::min<int64_t>(P.TS, (int64_t)(256u << 20) / std::max<int64_t>(per_site, 1)));
@@ -104,6 +121,7 @@ template <class T> struct PBuf {
 // ---- tile buffers (host side of vgl_tile_out): the union of what the modes need; allocate() makes what the plan asks for
 struct TileBufs {
     int ns = 0; int64_t t0 = 0; int dev = 0;
+    long bad_pos = -1;                        // --device-inf 1: the position of the tile's first site without complete A/C/G/T genotypes
     std::vector<SiteMeta> meta; std::vector<uint8_t> gt;
     // outputs live in page-locked memory (vgl_host_alloc): the device writes them by DMA while the next tile is computed
     PBuf<uint8_t> reads;
@@ -137,7 +155,7 @@ struct TileBufs {
             ft.text = ftext.data(); ft.text_cap = cap; ft.offsets = foff.data();
         }
         if (P.rec0) return;                                      // (the per-site status and alleles above: a few bytes per site, for the run's summary)
-        idp.resize(TS, device); o.info_dp = idp.data();         // also tells which sites reach the read loop (TSV dumps)
+        if (!P.inf) { idp.resize(TS, device); o.info_dp = idp.data(); }         // also tells which sites reach the read loop (TSV dumps)
         if (a.add_info_ad) { iad.resize(TS * A, device); o.info_ad = iad.data(); }
         if (a.add_info_adf) { iadf.resize(TS * A, device); o.info_adf = iadf.data(); }
         if (a.add_info_adr) { iadr.resize(TS * A, device); o.info_adr = iadr.data(); }

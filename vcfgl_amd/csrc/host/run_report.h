@@ -137,6 +137,8 @@ static void verbose_report(const Args& a, const RunPlan& P, const std::vector<vg
 // the summary on stderr and, with the list of the files written, at the end of the run log
 static void finish_run(const Args& a, const RunPlan& P, RunLog& runlog, const size_t n_sites_total, const TileWriter& w) {
     char sb[512];
+    if (P.inf) snprintf(sb, sizeof sb, "\n\n-> Simulation finished successfully.\n\nSummary:\n\tNumber of samples: %d\n\tTotal number of sites simulated: %zu\n", P.N, n_sites_total);   // (run_depth_inf's block)
+    else
     snprintf(sb, sizeof sb, "\n\n-> Simulation finished successfully.\n\nSummary:\n\tNumber of samples: %d\n\tTotal number of sites simulated: %zu\n"
                             "\tNumber of sites included in simulation output file: %ld\n\tNumber of sites skipped: %ld\n", P.N, n_sites_total, w.n_out, w.n_skipped);
     fputs(sb, stderr);

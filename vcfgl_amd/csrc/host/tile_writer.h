@@ -33,7 +33,7 @@ struct TileWriter {
     // the record file, the pileup file and the first lines of the listings on stdout
     void open(const std::vector<vgl_ctx*>& ctxs) {
         // BGZF compression threads: --threads as in the reference; when it is not given, up to 8 (same bytes either way)
-        if (!P.rec0) out.open(a.out_prefix + P.ext, P.mode, output_header(a, vcf, false), vcf.samples,
+        if (!P.rec0) out.open(a.out_prefix + P.ext, P.mode, output_header(a, vcf, P.inf), vcf.samples,
                               a.threads_given ? a.threads : (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())), P.bgzf_dev);
         if (P.bcf) {                                                // dictionary ids of the FORMAT keys: the device writes them as typed keys
             const char* keys[7] = {"DP", "GL", "PL", "GP", "AD", "ADF", "ADR"};
@@ -117,8 +117,9 @@ struct TileWriter {
         const size_t sN = (size_t)N, sG = (size_t)nG, sA = (size_t)nA;
         if (a.add_fmt_dp) fmt.push_back({"DP", false, 1, &B.dp[(size_t)i * N], 1, sN});
         if (a.add_gl) fmt.push_back({"GL", true, nG, &B.gl[(size_t)i * G * N], sG, 1});
+        if (a.add_gp && P.inf) fmt.push_back({"GP", true, nG, &B.gp[(size_t)i * G * N], sG, 1});     // (true values: GL, GP, PL -- vcfgl.cpp:1243-1259)
         if (a.add_pl) fmt.push_back({"PL", false, nG, &B.pl[(size_t)i * G * N], sG, 1});
-        if (a.add_gp) fmt.push_back({"GP", true, nG, &B.gp[(size_t)i * G * N], sG, 1});
+        if (a.add_gp && !P.inf) fmt.push_back({"GP", true, nG, &B.gp[(size_t)i * G * N], sG, 1});
         if (a.add_fmt_ad) fmt.push_back({"AD", false, nA, &B.ad[(size_t)i * A * N], sA, 1});
         if (a.add_fmt_adf) fmt.push_back({"ADF", false, nA, &B.adf[(size_t)i * A * N], sA, 1});
         if (a.add_fmt_adr) fmt.push_back({"ADR", false, nA, &B.adr[(size_t)i * A * N], sA, 1});

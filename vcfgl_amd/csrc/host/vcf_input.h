@@ -661,7 +661,7 @@ static Vcf read_input(const Args& a, const int threads, InputStats& stats) {
     // --device-inflate 1: the inflater's page-locked staging and device buffers are made on that thread too, while the file is read
     vgl_inflate_host* inflater = nullptr; int inflater_rc = VGL_OK; std::string inflater_err;
     const bool want_inflater = a.device_inflate == 1;
-    if (!a.depth_inf) hip_warm = std::thread([warm_dev, want_inflater, &inflater, &inflater_rc, &inflater_err] {
+    if (!a.depth_inf || a.device_inf) hip_warm = std::thread([warm_dev, want_inflater, &inflater, &inflater_rc, &inflater_err] {
         vgl_host_free(vgl_host_alloc_on(warm_dev, 4096));
         if (want_inflater && (inflater_rc = vgl_inflate_host_create(warm_dev, INFLATE_BATCH, &inflater)) != VGL_OK) inflater_err = vgl_last_error();
     });

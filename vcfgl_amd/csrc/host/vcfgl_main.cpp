@@ -9,7 +9,8 @@
 // Records are batched into tiles and simulated on the GPU by vgl_simulate_tile(); there is no
 //   * the gVCF block builder prepare_gvcf_block()         bcf_utils.cpp:662-942
 //   * --depth inf (simulate_record_true_values, vcfgl.cpp:1089-1262): no sampling at all, the true
-//     genotype gets GL 0 / GP 1 / PL 0 and every other genotype -inf / 0 / 255; written directly
+//     genotype gets GL 0 / GP 1 / PL 0 and every other genotype -inf / 0 / 255; written directly (depth_inf.h), or with
+//     --device-inf 1 made on the device (vgl_ctx_true_values) and sent through the device run like simulated tiles
 //   * -printTruth 1: the decoded input records (incl. exploded ones) as <prefix>.truth.vcf
 // CPU simulation path here.  Input: VCF text, gzip / bgzip'd VCF, BCF (raw or BGZF).
 // The units, each a header beside this file: host_util.h (exit, clock, number text), cli_args.h, vcf_input.h, sites.h, gvcf_blocker.h,
@@ -38,7 +39,7 @@ static size_t run_ring(const Args& a, const RunPlan& P, SiteStream& stream, cons
     for (;;) {
         while (!eof && produced - retired < R) {
             TileBufs& B = entry(produced % R);
-            B.ns = 0; B.t0 = (int64_t)n_sites_total; B.done = false; B.dev = (int)(produced % D);
+            B.ns = 0; B.t0 = (int64_t)n_sites_total; B.done = false; B.dev = (int)(produced % D); B.bad_pos = -1;
             while (B.ns < P.TS && stream.next(&B.gt[(size_t)B.ns * P.N], B.meta[B.ns])) B.ns++;
             if (B.ns < P.TS) eof = true;
             if (B.ns == 0) break;
@@ -62,6 +63,7 @@ static size_t run_ring(const Args& a, const RunPlan& P, SiteStream& stream, cons
         TileBufs& B = *ring[consumed % R];
         { std::unique_lock<std::mutex> lk(B.m); B.cv.wait(lk, [&] { return B.done; }); }
         timer.lap(StageTimer::DEVICE_WAIT);
+        if (B.bad_pos >= 0) die("--depth inf needs complete A/C/G/T genotypes (position %ld)", B.bad_pos);
         w.write_tile(B);
         timer.lap(StageTimer::WRITE);
         consumed++;
@@ -73,6 +75,9 @@ static size_t run_ring(const Args& a, const RunPlan& P, SiteStream& stream, cons
     for (auto& W : workers) W->finish();
     return n_sites_total;
 }
+
+static int device_run(const Args& a, const Vcf& vcf, const int N, const int enc_threads, SiteStream& stream, vsink::Sink& truth_sink, RunLog& runlog,
+                      StageTimer& timer, const InputStats& in_stats, const std::vector<int8_t>& setal_table);
 
 // ---------------------------------------------------------------------------------------
 int main(int argc, char** argv) {
@@ -103,9 +108,13 @@ int main(int argc, char** argv) {
         truth_sink.open(a.out_prefix + ".truth" + output_ext(a), a.output_mode[0], truth_header(a, vcf), vcf.samples, 1, bgzf_device(a));
         stream.truth = &truth_sink;
     }
-    if (a.depth_inf) { run_depth_inf(a, vcf, stream, truth_sink, runlog); return 0; }
+    if (a.depth_inf && !a.device_inf) { run_depth_inf(a, vcf, stream, truth_sink, runlog); return 0; }
+    return device_run(a.device_inf ? true_values_args(a) : a, vcf, N, enc_threads, stream, truth_sink, runlog, timer, in_stats, setal_table);
+}
 
-    // ---- the device run: plan, contexts, sinks, workers, the ring
+// ---- the device run: plan, contexts, sinks, workers, the ring
+static int device_run(const Args& a, const Vcf& vcf, const int N, const int enc_threads, SiteStream& stream, vsink::Sink& truth_sink, RunLog& runlog,
+                      StageTimer& timer, const InputStats& in_stats, const std::vector<int8_t>& setal_table) {
     const vgl_params p = make_params(a, N);
     const RunPlan P = make_plan(a, p, N, enc_threads);
     std::vector<vgl_ctx*> ctxs(P.D, nullptr);
@@ -115,6 +124,7 @@ int main(int argc, char** argv) {
     if (P.fetch) for (vgl_ctx* ctx : ctxs) if (vgl_ctx_fetchgl(ctx, a.fetch_a, a.fetch_b, a.fetch_mode) != VGL_OK) die("--fetch-gl %s: %s", a.fetch_gl.c_str(), vgl_last_error());
     const size_t setal_lines = setal_table.size() / 8;
     if (P.setal) for (vgl_ctx* ctx : ctxs) if (vgl_ctx_set_alleles(ctx, setal_table.data(), 0, (int64_t)setal_lines) != VGL_OK) die("--set-alleles %s: %s", a.set_alleles_fn.c_str(), vgl_last_error());
+    if (P.inf) for (vgl_ctx* ctx : ctxs) if (vgl_ctx_true_values(ctx, 1) != VGL_OK) die("--device-inf 1: %s", vgl_last_error());
     timer.lap(StageTimer::CONTEXT);
     TileWriter w(a, P, vcf, timer);
     w.open(ctxs);

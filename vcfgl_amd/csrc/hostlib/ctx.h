@@ -93,7 +93,11 @@ struct HostSlot {
     // vgl_ctx_set_alleles: the tile's arrays are relabelled on the device (vgl_setal.hip) behind its likelihood kernels; d_sbad / h_sbad
     // (pinned) hold the first refused site of the tile, counted from its first site (>= n_sites: none)
     bool setal = false; DevBuf<int32_t> d_sbad; PinBuf<int32_t> h_sbad; DevBuf<uint8_t> d_sws; int64_t sws_bytes = 0;
+    // vgl_ctx_true_values: the tile was filled from its genotypes (vgl_inf.hip); h_ibad (pinned) holds the smallest bad absolute site of
+    // the tile (VGL_INF_NO_BAD_SITE: none)
+    bool inf = false; PinBuf<unsigned long long> h_ibad;
 };
+#define VGL_INF_NO_BAD_SITE (~0ULL)
 
 #define VGL_NEV (VGL_N_TIMING_BUCKETS + 1)
 struct vgl_ctx {
@@ -137,6 +141,11 @@ struct vgl_ctx {
     // vgl_ctx_set_alleles: the target entries (8 bytes each) of the absolute sites setal_first .. setal_first + setal_n - 1 on the device;
     // the sibling context `deep` borrows its parent's
     DevBuf<int8_t> d_setal; int64_t setal_first = 0, setal_n = 0;
+    // vgl_ctx_true_values: tiles are filled from their genotypes (vgl_inf.hip) instead of simulated.  d_inf_ws: the kernels' workspace;
+    // d_inf_bad: the stateless call's tile-relative word; d_inf_abs: the smallest bad absolute site since it was last read
+    // (VGL_INF_NO_BAD_SITE: none); d_inf_nobs: n_alleles_obs of a device tile whose caller does not ask for it
+    bool true_values = false;
+    DevBuf<uint8_t> d_inf_ws{W}; DevBuf<int32_t> d_inf_bad{W}, d_inf_nobs{W}; DevBuf<unsigned long long> d_inf_abs{W};
     // vgl_ctx_bcf_keys: the text / gVCF tile calls deliver BCF typed vectors (vgl_bcf.hip) instead of text; dictionary ids of
     // DP, GL, PL, GP, AD, ADF, ADR
     bool bcf = false; int32_t bcf_keys[7] = {0, 0, 0, 0, 0, 0, 0};

@@ -52,14 +52,17 @@ static int deliver_text(vgl_ctx* c, const TextNames& what, int64_t cap, uint8_t*
 
 // ---- record text / BCF typed vectors (vgl_text.hip, vgl_bcf.hip) --------------------------------------------------------------------
 // The FORMAT tags vgl_simulate_tile_text_async formats, in add_tags()'s order (bcf_utils.cpp:426-507): DP, GL, PL, GP, AD, ADF, ADR.
+// vgl_ctx_true_values: GL, GP, PL, the order simulate_record_true_values adds them in (vcfgl.cpp:1243-1259).
 // Returns their count; fid[k] = index into FIELDS.
 static int text_fields(const vgl_ctx* c, vgl_text_field* tf, int* fid) {
     struct T { int on; const char* key; int is_float; int count; int f; };
     const T all[] = {{c->p.add_fmt_dp, "DP", 0, VGL_TEXT_ONE, 10}, {c->p.add_gl, "GL", 1, VGL_TEXT_PER_G, 11}, {c->p.add_pl, "PL", 0, VGL_TEXT_PER_G, 12},
                      {c->p.add_gp, "GP", 1, VGL_TEXT_PER_G, 13}, {c->p.add_fmt_ad, "AD", 0, VGL_TEXT_PER_A, 14},
                      {c->p.add_fmt_adf, "ADF", 0, VGL_TEXT_PER_A, 15}, {c->p.add_fmt_adr, "ADR", 0, VGL_TEXT_PER_A, 16}};
+    static const int ORDER[2][7] = {{0, 1, 2, 3, 4, 5, 6}, {0, 1, 3, 2, 4, 5, 6}};
     int n = 0;
-    for (const T& t : all) {
+    for (const int k : ORDER[c->true_values ? 1 : 0]) {
+        const T& t = all[k];
         if (!t.on) continue;
         tf[n].key = t.key; tf[n].is_float = t.is_float; tf[n].count = t.count; tf[n].base = nullptr;
         tf[n].site_stride = (int64_t)field_count(c, FIELDS[t.f].kind, 1);
@@ -405,6 +408,32 @@ static int enqueue_setal(vgl_ctx* c, HostSlot& S, int64_t site0, int32_t n_sites
     HIPCHK(hipMemcpyAsync(S.h_sbad, S.d_sbad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     return VGL_OK;
 }
+// ---- tiles filled from their true genotypes instead of simulated (vgl_inf.hip; the tile itself: true_values_tile, tile_device.h) -----
+extern "C" int vgl_ctx_true_values(vgl_ctx* c, int32_t on) {
+    if (!c) return fail(VGL_E_ARG, "vgl_ctx_true_values: null context");
+    for (const auto& S : c->slot) if (S.busy) return fail(VGL_E_ARG, "vgl_ctx_true_values: a tile of the context is in flight");
+    if (!on) { c->true_values = false; return VGL_OK; }
+    const vgl_params& p = c->p;
+    if (p.add_fmt_dp || p.add_info_dp || p.add_fmt_ad || p.add_info_ad || p.add_fmt_adf || p.add_info_adf || p.add_fmt_adr || p.add_info_adr || p.add_qs || p.add_i16)
+        return fail(VGL_E_ARG, "vgl_ctx_true_values: the context writes DP, AD, ADF, ADR, QS or I16 tags, which true values do not define (no read is drawn)");
+    VGLCHK(true_values_ctx_ok(c, "vgl_ctx_true_values"));
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_inf_abs) {
+        VGLCHK(c->d_inf_ws.reserve((size_t)vgl_inf_workspace_bytes(c->dp.n_samples, c->max_sites)));
+        VGLCHK(c->d_inf_bad.reserve(1)); VGLCHK(c->d_inf_abs.reserve(1));
+        HIPCHK(hipMemset(c->d_inf_abs, 0xFF, sizeof(unsigned long long)));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    c->true_values = true;
+    return VGL_OK;
+}
+// the tile's smallest bad site into S.h_ibad, and a clean word for the next tile (compute stream)
+static int enqueue_true_values_rc(vgl_ctx* c, HostSlot& S) {
+    HIPCHK(hipMemcpyAsync(S.h_ibad, c->d_inf_abs, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
+    HIPCHK(hipMemsetAsync(c->d_inf_abs, 0xFF, sizeof(unsigned long long), c->s_compute));
+    return VGL_OK;
+}
+
 static int setal_rc(HostSlot& S) {
     if (!S.setal || !S.h_sbad || *S.h_sbad < 0 || *S.h_sbad >= S.n_sites) return VGL_OK;
     return fail(VGL_E_SETAL, "site %lld: the target allele list names an allele the record does not have (misc/setAlleles is undefined there)",

@@ -17,6 +17,7 @@ static uint32_t wanted_fields(const vgl_ctx* c, const HostSlot& S, vgl_tile_out*
     if (S.fetch) mask |= 1u << 11;                                     // (the fetch-GL formatter reads FORMAT/GL)
     if (S.setal && (o->pl_u8 || (mask >> 17 & 1u))) mask |= 1u << 10;  // (the one-byte PL is relabelled by FORMAT/DP == 0)
     if (S.setal) mask |= 1u << 0 | 1u << 1 | 1u << 3;
+    if (S.inf) mask |= 1u << 0 | 1u << 1 | 1u << 2 | 1u << 3;          // (the fill writes all four per-site arrays)
     for (int f = 0; f < N_FIELDS; f++) if (field_ptr(o, f)) mask |= 1u << f;
     return mask;
 }
@@ -74,6 +75,7 @@ static int enqueue_host_tile(vgl_ctx* c, HostSlot& S, int64_t site0, int32_t n_s
     if (rc != VGL_OK) return rc;
     if (S.gvcf && (rc = stage_gvcf(c, S, n_sites, contig, pos0)) != VGL_OK) return rc;
     if ((rc = vgl_simulate_tile_device(c, site0, n_sites, S.d_gt, &d, c->s_compute))) return rc;
+    if (S.inf && (rc = enqueue_true_values_rc(c, S)) != VGL_OK) return rc;
     if (S.setal && (rc = enqueue_setal(c, S, site0, n_sites, d, c->s_compute)) != VGL_OK) return rc;
     if (S.pile && (rc = enqueue_pileup(c, S, n_sites, d)) != VGL_OK) return rc;
     if (S.fetch && (rc = enqueue_fetchgl(c, S, n_sites)) != VGL_OK) return rc;
@@ -121,6 +123,13 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     if (want_text && c->p.out_layout != VGL_LAYOUT_SAMPLE_MAJOR) return fail(VGL_E_ARG, "vgl_simulate_tile_text_async: the context needs out_layout = VGL_LAYOUT_SAMPLE_MAJOR");
     if (n_sites < 0 || n_sites > c->max_sites) return fail(VGL_E_ARG, "n_sites %d exceeds max_sites_per_tile %d", n_sites, c->max_sites);
     if (n_sites > 0 && !gt) return fail(VGL_E_ARG, "null gt");
+    if (c->true_values) {
+        if (gq) return fail(VGL_E_ARG, "vgl_simulate_tile_gvcf_async: not supported while vgl_ctx_true_values is on (the reference writes no gVCF from true values)");
+        if (pile) return fail(VGL_E_ARG, "vgl_ctx_pileup_next: not supported while vgl_ctx_true_values is on (no read is drawn: there is no pileup)");
+        if (fetch) return fail(VGL_E_ARG, "vgl_ctx_fetchgl_next: not supported while vgl_ctx_true_values is on");
+        VGLCHK(true_values_ctx_ok(c, "vgl_ctx_true_values is on"));
+        VGLCHK(true_values_outputs_ok(o));
+    }
     if (c->d_setal && gq) return fail(VGL_E_ARG, "vgl_simulate_tile_gvcf_async: not supported while vgl_ctx_set_alleles is set");
     if (c->d_setal && n_sites > 0 && (site0 < c->setal_first || site0 + n_sites > c->setal_first + c->setal_n))
         return fail(VGL_E_ARG, "the tile's sites %lld .. %lld are not all inside vgl_ctx_set_alleles' table (%lld .. %lld)", (long long)site0, (long long)(site0 + n_sites - 1),
@@ -141,6 +150,8 @@ static int tile_async(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t*
     S.pile = pile;
     S.fetch = fetch;
     S.setal = c->d_setal && n_sites > 0;
+    S.inf = c->true_values && n_sites > 0;
+    if (S.inf) { VGLCHK(S.h_ibad.reserve(1)); *S.h_ibad = VGL_INF_NO_BAD_SITE; }
     if (pile) { const int rc = pileup_qual_char(c, &S.pile_qc); if (rc != VGL_OK) { S.pile = nullptr; S.fetch = nullptr; return rc; } }
     if (gq) S.dps.assign(gq->dps, gq->dps + gq->n_dps);
     if (want_text || gq || pile || fetch) VGLCHK(c->s_text.create());
@@ -263,6 +274,7 @@ extern "C" int vgl_tile_wait(vgl_ctx* c, int32_t ticket) {
         if (rc == VGL_E_CAPACITY) return flags_to_rc(c, *S.h_flag);
     } else {
         VGLCHK(flags_to_rc(c, *S.h_flag));
+        if (S.inf) VGLCHK(true_values_rc(*S.h_ibad));
         VGLCHK(setal_rc(S));
         if (S.pile) VGLCHK(finish_pileup(c, S));
     }

@@ -75,6 +75,42 @@ static void fill_tile_ptrs(const vgl_ctx* c, int64_t site0, int32_t n_sites, con
     T.reads_out_cap = o->read_capacity > 0 ? (o->read_capacity < D.read_cap ? o->read_capacity : D.read_cap) : 0;
 }
 
+// ---- vgl_ctx_true_values: a tile filled from its genotypes (vgl_inf.hip) instead of simulated ----------------------------------------
+extern "C" int vgl_inf_fill_impl(int32_t device, int32_t n_samples, int32_t n_sites, int32_t do_unobserved, int32_t max_genotypes, int32_t max_alleles,
+                                 int32_t layout, const uint8_t* gt, int32_t* site_status, int32_t* n_alleles, int32_t* n_alleles_obs, int8_t* alleles2acgt,
+                                 float* gl, int32_t* pl, float* gp, uint8_t* pl_u8, int32_t* bad_site, void* workspace, int64_t workspace_bytes,
+                                 int64_t site0, unsigned long long* bad_abs, void* hip_stream);       // vgl_inf.hip (not exported)
+
+// the outputs a true-value tile does not define
+static int true_values_outputs_ok(const vgl_tile_out* o) {
+    if (o->info_dp || o->info_ad || o->info_adf || o->info_adr || o->qs || o->i16 || o->fmt_dp || o->fmt_ad || o->fmt_adf || o->fmt_adr || o->reads ||
+        o->read_errp || o->site_pick_err)
+        return fail(VGL_E_ARG, "vgl_ctx_true_values is on: no read is drawn, so DP, AD, ADF, ADR, QS, I16, the read dumps and site_pick_err are not defined (their vgl_tile_out pointers must be NULL)");
+    return VGL_OK;
+}
+// what else a context in that mode does not compose with (`who`: the entry point that reports it)
+static int true_values_ctx_ok(const vgl_ctx* c, const char* who) {
+    if (c->disc) return fail(VGL_E_ARG, "%s: not supported together with vgl_ctx_discordance (every call would be the truth)", who);
+    if (c->fetch_a >= 0) return fail(VGL_E_ARG, "%s: not supported together with vgl_ctx_fetchgl", who);
+    if (c->d_setal) return fail(VGL_E_ARG, "%s: not supported together with vgl_ctx_set_alleles", who);
+    return VGL_OK;
+}
+
+static int true_values_tile(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt, vgl_tile_out* o, hipStream_t st) {
+    VGLCHK(true_values_outputs_ok(o));
+    VGLCHK(true_values_ctx_ok(c, "vgl_ctx_true_values is on"));
+    HIPCHK(hipSetDevice(c->device));
+    int32_t* nobs = o->n_alleles_obs;
+    if (!nobs) { VGLCHK(c->d_inf_nobs.reserve((size_t)c->max_sites)); nobs = c->d_inf_nobs; }
+    HIPCHK(hipMemsetAsync(c->d_inf_bad, 0x7F, sizeof(int32_t), st));
+    return vgl_inf_fill_impl(c->device, c->dp.n_samples, n_sites, c->p.do_unobserved, c->dp.G, c->dp.A, c->dp.out_layout, gt, o->site_status, o->n_alleles, nobs,
+                             o->alleles2acgt, o->gl, o->pl, o->gp, o->pl_u8, c->d_inf_bad, c->d_inf_ws, (int64_t)c->d_inf_ws.bytes(), site0, c->d_inf_abs, st);
+}
+static int true_values_rc(unsigned long long bad) {
+    if (bad == VGL_INF_NO_BAD_SITE) return VGL_OK;
+    return fail(VGL_E_ARG, "site %llu: a true genotype is not a pair of A, C, G, T (true values need complete genotypes)", bad);
+}
+
 extern "C" int vgl_simulate_tile_device(vgl_ctx* c, int64_t site0, int32_t n_sites, const uint8_t* gt,
                                         vgl_tile_out* o, void* stream) {
     if (!c || !o) return fail(VGL_E_ARG, "null argument");
@@ -82,6 +118,7 @@ extern "C" int vgl_simulate_tile_device(vgl_ctx* c, int64_t site0, int32_t n_sit
     if (n_sites == 0) return VGL_OK;
     if (!gt || !o->site_status || !o->n_alleles || !o->alleles2acgt) return fail(VGL_E_ARG, "gt, site_status, n_alleles and alleles2acgt are required");
     if (site0 < 0) return fail(VGL_E_ARG, "site0 must be >= 0");
+    if (c->true_values) return true_values_tile(c, site0, n_sites, gt, o, (hipStream_t)stream);
     if (!c->dp.serial) {
         // VGL_RNG_TILE windows are slices of ONE rand48 sequence of period 2^48: evaluation (site, sample) owns draws
         // [e block, (e + 1) block), e = H(site) n_samples + sample, H a permutation of [0, 2^W).  Past 2^W sites the windows would
@@ -193,10 +230,14 @@ extern "C" int vgl_ctx_check(vgl_ctx* c, void* stream) {
     if (!c) return fail(VGL_E_ARG, "null ctx");
     HIPCHK(hipSetDevice(c->device));
     uint32_t flag = 0;
+    unsigned long long bad = VGL_INF_NO_BAD_SITE;                   // vgl_ctx_true_values: the smallest bad site of the tiles since the last check
     HIPCHK(hipMemcpyAsync(&flag, c->d_errflag, sizeof flag, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (c->d_inf_abs) HIPCHK(hipMemcpyAsync(&bad, c->d_inf_abs, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (flag) HIPCHK(hipMemsetAsync(c->d_errflag, 0, sizeof flag, (hipStream_t)stream));
-    return flags_to_rc(c, flag);
+    if (bad != VGL_INF_NO_BAD_SITE) HIPCHK(hipMemsetAsync(c->d_inf_abs, 0xFF, sizeof bad, (hipStream_t)stream));
+    VGLCHK(flags_to_rc(c, flag));
+    return true_values_rc(bad);
 }
 
 #ifdef VGL_TEST_HOOKS

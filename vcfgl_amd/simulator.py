@@ -172,6 +172,13 @@ class Simulator:
             raise ValueError("table is int8 [n_sites][8]")
         self._check(self.lib.vgl_ctx_set_alleles(self.ctx, t.ctypes.data, int(first_site), t.shape[0]))
 
+    def true_values(self, on=1):
+        """vgl_ctx_true_values: every following tile of this context is filled from its true genotypes (--depth inf: GL 0 / GP 1 / PL 0
+        at the true genotype, -inf / 0 / 255 elsewhere; vcfgl_amd.truevals) instead of simulated.  Ask such a tile only for
+        site_status, n_alleles, n_alleles_obs, alleles2acgt, gl, pl, gp and pl_u8.  A genotype that is not a pair of A, C, G, T makes
+        `simulate` / `check` raise VglError(VGL_E_ARG) naming the site."""
+        self._check(self.lib.vgl_ctx_true_values(self.ctx, 1 if on else 0))
+
     def close(self):
         if getattr(self, "ctx", None):
             self.lib.vgl_ctx_destroy(self.ctx)
