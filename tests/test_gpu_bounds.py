@@ -146,3 +146,68 @@ def test_fixed_point_score_decision_every_float_probability(adjust_by):
     print(f"qs_fix adjust_by {adjust_by}: {r['n']} of {n_all} arguments decided, violations {r['violations']}")
     assert r["violations"] == 0, r
     assert r["n"] > 0.02 * n_all          # (p >= 4e-7, i.e. tf < 64, is 2.3 % of the float32 values below 1; all of them but a band of 3.7e-4 per score)
+
+
+# ---- the GL output tail: pl_of, exp10_nonpos, log10_unit and div_inrange on the operands of the GL side (tests/test_gpu_gl_tail.py holds
+# ---- the same helpers to mpmath / exact rationals on up to 1e5 arguments each; here the whole domain, against the device's own double functions)
+PL_OF, EXP10_F32, LOG10_UNIT, DIV_LOG, DIV_GAMMA = range(14, 19)
+NEG_ZERO, NEG_INF = 0x80000000, 0xFF800000
+
+
+def test_pl_of_equals_lroundf_for_every_nonpositive_float():
+    """k_gl / k_gl2 tails: pl_of(gl) == the reference's `x = lroundf(-10.0 * gl); if (x > MAXPL) x = MAXPL` (vcfgl.cpp:931-934; -inf: MAXPL)
+    for EVERY float32 gl from -0 to -inf (2 139 095 041 patterns) and +0; valid = false gives the int32 missing pattern; the byte form
+    v > 255 ? 255 : v equals the capped value (255 for missing)"""
+    r = sweep(PL_OF, NEG_ZERO, NEG_INF)
+    print(f"pl_of: {r['n']} arguments, violations {r['violations']} (one at bits 0x{r['arg_bits']:08x})")
+    assert r["n"] == NEG_INF - NEG_ZERO + 1 == 2_139_095_041 and r["violations"] == 0, r
+    z = sweep(PL_OF, 0, 0)
+    assert z["n"] == 1 and z["violations"] == 0, z
+
+
+def test_pl_of_the_one_float_where_trunc_of_x_plus_half_is_wrong():
+    """gl = -0x1.999998p-5: x = -10 gl = 0x1.fffffep-2 = 0.5 - 2^-25 and x + 0.5f rounds to 1.0 -- lroundf gives 0, and so must pl_of (its
+    one compare); the float next to it towards zero gives 0 as well, the one away from zero (x = 0.5 + 2^-24) gives 1.  Each as a sweep of
+    one argument, and through the dump entry for the values themselves."""
+    g = f2b(float.fromhex("-0x1.999998p-5"))
+    assert struct.unpack("<f", struct.pack("<I", g))[0] * -10.0 == float.fromhex("0x1.fffffep-2")
+    for bits in (g - 1, g, g + 1):
+        r = sweep(PL_OF, bits, bits)
+        assert r["n"] == 1 and r["violations"] == 0, (hex(bits), r)
+    lib = _abi.load_library(hooks=True)
+    lib.vgl_dbg_gl_tail.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong]
+    x = (C.c_uint32 * 3)(g - 1, g, g + 1)
+    out = (C.c_uint32 * 3)()
+    assert lib.vgl_dbg_gl_tail(2, x, out, 3) == 0
+    assert list(out) == [0, 0, 1], list(out)
+
+
+def test_exp10_nonpos_float_criterion_for_every_nonpositive_float():
+    """GP: (float)exp10_nonpos((double)x) against (float)pow(10.0, x) for EVERY float32 x from -0 to -inf, DESIGN section 6's float criterion:
+    never more than one unit in the last place of float32 apart (subnormal results included), at most a share of 1e-5 of the finite
+    nonzero results not identical (the count is printed), zero for every x whose pow rounds to zero; and the double result within 1e-15
+    relative of pow's for x >= -300 (the worst ratio is printed)"""
+    r = sweep(EXP10_F32, NEG_ZERO, NEG_INF, param=0.0)
+    check("exp10_nonpos (double, x >= -300, bound 1e-15)", r, 2_139_095_041)
+    c = sweep(EXP10_F32, NEG_ZERO, NEG_INF, param=1.0)
+    nonid = int(c["max_ratio"])
+    print(f"exp10_nonpos float32: {nonid} of {c['n']} finite nonzero results not identical to (float)pow (one at bits 0x{c['arg_bits']:08x}), violations {c['violations']}")
+    assert c["violations"] == 0 and 1.0e9 < c["n"] < 1.2e9, c          # (the floats from -0 down to -45.15: 0x80000000 ... 0xC2349E35)
+    assert nonid <= 1e-5 * c["n"], c
+
+
+def test_log10_unit_bound_on_the_unit_interval():
+    """--precise-gl 1: |log10_unit(x) - log10(x)| <= 1e-15 |log10(x)| on 2^32 doubles of (0, 1] -- random mantissas at every exponent from
+    the subnormals up, every eighth within 2^-40 of sqrt(1/2) 2^k or of 1, and the read loop's 1 - e, (1 - e) / 2 + e / 6, e / 3 for e from
+    0.75 down to 4e-17 -- exactly +0 at x = 1 and -inf at x = 0"""
+    r = sweep(LOG10_UNIT, 0, 0, param=0.0, count=1 << 32)
+    check("log10_unit (bound 1e-15; worst at index, not bits)", r, 4.2e9)
+
+
+@pytest.mark.parametrize("mode,name", [(DIV_LOG, "(m - 1, m + 1), m in [sqrt(1/2), sqrt(2))"), (DIV_GAMMA, "(g, g + v), gamma deviates of shapes 8 ... 2e5")])
+def test_div_inrange_equals_ieee_division_on_the_gl_side_operands(mode, name):
+    """div_inrange is also log10_unit's quotient (m - 1) / (m + 1) and the deferred build's read_errp = gx / (gx + val): bit for bit the
+    compiler's IEEE quotient on 2^32 pairs of each family (vgl_bounds.hip: k_bound_div2)"""
+    r = sweep(mode, 0, 0, count=1 << 32)
+    print(f"div_inrange {name}: {r['n']} pairs, violations {r['violations']} (last at index {r['arg_bits']})")
+    assert r["n"] == 1 << 32 and r["violations"] == 0, r

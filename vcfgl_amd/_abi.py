@@ -179,7 +179,7 @@ class PackPlan(C.Structure):
     _fields_ = [("n_kept", C.c_int64), ("rows_g", C.c_int64), ("rows_a", C.c_int64)]
 
 # entry points of the -DVGL_TEST_HOOKS build only (lib/libvcfgl_hip_hooks.so): never in the shipped library
-HOOK_EXPORTS = ["vgl_dbg_bound_sweep", "vgl_dbg_chain", "vgl_dbg_redo_count", "vgl_dbg_site_base", "vgl_dbg_stamps", "vgl_dbg_vlog"]
+HOOK_EXPORTS = ["vgl_dbg_bound_sweep", "vgl_dbg_chain", "vgl_dbg_gl_tail", "vgl_dbg_redo_count", "vgl_dbg_site_base", "vgl_dbg_stamps", "vgl_dbg_vlog"]
 
 _LIB = {}
 

@@ -25,10 +25,16 @@ enum {
     VGL_BOUND_POISSON = 11,     // poisson_fast == poisson_exact wherever it does not call the attempt ambiguous (param = mean depth; count = attempts)
     VGL_BOUND_POOL32 = 12,      // the float32 pool loop of k_sample<2>: every decision it takes equals the float64 one, values within their bounds (param = shape alpha >= 8; count = attempts)
     VGL_BOUND_QS_FIX = 13,      // qs_decide_fix: every float32 p it decides has ONE score over the whole interval its true value can lie in (param = adjust_by, 0 = none)
+    VGL_BOUND_PL_OF = 14,       // pl_of == lround(-10 gl) capped at MAXPL for every float32 gl of the sweep; the missing pattern; the byte form (k_gl / k_gl2 tails)
+    VGL_BOUND_EXP10_F32 = 15,   // (float)exp10_nonpos((double)x) against (float)pow(10.0, x) for every float32 x <= 0 (GP); param 0: worst relative error of the
+                                // double result / 1e-15 (x >= -300), param 1: n = finite nonzero results, out[2] = how many of them are not identical
+    VGL_BOUND_LOG10_UNIT = 16,  // log10_unit against log10 on doubles of (0, 1] (--precise-gl 1; count = arguments, param = 0.0: the argument of the x = 0 / x = 1 cases)
+    VGL_BOUND_DIV_LOG = 17,     // div_inrange == IEEE quotient for (m - 1, m + 1), m in [sqrt(1/2), sqrt(2)) as log10_unit forms it (count = pairs)
+    VGL_BOUND_DIV_GAMMA = 18,   // div_inrange == IEEE quotient for (g, g + v), g and v of the size of gamma deviates of shapes 8 ... 2e5 (read_errp of the deferred build; count = pairs)
     VGL_BOUND_N
 };
 
-struct BoundAcc { unsigned long long n, viol, max_ratio_bits, arg_bits; };
+struct BoundAcc { unsigned long long n, viol, max_ratio_bits, arg_bits, aux; };
 
 __device__ __forceinline__ void acc_update(double& mr, uint32_t& arg, unsigned long long& viol, const double err, const double bound, const uint32_t bits) {
     // ratio err / bound; a non-positive bound with a non-zero error is a violation outright
@@ -40,7 +46,7 @@ __device__ __forceinline__ void acc_update(double& mr, uint32_t& arg, unsigned l
 template <int MODE>
 __global__ __launch_bounds__(256) void k_bound_sweep(const uint32_t lo, const unsigned long long count, const double param, BoundAcc* out) {
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-    double mr = 0.0; uint32_t arg = 0; unsigned long long viol = 0, n = 0;
+    double mr = 0.0; uint32_t arg = 0; unsigned long long viol = 0, n = 0, aux = 0;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
         const uint32_t bits = lo + (uint32_t)i;
         const float x = __uint_as_float(bits);
@@ -60,6 +66,28 @@ __global__ __launch_bounds__(256) void k_bound_sweep(const uint32_t lo, const un
             // exact equality wanted: error 0 against a bound of 0 passes, anything else is a violation (acc_update)
             const float want = (float)(xd / 10.0);
             acc_update(mr, arg, viol, (__float_as_uint(div10_f32(x)) == __float_as_uint(want)) ? 0.0 : 1.0, 0.0, bits);
+        } else if (MODE == VGL_BOUND_PL_OF) {
+            // the reference's x = lroundf(-10.0 * gl); if (x > MAXPL) x = MAXPL (vcfgl.cpp:931-934; gl = -inf: MAXPL, :923), the cap taken first so
+            // that the conversion stays in range: the double product rounded to float as lroundf's argument is, then round-half-away in double
+            const float xf = (float)(-10.0 * xd);
+            const long want = lround(fmin((double)xf, (double)MAXPL));
+            const uint32_t got = pl_of(x, true), miss = pl_of(x, false);
+            const uint8_t b = (uint8_t)(got > 255u ? 255u : got), bm = (uint8_t)(miss > 255u ? 255u : miss);      // pl_u8 as the tails form it
+            const bool good = (long)got == want && miss == (uint32_t)I32_MISSING && (long)b == want && bm == 255u;
+            acc_update(mr, arg, viol, good ? 0.0 : 1.0, 0.0, bits);
+        } else if (MODE == VGL_BOUND_EXP10_F32) {
+            // DESIGN section 6's float criterion against the device's pow: never more than one unit in the last place of float32 apart (subnormal
+            // results included: non-negative floats order like their bits), zero wherever the reference rounds to zero; the count of
+            // non-identical results among the finite nonzero ones goes to the caller.  The double result within 1e-15 of pow's for x >= -300.
+            const double a = exp10_nonpos(xd), r = pow(10.0, xd);
+            const float af = (float)a, rf = (float)r;
+            const uint32_t ab = __float_as_uint(af), rb = __float_as_uint(rf);
+            const uint32_t dist = ab > rb ? ab - rb : rb - ab;
+            const bool nz = rf != 0.0f;
+            if (nz && ab != rb) { ++aux; if (param != 0.0) arg = bits; }
+            if (dist > 1u || (!nz && ab != 0u)) ++viol;
+            if (param != 0.0) { if (!nz) --n; }
+            else if (x >= -300.0f) acc_update(mr, arg, viol, fabs(a - r), r * 1e-15, bits);
         } else if (MODE == VGL_BOUND_GAMMA_SERIES || MODE == VGL_BOUND_GAMMA_REFEXPR) {
             if (!(fabsf(x) <= 0.3333f)) { --n; continue; }
             const float a1f = (float)param;
@@ -118,6 +146,8 @@ __global__ __launch_bounds__(256) void k_bound_sweep(const uint32_t lo, const un
             acc_update(mr, arg, viol, fabs((double)e - ex), ex * (0x1p-19 - 0x1p-22), bits);
         }
     }
+    if (MODE == VGL_BOUND_EXP10_F32 && aux) { atomicAdd(&out->aux, aux); if (param != 0.0) out->arg_bits = arg; }
+    if (MODE == VGL_BOUND_EXP10_F32 && viol && !n) atomicAdd(&out->viol, viol);
     if (n) {
         atomicAdd(&out->n, n);
         if (viol) atomicAdd(&out->viol, viol);
@@ -153,6 +183,115 @@ __global__ __launch_bounds__(256) void k_bound_div(const unsigned long long coun
     }
     atomicAdd(&out->n, n);
     if (viol) { atomicAdd(&out->viol, viol); out->arg_bits = arg; }
+}
+
+// a double with the 52 mantissa bits of h below the leading one: [1, 2)
+__device__ __forceinline__ double mant52(const uint64_t h) { return __longlong_as_double((long long)(0x3FF0000000000000ULL | (h & 0xFFFFFFFFFFFFFULL))); }
+// x moved by `ulps` units in its last place (finite positive x away from the exponent limits)
+__device__ __forceinline__ double nudge(const double x, const long long ulps) { return __longlong_as_double(__double_as_longlong(x) + ulps); }
+
+// div_inrange against the compiler's IEEE division on the two operand families of the GL side (k_bound_div keeps the sampler's):
+// FAM 0  (m - 1, m + 1) as log10_unit forms them: a frexp mantissa f in [1/2, 1) with 52 random bits, doubled below sqrt(1/2), so m in [sqrt(1/2), sqrt(2));
+//        every 8th pair next to the switch (f within 2^12 units in the last place of sqrt(1/2), either side) or next to m = 1 (m = 1 itself included);
+// FAM 1  (g, g + v): g = a (1 + r) 2^k with a, and independently the a' of v, one of the beta shapes of
+//        test_float32_pool_loop_decisions_equal_the_float64_ones (8, 9.889, 55.5, 979.011, 2e5; the deferred build runs with both >= 8), r 52 random
+//        bits and k in -4 .. 2 -- a gamma deviate of shape a lies within a few sqrt(a) of a --, so that g / (g + v) spans 2e-7 .. 1 - 2e-7.
+template <int FAM>
+__global__ __launch_bounds__(256) void k_bound_div2(const unsigned long long count, BoundAcc* out) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    unsigned long long viol = 0, n = 0; uint32_t arg = 0;
+    const double shapes[5] = {8.0, 9.889, 55.5, 979.011, 2.0e5};
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        const uint64_t h1 = mix64(i * 2 + 1), h2 = mix64(i * 2 + 2);
+        double nn, dd;
+        if (FAM == 0) {
+            double f = 0.5 * mant52(h1);
+            if ((i & 7) == 7) {
+                const long long off = (long long)(h2 & 0x1FFF) - 4096;
+                if ((i >> 3) & 1) f = nudge(0.70710678118654752, off);
+                else f = (off < 0) ? nudge(1.0, off) : nudge(0.5, off);      // m = 1 - j 2^-53, or (doubled) m = 1 + j 2^-52
+            }
+            const bool lo = f < 0.70710678118654752;
+            const double m = lo ? f + f : f;
+            nn = m - 1.0; dd = m + 1.0;
+        } else {
+            const double g = ldexp(shapes[(h2 >> 8) % 5] * mant52(h1), (int)((h2 >> 16) % 7) - 4);
+            const double v = ldexp(shapes[(h2 >> 24) % 5] * mant52(h2 >> 12), (int)((h2 >> 32) % 7) - 4);
+            nn = g; dd = g + v;
+        }
+        const double q0 = div_inrange(nn, dd);
+        const double q1 = nn / dd;
+        ++n;
+        if (__double_as_longlong(q0) != __double_as_longlong(q1)) { ++viol; arg = (uint32_t)i; }
+    }
+    atomicAdd(&out->n, n);
+    if (viol) { atomicAdd(&out->viol, viol); out->arg_bits = arg; }
+}
+
+// log10_unit against the device's log10 on `count` doubles of (0, 1], by class (i & 7):
+//   0-3  52 random mantissa bits at every exponent from the smallest subnormal's (2^-1074) to 2^-1;
+//   4-6  the three arguments of the --precise-gl 1 read loop for one e = (0.375 ... 0.75) 2^-k, k = 0 .. 53 (read_errp from 0.75 down to 4e-17):
+//        1 - e, (1 - e) / 2 + (e / 3) / 2, e / 3 (e / 3 as the kernel rounds it);
+//   7    within 2^-40 (relative) of sqrt(1/2) 2^k at every exponent, where the mantissa is doubled or not, and of 1 from below (1 itself included).
+// The first thread also takes x0 and x0 + 1 (x0 = 0.0 from the caller): -inf and exactly 0 are wanted.  Relative error against a bound of 1e-15.
+__global__ __launch_bounds__(256) void k_bound_log10(const unsigned long long count, const double x0, BoundAcc* out) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    double mr = 0.0; uint32_t arg = 0; unsigned long long viol = 0, n = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (!(log10_unit(x0) == -INFINITY)) ++viol;
+        if (__double_as_longlong(log10_unit(x0 + 1.0)) != 0) ++viol;       // +0, not just a value that compares equal
+    }
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        const uint64_t h1 = mix64(i * 2 + 1), h2 = mix64(i * 2 + 2);
+        const int cls = (int)(i & 7);
+        double x;
+        if (cls < 4) x = ldexp(mant52(h1), -1 - (int)(h2 % 1074));
+        else if (cls < 7) {
+            const double e = ldexp(0.375 + 0.375 * (mant52(h1) - 1.0), -(int)(h2 % 54));
+            const double third = 0.33333333333333331;
+            const double q0 = e * third;
+            const double e3 = __builtin_fma(__builtin_fma(-3.0, q0, e), third, q0);
+            x = (cls == 4) ? 1.0 - e : (cls == 5) ? (1.0 - e) / 2.0 + e3 * 0.5 : e3;
+        } else {
+            const long long off = (long long)(h1 & 0x1FFF) - 4096;
+            if ((i >> 3) & 1) x = ldexp(nudge(0.70710678118654752, off), -(int)(h2 % 1074));
+            else x = nudge(1.0, -(long long)(h1 & 0x1FFF));
+        }
+        if (!(x > 0.0 && x <= 1.0)) continue;
+        ++n;
+        const double got = log10_unit(x), want = log10(x);
+        if (want == 0.0) { if (__double_as_longlong(got) != 0) { ++viol; arg = (uint32_t)i; } }
+        else acc_update(mr, arg, viol, fabs(got - want), fabs(want) * 1e-15, (uint32_t)i);
+    }
+    atomicAdd(&out->n, n);
+    if (viol) atomicAdd(&out->viol, viol);
+    const unsigned long long mb = (unsigned long long)__double_as_longlong(mr);
+    const unsigned long long old = atomicMax(&out->max_ratio_bits, mb);
+    if (mb > old) out->arg_bits = arg;
+}
+
+// The helpers of the GL output tail over a caller's array, for a ground truth that is not the device's own pow / log10
+// (tests/test_gpu_gl_tail.py: mpmath at 200 bits, exact rationals for PL)
+__global__ __launch_bounds__(256) void k_tail_dump(const int fn, const void* in, void* outp, const long long n) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (fn == 0) ((double*)outp)[i] = log10_unit(((const double*)in)[i]);
+    else if (fn == 1) ((double*)outp)[i] = exp10_nonpos(((const double*)in)[i]);
+    else ((uint32_t*)outp)[i] = pl_of(((const float*)in)[i], true);
+}
+// fn 0: log10_unit, 1: exp10_nonpos (double in, double out); 2: pl_of (float in, uint32 out).  Host arrays of n elements.
+extern "C" __attribute__((visibility("default"))) int vgl_dbg_gl_tail(int fn, const void* in, void* out, long long n) {
+    if (fn < 0 || fn > 2 || !in || !out || n <= 0 || n > (1LL << 24)) return -2;
+    const size_t es = (fn == 2) ? 4 : 8;
+    void *d_in = nullptr, *d_out = nullptr;
+    int rc = -1;
+    if (hipMalloc(&d_in, es * (size_t)n) == hipSuccess && hipMalloc(&d_out, es * (size_t)n) == hipSuccess &&
+        hipMemcpy(d_in, in, es * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_tail_dump, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, (const void*)d_in, d_out, n);
+        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, d_out, es * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    }
+    (void)hipFree(d_in); (void)hipFree(d_out);
+    return rc;
 }
 
 // quot_int24(q, recip_int24(sum)) against the compiler's IEEE float32 division: pairs 0 .. 2^24 - 1 are EVERY (sum, q) with sum, q in
@@ -350,6 +489,11 @@ extern "C" __attribute__((visibility("default"))) int vgl_dbg_bound_sweep(int mo
         case VGL_BOUND_DIV10: hipLaunchKernelGGL((k_bound_sweep<VGL_BOUND_DIV10>), g, b, 0, 0, lo_bits, count, param, d); break;
         case VGL_BOUND_DIV: hipLaunchKernelGGL(k_bound_div, g, b, 0, 0, count, d); break;
         case VGL_BOUND_QUOT: hipLaunchKernelGGL(k_bound_quot, g, b, 0, 0, count, d); break;
+        case VGL_BOUND_PL_OF: hipLaunchKernelGGL((k_bound_sweep<VGL_BOUND_PL_OF>), g, b, 0, 0, lo_bits, count, param, d); break;
+        case VGL_BOUND_EXP10_F32: hipLaunchKernelGGL((k_bound_sweep<VGL_BOUND_EXP10_F32>), g, b, 0, 0, lo_bits, count, param, d); break;
+        case VGL_BOUND_LOG10_UNIT: hipLaunchKernelGGL(k_bound_log10, g, b, 0, 0, count, param, d); break;
+        case VGL_BOUND_DIV_LOG: hipLaunchKernelGGL((k_bound_div2<0>), g, b, 0, 0, count, d); break;
+        case VGL_BOUND_DIV_GAMMA: hipLaunchKernelGGL((k_bound_div2<1>), g, b, 0, 0, count, d); break;
         case VGL_BOUND_POISSON: {
             // param > 0: the exponent from the float64 expression (per-sample depths); param < 0: mean depth -param with the float32 exponent table
             const bool tab = param < 0.0;
@@ -387,6 +531,7 @@ extern "C" __attribute__((visibility("default"))) int vgl_dbg_bound_sweep(int mo
     out[0] = (double)h.n; out[1] = (double)h.viol;
     out[2] = (mode == VGL_BOUND_POISSON || mode == VGL_BOUND_POOL32) ? (double)h.max_ratio_bits / (0.5 * (double)(h.n ? h.n : 1))     // ambiguous share of the pseudo-random half
                                          : __builtin_bit_cast(double, h.max_ratio_bits);
+    if (mode == VGL_BOUND_EXP10_F32 && param != 0.0) out[2] = (double)h.aux;      // the finite nonzero results that are not identical (out[3]: one such argument)
     out[3] = (double)h.arg_bits;
     return 0;
 }

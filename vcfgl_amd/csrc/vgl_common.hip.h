@@ -336,6 +336,60 @@ __device__ __forceinline__ float div10_f32(const float x) {
     return q;
 }
 
+// PL of one likelihood (vcfgl.cpp:907-939)
+// lroundf(-10.0 * gl) capped at MAXPL, MAXPL for gl = -inf.  The double product of a float and -10 is exact, so its conversion to
+// float is the float product x; gl <= 0 (the maximum has been subtracted), so x >= 0 and lroundf(x) = floor(x + 0.5).  In float32
+// trunc(x + 0.5f) equals that for EVERY x in [0, 255] except x = 0.5 - 2^-25 (the sum rounds up to 1), which one compare puts right
+// (x = -10 gl does reach that value, for gl = -0x1.999998p-5); capping x at 255 first takes x = +inf (gl = -inf) and keeps the
+// conversion in range.  Branch-free, seven instructions.  Held by tests/test_gpu_bounds.py (mode PL_OF of vgl_bounds.hip: equal to
+// lroundf for EVERY float32 from -0 to -inf, 2 139 095 041 patterns, with the missing pattern and the byte form) and by
+// tests/test_gpu_gl_tail.py (exact rational rounding on 6e4 values and on every build's tiles).
+__device__ __forceinline__ uint32_t pl_of(const float v, const bool valid) {
+    const float x = __builtin_fminf(v * -10.0f, (float)MAXPL);
+    uint32_t r = (uint32_t)(int32_t)(x + 0.5f);
+    r -= (x == 0x1.fffffep-2f) ? 1u : 0u;
+    return valid ? r : (uint32_t)I32_MISSING;
+}
+// log10(x) for 0 < x <= 1 (--precise-gl 1: three per read, gl_methods.cpp:171-220), relative error < 1e-15 (asserted: 4.6e-16 against
+// 200-bit arithmetic at 0x1.6927bc0fb3561p-1, just below sqrt(1/2), tests/test_gpu_gl_tail.py; 5.5e-16 from the device's log10 over 2^32
+// arguments, tests/test_gpu_bounds.py mode LOG10_UNIT) -- the mode is held to 1e-6, like the device log10() it replaces: x = m 2^e with m in [sqrt(1/2), sqrt(2)), ln m = 2 atanh((m - 1) / (m + 1)) by its series up to
+// s^19 (|s| <= 0.172: remainder 2e-17 relative), log10 x = (e ln 2 + ln m) log10(e).  x <= 0 gives -inf (log10(0) of a certain base).
+__device__ __forceinline__ double log10_unit(const double x) {
+    if (!(x > 0.0)) return -INFINITY;
+    int e;
+    double m = frexp(x, &e);                                         // [1/2, 1)
+    const bool lo = m < 0.70710678118654752;
+    m = lo ? m + m : m;
+    e = lo ? e - 1 : e;
+    const double s = div_inrange(m - 1.0, m + 1.0);                  // the correctly rounded quotient without the exponent handling of the IEEE sequence (|m - 1| < 0.42, m + 1 in [1.7, 2.42))
+    const double z = s * s;
+    double p = 1.0 / 19.0;
+    p = __builtin_fma(p, z, 1.0 / 17.0); p = __builtin_fma(p, z, 1.0 / 15.0); p = __builtin_fma(p, z, 1.0 / 13.0);
+    p = __builtin_fma(p, z, 1.0 / 11.0); p = __builtin_fma(p, z, 1.0 / 9.0); p = __builtin_fma(p, z, 1.0 / 7.0);
+    p = __builtin_fma(p, z, 1.0 / 5.0); p = __builtin_fma(p, z, 1.0 / 3.0); p = __builtin_fma(p, z, 1.0);
+    const double ln = __builtin_fma((double)e, 0.69314718055994531, (s + s) * p);
+    return ln * 0.43429448190325183;
+}
+// 10^x for x <= 0 (GP = 10^GL, vcfgl.cpp:941-970), relative error < 1e-15 (asserted: 1.7e-16 against 200-bit arithmetic on 4e4 float32
+// arguments, its float32 the correctly rounded one on all of them, tests/test_gpu_gl_tail.py; 3.6e-16 from the device's pow and no float32
+// result different from pow's over EVERY float32 argument, tests/test_gpu_bounds.py mode EXP10_F32) -- GP is held to 1e-6, like the device pow()
+// it replaces (≈200 vector instructions per call, fifteen calls per evaluation): 2^n 2^f with n = rint(x log2 10), f in [-1/2, 1/2]
+// taken as x log2 10 - n in two pieces, 2^f = e^(f ln 2) by a degree-13 Taylor polynomial (|f ln 2| <= 0.35: remainder < 2e-17).
+__device__ __forceinline__ double exp10_nonpos(const double x) {
+    if (!(x > -330.0)) return 0.0;                                // underflow of the float result, -inf
+    const double L2_10_hi = 3.3219280948873622, L2_10_lo = 1.6616175169735921e-16;     // log2(10) = hi + lo
+    const double y = x * L2_10_hi;
+    const double n = rint(y);
+    const double f = __builtin_fma(x, L2_10_hi, -n) + x * L2_10_lo;
+    const double t = f * 0.69314718055994531;
+    double p = 1.0 / 6227020800.0;
+    p = __builtin_fma(p, t, 1.0 / 479001600.0); p = __builtin_fma(p, t, 1.0 / 39916800.0); p = __builtin_fma(p, t, 1.0 / 3628800.0);
+    p = __builtin_fma(p, t, 1.0 / 362880.0); p = __builtin_fma(p, t, 1.0 / 40320.0); p = __builtin_fma(p, t, 1.0 / 5040.0);
+    p = __builtin_fma(p, t, 1.0 / 720.0); p = __builtin_fma(p, t, 1.0 / 120.0); p = __builtin_fma(p, t, 1.0 / 24.0);
+    p = __builtin_fma(p, t, 1.0 / 6.0); p = __builtin_fma(p, t, 0.5); p = __builtin_fma(p, t, 1.0); p = __builtin_fma(p, t, 1.0);
+    return ldexp(p, (int)n);
+}
+
 // error probability -> qScore / adjusted qScore, vcfgl.cpp:500-523
 static __device__ void errprob_to_qs(const VglDevParams& P, double ep, int& q, int& aq, uint32_t* errflag) {
     q = -1; aq = -1;

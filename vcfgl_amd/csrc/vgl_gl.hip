@@ -166,54 +166,6 @@ typedef __attribute__((address_space(1))) uint32_t vgl_gu32;             // a gl
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ float f32_missing() { return __uint_as_float(F32_MISSING_BITS); }
 __device__ __forceinline__ int nib(uint32_t v, int k) { return (int)((v >> (4 * k)) & 0xF); }
-// PL of one likelihood (vcfgl.cpp:907-939)
-// lroundf(-10.0 * gl) capped at MAXPL, MAXPL for gl = -inf.  The double product of a float and -10 is exact, so its conversion to
-// float is the float product x; gl <= 0 (the maximum has been subtracted), so x >= 0 and lroundf(x) = floor(x + 0.5).  In float32
-// trunc(x + 0.5f) equals that for EVERY x in [0, 255] except x = 0.5 - 2^-25 (the sum rounds up to 1), which one compare puts right
-// (checked over all 1.1e9 float32 values of the range; x = -10 gl does reach that value, for gl = -0x1.999998p-5); capping x at 255
-// first takes x = +inf (gl = -inf) and keeps the conversion in range.  Branch-free, seven instructions.
-__device__ __forceinline__ uint32_t pl_of(const float v, const bool valid) {
-    const float x = __builtin_fminf(v * -10.0f, (float)MAXPL);
-    uint32_t r = (uint32_t)(int32_t)(x + 0.5f);
-    r -= (x == 0x1.fffffep-2f) ? 1u : 0u;
-    return valid ? r : (uint32_t)I32_MISSING;
-}
-// log10(x) for 0 < x <= 1 (--precise-gl 1: three per read, gl_methods.cpp:171-220), relative error < 1e-15 -- the mode is held to 1e-6,
-// like the device log10() it replaces: x = m 2^e with m in [sqrt(1/2), sqrt(2)), ln m = 2 atanh((m - 1) / (m + 1)) by its series up to
-// s^19 (|s| <= 0.172: remainder 2e-17 relative), log10 x = (e ln 2 + ln m) log10(e).  x <= 0 gives -inf (log10(0) of a certain base).
-__device__ __forceinline__ double log10_unit(const double x) {
-    if (!(x > 0.0)) return -INFINITY;
-    int e;
-    double m = frexp(x, &e);                                         // [1/2, 1)
-    const bool lo = m < 0.70710678118654752;
-    m = lo ? m + m : m;
-    e = lo ? e - 1 : e;
-    const double s = div_inrange(m - 1.0, m + 1.0);                  // the correctly rounded quotient without the exponent handling of the IEEE sequence (|m - 1| < 0.42, m + 1 in [1.7, 2.42))
-    const double z = s * s;
-    double p = 1.0 / 19.0;
-    p = __builtin_fma(p, z, 1.0 / 17.0); p = __builtin_fma(p, z, 1.0 / 15.0); p = __builtin_fma(p, z, 1.0 / 13.0);
-    p = __builtin_fma(p, z, 1.0 / 11.0); p = __builtin_fma(p, z, 1.0 / 9.0); p = __builtin_fma(p, z, 1.0 / 7.0);
-    p = __builtin_fma(p, z, 1.0 / 5.0); p = __builtin_fma(p, z, 1.0 / 3.0); p = __builtin_fma(p, z, 1.0);
-    const double ln = __builtin_fma((double)e, 0.69314718055994531, (s + s) * p);
-    return ln * 0.43429448190325183;
-}
-// 10^x for x <= 0 (GP = 10^GL, vcfgl.cpp:941-970), relative error 2e-16 (numpy check of the same steps against 10**x) -- GP is held to 1e-6, like the device pow()
-// it replaces (≈200 vector instructions per call, fifteen calls per evaluation): 2^n 2^f with n = rint(x log2 10), f in [-1/2, 1/2]
-// taken as x log2 10 - n in two pieces, 2^f = e^(f ln 2) by a degree-13 Taylor polynomial (|f ln 2| <= 0.35: remainder < 2e-17).
-__device__ __forceinline__ double exp10_nonpos(const double x) {
-    if (!(x > -330.0)) return 0.0;                                // underflow of the float result, -inf
-    const double L2_10_hi = 3.3219280948873622, L2_10_lo = 1.6616175169735921e-16;     // log2(10) = hi + lo
-    const double y = x * L2_10_hi;
-    const double n = rint(y);
-    const double f = __builtin_fma(x, L2_10_hi, -n) + x * L2_10_lo;
-    const double t = f * 0.69314718055994531;
-    double p = 1.0 / 6227020800.0;
-    p = __builtin_fma(p, t, 1.0 / 479001600.0); p = __builtin_fma(p, t, 1.0 / 39916800.0); p = __builtin_fma(p, t, 1.0 / 3628800.0);
-    p = __builtin_fma(p, t, 1.0 / 362880.0); p = __builtin_fma(p, t, 1.0 / 40320.0); p = __builtin_fma(p, t, 1.0 / 5040.0);
-    p = __builtin_fma(p, t, 1.0 / 720.0); p = __builtin_fma(p, t, 1.0 / 120.0); p = __builtin_fma(p, t, 1.0 / 24.0);
-    p = __builtin_fma(p, t, 1.0 / 6.0); p = __builtin_fma(p, t, 0.5); p = __builtin_fma(p, t, 1.0); p = __builtin_fma(p, t, 1.0);
-    return ldexp(p, (int)n);
-}
 __device__ __forceinline__ int cnt_of(uint64_t ad4, int b) { return b < 4 ? (int)((ad4 >> (16 * b)) & 0xFFFF) : 0; }
 
 // Evaluations differ in depth -- and, for GL model 2, in how many distinct bases their reads show, which decides how many
