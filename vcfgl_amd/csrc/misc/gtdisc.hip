@@ -1,0 +1,444 @@
+// gtdisc.hip -- the kernels of gtdiscordance_hip and their launch code (a translation unit of the program: the library gets no entry point).
+// A batch is the text of the sample columns of up to max_recs matched truth / call lines and one gtd::Rec per record; the per-sample
+// rules are gtdisc_core.h.
+//   k_gtd_parse       one workgroup of 256 lanes per record, the truth region and then the call region.  A region is walked in chunks of
+//                     256 x 16 bytes on 16-byte address boundaries as k_vcfin_parse walks a line: a lane whose 16 bytes lie inside the
+//                     region loads them at once, the lanes at the two ends read their bytes one by one -- no byte outside the region is
+//                     read.  A scan of the tab counts numbers the columns; the lane that owns the tab before column s parses that column
+//                     (gtd::sample_true / gtd::sample_call, bounded by the region's end) and stores one byte per plane: true bases,
+//                     called bases (0xFF missing), GQ.  The status (an OR over the columns, and the column count against n_samples) is
+//                     stored by lane 0.  No atomics.
+//   k_gtd_tally       k_disc_tally's shape: a workgroup of 16 wavefronts owns 64 consecutive samples over a run of records, a wavefront
+//                     takes a record (ST_OK ones only), its lanes the samples; counts go to an LDS histogram [cell][GQ][sample] of 16-bit
+//                     counters -- a counter belongs to one sample and a run has at most 32768 records, so none can wrap -- and once per
+//                     workgroup the non-zero counters are added to the int64 table (layout of vgl_disc_table_len) with 64-bit atomics.
+//   k_gtd_list_plan   a workgroup per record: the byte counts of its -doGQ 1 / 2 lines and of its -perSite lines (0 for a ST_HOST record)
+//   k_gtd_list_scan   one workgroup: the exclusive prefix sums of both counts over the batch's records
+//   k_gtd_list_write  a workgroup per record, a lane per line: the lines' lengths are scanned across the workgroup, chunk by chunk, and
+//                     every lane formats its line at its offset, never past the text's capacity
+// The planes never leave the device; the table is read once, the listing text per batch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "../../../include/vcfgl_hip.h"
+#include "gtdisc_dev.h"
+
+namespace {
+
+constexpr int NT = 256;                  // lanes per workgroup of the parser and the listing kernels
+constexpr int LB = 16;                   // bytes per lane and chunk
+constexpr int CHUNK = NT * LB;
+constexpr int TNT = 1024;                // lanes per workgroup of the tally
+constexpr int SG = 64;                   // samples per tally workgroup
+constexpr int NCELL = gtd::N_CELLS, NGQ = gtd::N_GQ;
+constexpr int HIST = NCELL * NGQ * SG;   // 16-bit counters
+constexpr int MAX_RUN = 32768;           // records per tally workgroup: below 2^16
+constexpr size_t TALLY_LDS = (size_t)HIST * 2 + SG * sizeof(uint32_t);
+constexpr int SNT = 1024;                // lanes of the scan
+
+struct ParseArgs {
+    const uint8_t* text; int64_t text_bytes;
+    const gtd::Rec* recs; int32_t n_recs, N;
+    uint8_t* tb; uint8_t* cb; uint8_t* gq; int32_t* status;
+};
+
+// the columns of the region [lb, le): f(col, q) for every column that starts at q; returns the number of columns.  One __syncthreads
+// per chunk on s_tot[parity]; every lane of the workgroup takes part.
+template <typename F>
+__device__ __forceinline__ int32_t scan_columns(const uint8_t* __restrict__ text, const int64_t lb, const int64_t le, int32_t (*s_tot)[NT / 64], F f) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t mis = (int64_t)((uintptr_t)(text + lb) & (LB - 1));
+    const int64_t o0 = lb - mis;                                       // the 16-byte boundary at or below the region's first byte
+    const int64_t n_chunks = (le - o0 + CHUNK - 1) / CHUNK;
+    int32_t base = 0;
+    if (t == 0) f(0, lb);                                              // column 0 starts at the region's first byte
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const int64_t o = o0 + c * CHUNK + (int64_t)t * LB;            // this lane's 16 bytes: [o, o + 16)
+        uint32_t w[4] = {0, 0, 0, 0};
+        if (o >= lb && o + LB <= le) {
+            const uint4 v = *reinterpret_cast<const uint4*>(text + o);
+            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        } else if (o + LB > lb && o < le) {
+#pragma unroll
+            for (int i = 0; i < LB; i++) { const int64_t at = o + i; if (at >= lb && at < le) w[i >> 2] |= (uint32_t)text[at] << (8 * (i & 3)); }
+        }
+        uint32_t mask = 0;                                             // bit i: byte i is a tab (a byte outside the region is 0 here)
+#pragma unroll
+        for (int i = 0; i < LB; i++) mask |= (((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) == (uint32_t)'\t' ? 1u : 0u) << i;
+        const int cnt = __popc(mask);
+        int inc = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(inc, d, 64); if (lane >= d) inc += y; }
+        if (lane == 63) s_tot[c & 1][wave] = inc;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < NT / 64; k++) { const int x = s_tot[c & 1][k]; if (k < wave) before += x; total += x; }
+        int32_t col = base + before + inc - cnt + 1;                   // the column after this lane's first tab
+        base += total;
+        while (mask) {
+            const int i = __ffs(mask) - 1; mask &= mask - 1;
+            f(col, o + i + 1);
+            col++;
+        }
+    }
+    return base + 1;
+}
+
+__global__ void __launch_bounds__(NT) k_gtd_parse(const ParseArgs A) {
+    __shared__ int32_t s_tot[2][NT / 64];
+    __shared__ int32_t s_bad[NT / 64];
+    const int rec = blockIdx.x;
+    if (rec >= A.n_recs) return;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const gtd::Rec r = A.recs[rec];
+    const int32_t N = A.N;
+    const int64_t tl = r.t_off, te = r.t_off + r.t_len, cl = r.c_off, ce = r.c_off + r.c_len;
+    const bool fits = r.t_off >= 0 && r.t_len >= 0 && te <= A.text_bytes && r.c_off >= 0 && r.c_len >= 0 && ce <= A.text_bytes;
+    const bool known = r.t_gti >= 0 && r.c_gti >= 0 && r.t_nal >= 1 && r.c_nal >= 1 && (r.gq_mode != gtd::GQ_TAG || r.c_gqi >= 0) &&
+                       (r.gq_mode != gtd::GQ_PL || r.c_nal == 1 || (r.c_pli >= 0 && r.c_nal <= 5 && r.nG == gtd::n_genotypes(r.c_nal)));
+    if (!fits || !known) {                                             // (the host sends no such record; never read outside the text)
+        if (t == 0) A.status[rec] = gtd::ST_HOST;
+        return;
+    }
+    const uint8_t* __restrict__ text = A.text;
+    uint8_t* __restrict__ tb = A.tb + (size_t)rec * (size_t)N;
+    uint8_t* __restrict__ cb = A.cb + (size_t)rec * (size_t)N;
+    uint8_t* __restrict__ gq = A.gq + (size_t)rec * (size_t)N;
+    int bad = 0;
+    const int32_t cols_t = scan_columns(text, tl, te, s_tot, [&](const int32_t col, const int64_t q) {
+        if (col >= N) return;
+        uint32_t b;
+        if (!gtd::sample_true(text, q, te, r, b)) bad = 1; else tb[col] = (uint8_t)b;
+    });
+    __syncthreads();                                                   // (s_tot is used again)
+    const int32_t cols_c = scan_columns(text, cl, ce, s_tot, [&](const int32_t col, const int64_t q) {
+        if (col >= N) return;
+        uint32_t b, g;
+        if (!gtd::sample_call(text, q, ce, r, b, g)) bad = 1; else { cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
+    });
+    bad = __any(bad) ? 1 : 0;
+    if (lane == 0) s_bad[wave] = bad;
+    __syncthreads();
+    if (t == 0) {
+        int B = 0;
+        for (int k = 0; k < NT / 64; k++) B |= s_bad[k];
+        if (cols_t != N || cols_c != N) B = 1;
+        A.status[rec] = B ? gtd::ST_HOST : gtd::ST_OK;
+    }
+}
+
+struct TallyArgs {
+    int32_t N, n_recs, run;
+    const uint8_t* tb; const uint8_t* cb; const uint8_t* gq; const int32_t* status;
+    unsigned long long* table;
+};
+
+__global__ __launch_bounds__(TNT) void k_gtd_tally(const TallyArgs A) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_h[];       // [HIST / 2] counters, [SG] call-missing
+    uint32_t* const s_mis = s_h + HIST / 2;
+    const int tid = (int)threadIdx.x;
+    for (int k = tid; k < HIST / 2 + SG; k += TNT) s_h[k] = 0u;
+    __syncthreads();
+    const int lane = tid & 63, wv = tid >> 6;
+    const int N = A.N;
+    const int s = (int)blockIdx.x * SG + lane;
+    const int i0 = (int)blockIdx.y * A.run;
+    const int i1 = (A.n_recs - i0 < A.run) ? A.n_recs : i0 + A.run;
+    uint32_t mis = 0;
+    const int wv0 = __builtin_amdgcn_readfirstlane(wv);
+    for (int i = i0 + wv0; i < i1; i += TNT / 64) {
+        if (A.status[i] != gtd::ST_OK || s >= N) continue;
+        const size_t at = (size_t)i * (size_t)N + (size_t)s;
+        const uint32_t c = A.cb[at];
+        if (c == (uint32_t)gtd::CALL_MISSING) { ++mis; continue; }
+        const uint32_t cell = gtd::classify(A.tb[at], c);
+        const uint32_t g = A.gq[at] & (uint32_t)(NGQ - 1);
+        const uint32_t idx = (cell * NGQ + g) * SG + (uint32_t)lane;
+        atomicAdd(&s_h[idx >> 1], 1u << (16u * (idx & 1u)));
+    }
+    if (mis) atomicAdd(&s_mis[lane], mis);
+    __syncthreads();
+    for (int w = tid; w < HIST / 2; w += TNT) {
+        const uint32_t word = s_h[w];
+        if (!word) continue;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const uint32_t n = word >> (16 * h) & 0xffffu;
+            const int idx = 2 * w + h, ls = idx & (SG - 1), cg = idx >> 6;   // cg = cell * 128 + GQ
+            const int sm = (int)blockIdx.x * SG + ls;
+            if (n && sm < N) atomicAdd(&A.table[(size_t)sm * (NCELL * NGQ) + cg], (unsigned long long)n);
+        }
+    }
+    if (tid < SG) {
+        const int sm = (int)blockIdx.x * SG + tid;
+        if (s_mis[tid] && sm < N) atomicAdd(&A.table[(size_t)N * (NCELL * NGQ) + sm], (unsigned long long)s_mis[tid]);
+    }
+}
+
+struct ListArgs {
+    int32_t N, n_recs, list, per_site;
+    const gtd::Rec* recs;
+    const uint8_t* tb; const uint8_t* cb; const uint8_t* gq; const int32_t* status;
+    int64_t* len;                        // [2][n_recs]: listing, per-site
+    int64_t* off;                        // [2][n_recs + 1]
+    uint8_t* list_text; uint8_t* site_text; int64_t list_cap, site_cap;
+};
+
+// the lengths of sample s's two lines (0 where it has none)
+__device__ __forceinline__ void line_lens(const ListArgs& A, const gtd::Rec& r, const size_t row, const int32_t s, uint32_t& l0, uint32_t& l1, uint32_t& cell, uint32_t& g) {
+    l0 = l1 = 0; cell = 0; g = 0;
+    const uint32_t c = A.cb[row + s];
+    if (c == (uint32_t)gtd::CALL_MISSING) return;
+    cell = gtd::classify(A.tb[row + s], c); g = A.gq[row + s];
+    if (A.list) l0 = gtd::list_len(A.list, r.nsites1, (uint32_t)s, cell, g);
+    if (A.per_site) l1 = gtd::site_len(r.pos, (uint32_t)s, cell);
+}
+
+__global__ void __launch_bounds__(NT) k_gtd_list_plan(const ListArgs A) {
+    __shared__ unsigned long long s_sum[2][NT / 64];
+    const int rec = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (rec >= A.n_recs) return;
+    unsigned long long n0 = 0, n1 = 0;
+    if (A.status[rec] == gtd::ST_OK) {
+        const gtd::Rec r = A.recs[rec];
+        const size_t row = (size_t)rec * (size_t)A.N;
+        for (int32_t s = t; s < A.N; s += NT) { uint32_t l0, l1, cell, g; line_lens(A, r, row, s, l0, l1, cell, g); n0 += l0; n1 += l1; }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { n0 += __shfl_down(n0, d, 64); n1 += __shfl_down(n1, d, 64); }
+    if (lane == 0) { s_sum[0][wave] = n0; s_sum[1][wave] = n1; }
+    __syncthreads();
+    if (t < 2) {
+        unsigned long long x = 0;
+        for (int k = 0; k < NT / 64; k++) x += s_sum[t][k];
+        A.len[(size_t)t * A.n_recs + rec] = (int64_t)x;
+    }
+}
+
+// off[w][0 .. n_recs] = exclusive prefix sums of len[w][0 .. n_recs), w = blockIdx.x
+__global__ void __launch_bounds__(SNT) k_gtd_list_scan(const ListArgs A) {
+    __shared__ long long s_tot[2][SNT / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t* len = A.len + (size_t)blockIdx.x * A.n_recs;
+    int64_t* off = A.off + (size_t)blockIdx.x * ((size_t)A.n_recs + 1);
+    long long base = 0;
+    const int n_chunks = (A.n_recs + SNT - 1) / SNT;
+    for (int c = 0; c < n_chunks; c++) {
+        const int i = c * SNT + t;
+        const long long v = i < A.n_recs ? (long long)len[i] : 0;
+        long long inc = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const long long y = __shfl_up(inc, d, 64); if (lane >= d) inc += y; }
+        if (lane == 63) s_tot[c & 1][wave] = inc;
+        __syncthreads();
+        long long before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < SNT / 64; k++) { const long long x = s_tot[c & 1][k]; if (k < wave) before += x; total += x; }
+        if (i < A.n_recs) off[i] = (int64_t)(base + before + inc - v);
+        base += total;
+    }
+    if (t == 0) off[A.n_recs] = (int64_t)base;
+}
+
+__global__ void __launch_bounds__(NT) k_gtd_list_write(const ListArgs A) {
+    __shared__ uint32_t s_tot[2][2][NT / 64];
+    const int rec = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (rec >= A.n_recs || A.status[rec] != gtd::ST_OK) return;       // (uniform over the workgroup)
+    const gtd::Rec r = A.recs[rec];
+    const size_t row = (size_t)rec * (size_t)A.N;
+    int64_t at0 = A.off[rec], at1 = A.off[(size_t)A.n_recs + 1 + rec];
+    const int n_chunks = (A.N + NT - 1) / NT;
+    for (int c = 0; c < n_chunks; c++) {
+        const int32_t s = c * NT + t;
+        uint32_t l0 = 0, l1 = 0, cell = 0, g = 0;
+        if (s < A.N) line_lens(A, r, row, s, l0, l1, cell, g);
+        uint32_t i0 = l0, i1 = l1;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t y0 = __shfl_up(i0, d, 64), y1 = __shfl_up(i1, d, 64); if (lane >= d) { i0 += y0; i1 += y1; } }
+        if (lane == 63) { s_tot[c & 1][0][wave] = i0; s_tot[c & 1][1][wave] = i1; }
+        __syncthreads();
+        uint32_t b0 = 0, b1 = 0, t0 = 0, t1 = 0;
+#pragma unroll
+        for (int k = 0; k < NT / 64; k++) {
+            const uint32_t x0 = s_tot[c & 1][0][k], x1 = s_tot[c & 1][1][k];
+            if (k < wave) { b0 += x0; b1 += x1; }
+            t0 += x0; t1 += x1;
+        }
+        if (l0) {
+            const int64_t at = at0 + b0 + i0 - l0;
+            if (at >= 0 && at < A.list_cap) {
+                const int64_t room = A.list_cap - at;
+                gtd::Emit<true> e{A.list_text + at, 0u, (uint32_t)(room < gtd::LINE_BOUND ? room : gtd::LINE_BOUND)};
+                gtd::list_line(e, A.list, r.nsites1, (uint32_t)s, cell, g);
+            }
+        }
+        if (l1) {
+            const int64_t at = at1 + b1 + i1 - l1;
+            if (at >= 0 && at < A.site_cap) {
+                const int64_t room = A.site_cap - at;
+                gtd::Emit<true> e{A.site_text + at, 0u, (uint32_t)(room < gtd::LINE_BOUND ? room : gtd::LINE_BOUND)};
+                gtd::site_line(e, r.pos, (uint32_t)s, cell);
+            }
+        }
+        at0 += t0; at1 += t1;
+    }
+}
+
+}  // namespace
+
+// ---- the handle --------------------------------------------------------------------------------------------------------------
+struct GtdSlot {
+    uint8_t* h_text = nullptr; gtd::Rec* h_recs = nullptr;              // page-locked staging (vgl_host_alloc_on)
+    int32_t* h_status = nullptr; int64_t* h_off = nullptr; uint8_t* h_list = nullptr; uint8_t* h_site = nullptr;
+    uint8_t* d_text = nullptr; gtd::Rec* d_recs = nullptr;
+    uint8_t* d_planes = nullptr; int32_t* d_status = nullptr; int64_t* d_len = nullptr; int64_t* d_off = nullptr;
+    uint8_t* d_list = nullptr; uint8_t* d_site = nullptr;
+    hipEvent_t done = nullptr;
+    int32_t n_recs = 0; bool busy = false;
+};
+struct GtdDev {
+    int device = 0; int32_t N = 0, max_recs = 0; int64_t max_text = 0; int list = 0, per_site = 0;
+    int64_t list_cap = 0, site_cap = 0;
+    hipStream_t stream = nullptr;
+    unsigned long long* d_table = nullptr; int64_t table_len = 0;
+    GtdSlot slot[2];
+    char err[256] = {0};
+};
+
+static int gtd_fail(GtdDev* d, const char* what, hipError_t e) {
+    snprintf(d->err, sizeof d->err, "%s: %s", what, hipGetErrorString(e));
+    return -1;
+}
+#define GTD_HIP(d, call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return gtd_fail(d, #call, e_); } while (0)
+
+const char* gtd_dev_error(GtdDev* d) { return d->err; }
+
+static int gtd_dev_setup(GtdDev* d) {
+    GTD_HIP(d, hipSetDevice(d->device));
+    GTD_HIP(d, hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    d->table_len = vgl_disc_table_len(d->N);
+    GTD_HIP(d, hipMalloc((void**)&d->d_table, (size_t)d->table_len * 8));
+    GTD_HIP(d, hipMemsetAsync(d->d_table, 0, (size_t)d->table_len * 8, d->stream));
+    const size_t R = (size_t)d->max_recs, N = (size_t)d->N;
+    for (GtdSlot& s : d->slot) {
+        auto pinned = [&](size_t bytes) { return vgl_host_alloc_on(d->device, bytes ? bytes : 1); };
+        s.h_text = (uint8_t*)pinned((size_t)d->max_text); s.h_recs = (gtd::Rec*)pinned(R * sizeof(gtd::Rec));
+        s.h_status = (int32_t*)pinned(R * 4); s.h_off = (int64_t*)pinned(2 * (R + 1) * 8);
+        s.h_list = (uint8_t*)pinned((size_t)d->list_cap); s.h_site = (uint8_t*)pinned((size_t)d->site_cap);
+        if (!s.h_text || !s.h_recs || !s.h_status || !s.h_off || !s.h_list || !s.h_site) {
+            snprintf(d->err, sizeof d->err, "page-locked host memory could not be allocated: %s", vgl_last_error());
+            return -1;
+        }
+        GTD_HIP(d, hipMalloc((void**)&s.d_text, (size_t)d->max_text + LB));
+        GTD_HIP(d, hipMalloc((void**)&s.d_recs, R * sizeof(gtd::Rec)));
+        GTD_HIP(d, hipMalloc((void**)&s.d_planes, 3 * R * N));
+        GTD_HIP(d, hipMalloc((void**)&s.d_status, R * 4));
+        GTD_HIP(d, hipMalloc((void**)&s.d_len, 2 * R * 8));
+        GTD_HIP(d, hipMalloc((void**)&s.d_off, 2 * (R + 1) * 8));
+        GTD_HIP(d, hipMalloc((void**)&s.d_list, (size_t)d->list_cap + 1));
+        GTD_HIP(d, hipMalloc((void**)&s.d_site, (size_t)d->site_cap + 1));
+        GTD_HIP(d, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    }
+    return 0;
+}
+
+GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, char* err, size_t err_len) {
+    auto refuse = [&](const char* why) { snprintf(err, err_len, "%s", why); return (GtdDev*)nullptr; };
+    if (n_samples <= 0 || max_recs <= 0 || max_text < 0) return refuse("bad batch shape");
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return refuse("no HIP device is available");
+    if (device < 0 || device >= nd) return refuse("no such device");
+    GtdDev* d = new GtdDev();
+    d->device = device; d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->list = list; d->per_site = per_site;
+    d->list_cap = list ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
+    d->site_cap = per_site ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
+    if (gtd_dev_setup(d) != 0) { snprintf(err, err_len, "%s", d->err); gtd_dev_destroy(d); return nullptr; }
+    return d;
+}
+
+uint8_t* gtd_dev_text(GtdDev* d, int slot) { return d->slot[slot & 1].h_text; }
+gtd::Rec* gtd_dev_recs(GtdDev* d, int slot) { return d->slot[slot & 1].h_recs; }
+
+int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
+    GtdSlot& s = d->slot[slot & 1];
+    if (s.busy || n_recs < 0 || n_recs > d->max_recs || text_bytes < 0 || text_bytes > d->max_text) {
+        snprintf(d->err, sizeof d->err, "a batch outside the shape the handle was made for, or a slot still in flight");
+        return -1;
+    }
+    s.n_recs = n_recs; s.busy = true;
+    if (n_recs == 0) return 0;
+    hipStream_t st = d->stream;
+    const size_t R = (size_t)n_recs, N = (size_t)d->N;
+    GTD_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
+    GTD_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(gtd::Rec), hipMemcpyHostToDevice, st));
+    uint8_t* tb = s.d_planes; uint8_t* cb = tb + (size_t)d->max_recs * N; uint8_t* gq = cb + (size_t)d->max_recs * N;
+    const ParseArgs P{s.d_text, text_bytes, s.d_recs, n_recs, d->N, tb, cb, gq, s.d_status};
+    hipLaunchKernelGGL(k_gtd_parse, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
+    GTD_HIP(d, hipGetLastError());
+    // the tally: about two workgroups per CU where the batch has them, runs of at least 16 records, never more than MAX_RUN
+    const int groups = (d->N + SG - 1) / SG;
+    int runs = 512 / groups;
+    const int most = (n_recs + 15) / 16;
+    if (runs > most) runs = most;
+    if (runs < 1) runs = 1;
+    int run = (n_recs + runs - 1) / runs;
+    if (run > MAX_RUN) run = MAX_RUN;
+    runs = (n_recs + run - 1) / run;
+    const TallyArgs T{d->N, n_recs, run, tb, cb, gq, s.d_status, d->d_table};
+    if (runs > 65535) { snprintf(d->err, sizeof d->err, "too many records for one batch"); return -1; }
+    hipLaunchKernelGGL(k_gtd_tally, dim3((unsigned)groups, (unsigned)runs), dim3(TNT), TALLY_LDS, st, T);
+    GTD_HIP(d, hipGetLastError());
+    if (d->list || d->per_site) {
+        const ListArgs L{d->N, n_recs, d->list, d->per_site, s.d_recs, tb, cb, gq, s.d_status, s.d_len, s.d_off, s.d_list, s.d_site, d->list_cap, d->site_cap};
+        hipLaunchKernelGGL(k_gtd_list_plan, dim3((unsigned)n_recs), dim3(NT), 0, st, L);
+        GTD_HIP(d, hipGetLastError());
+        hipLaunchKernelGGL(k_gtd_list_scan, dim3(2), dim3(SNT), 0, st, L);
+        GTD_HIP(d, hipGetLastError());
+        hipLaunchKernelGGL(k_gtd_list_write, dim3((unsigned)n_recs), dim3(NT), 0, st, L);
+        GTD_HIP(d, hipGetLastError());
+        GTD_HIP(d, hipMemcpyAsync(s.h_off, s.d_off, 2 * (R + 1) * 8, hipMemcpyDeviceToHost, st));
+    }
+    GTD_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, R * 4, hipMemcpyDeviceToHost, st));
+    GTD_HIP(d, hipEventRecord(s.done, st));
+    return 0;
+}
+
+int gtd_dev_wait(GtdDev* d, int slot, GtdBatchOut* out) {
+    GtdSlot& s = d->slot[slot & 1];
+    if (!s.busy) { snprintf(d->err, sizeof d->err, "nothing in flight in this slot"); return -1; }
+    s.busy = false;
+    const size_t R = (size_t)s.n_recs;
+    if (s.n_recs > 0) GTD_HIP(d, hipEventSynchronize(s.done));
+    if (!(d->list || d->per_site) || s.n_recs == 0) for (size_t i = 0; i < 2 * (R + 1); i++) s.h_off[i] = 0;
+    const int64_t n_list = s.h_off[R], n_site = s.h_off[2 * R + 1];
+    if (n_list < 0 || n_list > d->list_cap || n_site < 0 || n_site > d->site_cap) { snprintf(d->err, sizeof d->err, "a batch's listing is longer than its bound"); return -1; }
+    if (n_list > 0) GTD_HIP(d, hipMemcpyAsync(s.h_list, s.d_list, (size_t)n_list, hipMemcpyDeviceToHost, d->stream));
+    if (n_site > 0) GTD_HIP(d, hipMemcpyAsync(s.h_site, s.d_site, (size_t)n_site, hipMemcpyDeviceToHost, d->stream));
+    if (n_list > 0 || n_site > 0) GTD_HIP(d, hipStreamSynchronize(d->stream));
+    out->status = s.h_status; out->list_off = s.h_off; out->site_off = s.h_off + R + 1; out->list_text = s.h_list; out->site_text = s.h_site;
+    return 0;
+}
+
+int gtd_dev_table(GtdDev* d, int64_t* table) {
+    GTD_HIP(d, hipMemcpyAsync(table, d->d_table, (size_t)d->table_len * 8, hipMemcpyDeviceToHost, d->stream));
+    GTD_HIP(d, hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+void gtd_dev_quiesce(GtdDev* d) { if (d && d->stream) (void)hipStreamSynchronize(d->stream); }
+
+void gtd_dev_destroy(GtdDev* d) {
+    if (!d) return;
+    gtd_dev_quiesce(d);
+    for (GtdSlot& s : d->slot) {
+        for (void* p : {(void*)s.h_text, (void*)s.h_recs, (void*)s.h_status, (void*)s.h_off, (void*)s.h_list, (void*)s.h_site}) if (p) vgl_host_free(p);
+        for (void* p : {(void*)s.d_text, (void*)s.d_recs, (void*)s.d_planes, (void*)s.d_status, (void*)s.d_len, (void*)s.d_off, (void*)s.d_list, (void*)s.d_site}) if (p) (void)hipFree(p);
+        if (s.done) (void)hipEventDestroy(s.done);
+    }
+    if (d->d_table) (void)hipFree(d->d_table);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
+}

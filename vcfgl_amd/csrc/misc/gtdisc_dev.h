@@ -1,0 +1,27 @@
+// gtdisc_dev.h -- what gtdisc_main.cpp sees of gtdisc.hip: a handle that holds two batches of records (slots 0 and 1) on one stream
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include "gtdisc_core.h"
+
+struct GtdDev;
+
+// what a retired batch gives back; the pointers are page-locked host memory of the slot, valid until the slot is submitted again
+struct GtdBatchOut {
+    const int32_t* status;             // [n_recs] gtd::ST_OK / gtd::ST_HOST
+    const int64_t* list_off;           // [n_recs + 1] offsets of the records' -doGQ 1 / 2 lines in list_text (a ST_HOST record: empty)
+    const int64_t* site_off;           // [n_recs + 1] likewise for -perSite 1
+    const uint8_t* list_text;
+    const uint8_t* site_text;
+};
+
+// n_samples, the most records and text bytes of a batch, the listing (gtd::LIST_*) and -perSite.  nullptr with the reason in err
+GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, char* err, size_t err_len);
+uint8_t* gtd_dev_text(GtdDev* d, int slot);                    // the slot's staging: max_text bytes, max_recs descriptors
+gtd::Rec* gtd_dev_recs(GtdDev* d, int slot);
+int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes);
+int gtd_dev_wait(GtdDev* d, int slot, GtdBatchOut* out);
+int gtd_dev_table(GtdDev* d, int64_t* table);                  // the cells and call-missing counts of every batch so far (vgl_disc_table_len(n_samples) elements)
+void gtd_dev_quiesce(GtdDev* d);                               // waits for whatever is in flight (before the process leaves on an error)
+void gtd_dev_destroy(GtdDev* d);
+const char* gtd_dev_error(GtdDev* d);

@@ -1,0 +1,531 @@
+// gtdisc_main.cpp -- gtdiscordance_hip: the reference's misc/gtDiscordance (a call file against -printTruth's file) for this platform.
+//   gtdiscordance_hip -t truth -i call -o out [-doGQ 0..8] [-perSite 0|1] [--on-device 0|1] [--device INT] [--batch-records INT] [--verbose 0|1]
+// Both files are read whole (plain, gzip or bgzip text through zlib; BCF records are decoded into the same text lines on the host), their
+// first nine columns are parsed on the host and the records matched by the tool's sequential merge on POS.  Every matched pair is then
+// judged by the PLAIN grammar of gtdisc_core.h -- on the device in batches (--on-device 1: gtdisc.hip) or by the same routines on the
+// host (--on-device 0) -- and a record outside that grammar is redone whole by the permissive reader below, which owns every message.
+// Both paths therefore write the same bytes.  A run that has to stop does so at the record the tool would stop at: what the records
+// before it gave is written first.
+#include <strings.h>
+#include "../host/vcf_input.h"
+#include "gtdisc_dev.h"
+
+namespace {
+
+struct Opt {
+    std::string truth, call, out;
+    int do_gq = 0, per_site = 0, on_device = 1, device = 0, batch = 4096, verbose = 0;
+};
+
+const char GTD_USAGE[] =
+    "Usage: gtdiscordance_hip -t <truth> -i <call> -o <output.tsv>\n"
+    "Options:\n"
+    "  -t, --truth <file>        truth file (VCF text, gzip / bgzip'd, or BCF)\n"
+    "  -i, --input <file>        input file, to be compared with truth file, typically a genotype call file\n"
+    "  -o, --output <file>       output\n"
+    "  -doGQ 1                   print the discordance indicator and GQ scores for each sample at each site\n"
+    "  -doGQ 2                   print the discordance indicator and GQ scores for each sample at each site, with extra info\n"
+    "  -doGQ 3                   print tidy gq summary\n"
+    "  -doGQ 4                   print tidy gq summary with hom/het details\n"
+    "  -doGQ 5                   per-sample doGQ 3\n"
+    "  -doGQ 6                   per-sample doGQ 4\n"
+    "  -doGQ 7                   per-sample doGQ 4, for the sites with missing GQ assume highest GQ value\n"
+    "  -doGQ 8                   doGQ 7, but for the genotype calling files without GQ tags sets GQ to second lowest PL\n"
+    "  -perSite 1                print position, sample, discordance indicator and hom/het type of every compared call to stdout\n"
+    "  --on-device 0|1 [1]       1: the sample columns are parsed, tallied and listed on the GPU; 0: on the host, no GPU touched\n"
+    "  --device INT [0]          the GPU\n"
+    "  --batch-records INT [4096] call records per device batch\n"
+    "  --verbose 0|1 [0]         record counts, bytes sent up and stage times\n"
+    "  -h, --help                print help\n\n";
+
+Opt parse_opt(int argc, char** argv) {
+    Opt o;
+    if (argc <= 1) { fputs(GTD_USAGE, stderr); exit(0); }
+    for (int i = 1; i < argc; i++) {
+        const char* a = argv[i];
+        if (!strcmp(a, "-h") || !strcmp(a, "--help")) { fputs(GTD_USAGE, stderr); exit(0); }
+        if (i + 1 >= argc) die("Missing value for arg:%s", a);
+        const char* v = argv[++i];
+        auto num = [&](int lo, int hi) {
+            char* e; const long x = strtol(v, &e, 10);
+            if (e == v || *e || x < lo || x > hi) die("%s takes an integer in %d .. %d, not '%s'", a, lo, hi, v);
+            return (int)x;
+        };
+        if (!strcmp(a, "-i") || !strcmp(a, "--input")) o.call = v;
+        else if (!strcmp(a, "-t") || !strcmp(a, "--truth")) o.truth = v;
+        else if (!strcmp(a, "-o") || !strcmp(a, "--output")) o.out = v;
+        else if (!strcasecmp(a, "-doGQ")) { o.do_gq = atoi(v); if (o.do_gq < 0 || o.do_gq > 8) die("Unknown doGq:%d", o.do_gq); }
+        else if (!strcasecmp(a, "-perSite")) o.per_site = num(0, 1);
+        else if (!strcmp(a, "--on-device")) o.on_device = num(0, 1);
+        else if (!strcmp(a, "--device")) o.device = num(0, 1 << 20);
+        else if (!strcmp(a, "--batch-records")) o.batch = num(1, 1 << 24);
+        else if (!strcmp(a, "--verbose")) o.verbose = num(0, 1);
+        else die("Unknown arg:%s", a);
+    }
+    if (o.call.empty()) die("Input file not specified. Please use -i/--input <file>.");
+    if (o.truth.empty()) die("Truth file not specified. Please use -t/--truth <file>.");
+    if (o.out.empty()) die("Output file not specified. Please use -o/--output <file>.");
+    return o;
+}
+
+// ---- the two files ---------------------------------------------------------------------------------------------------------------
+struct Input {
+    std::vector<uint8_t> text;                                   // the file's text, or the lines made from its BCF records
+    std::vector<std::string> header, samples;
+    std::vector<std::pair<int64_t, int64_t>> lines;              // [begin, end) of every record line
+    bool has_format(const char* id) const {
+        const std::string k = std::string("##FORMAT=<ID=") + id + ",";
+        for (const std::string& h : header) if (h.compare(0, k.size(), k) == 0) return true;
+        return false;
+    }
+};
+
+// BCF records -> the lines a VCF writer would give GT, GQ and PL (the other columns are '.': nothing reads them)
+void bcf_lines(std::vector<uint8_t>& raw, Input& in) {
+    BcfDict d; BcfIn c; c.buf = raw.data(); c.size = raw.size();
+    Vcf v;
+    bcf_header(c, d, v);
+    in.header = v.header; in.samples = v.samples;
+    const size_t N = v.samples.size();
+    std::string out; std::vector<int32_t> iv, gt, gq, pl; char num[16];
+    while (c.off < c.size) {
+        BcfRecAt at; int n_fmt, type, n;
+        bcf_scan_record(c, at);
+        Rec r;
+        bcf_shared(c, d, at, N, r, n_fmt);
+        int n_gt = 0, n_gq = 0, n_pl = 0; bool have_gt = false, have_gq = false, have_pl = false;
+        for (int k = 0; k < n_fmt; k++) {
+            c.typed(type, n); c.ints(type, n, iv);
+            const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
+            if (key == d.dict.end()) c.fail("BCF: undefined FORMAT key");
+            c.typed(type, n);
+            const size_t w = type == 1 ? 1 : type == 2 ? 2 : (type == 3 || type == 5) ? 4 : type == 7 ? 1 : 0;
+            const bool ints = type >= 1 && type <= 3;
+            if (ints && key->second == "GT") { c.ints(type, (int)(n * N), gt); n_gt = n; have_gt = true; }
+            else if (ints && key->second == "GQ") { c.ints(type, (int)(n * N), gq); n_gq = n; have_gq = true; }
+            else if (ints && key->second == "PL") { c.ints(type, (int)(n * N), pl); n_pl = n; have_pl = true; }
+            else { if (c.off + w * n * N > c.size) c.fail("truncated BCF record"); c.off += w * n * N; }
+        }
+        if (!have_gt) die("Could not find GT tag at position %ld.", r.pos0 + 1);
+        c.off = at.rec_end;
+        const int64_t begin = (int64_t)out.size();
+        out += r.chrom; out += '\t'; out += std::to_string(r.pos0 + 1); out += "\t.\t"; out += r.alleles[0]; out += '\t';
+        if (r.alleles.size() == 1) out += '.';
+        for (size_t a = 1; a < r.alleles.size(); a++) { if (a > 1) out += ','; out += r.alleles[a]; }
+        out += "\t.\t.\t.\tGT"; if (have_gq) out += ":GQ"; if (have_pl) out += ":PL";
+        auto put = [&](int32_t x) { if (x == INT32_MIN) out += '.'; else { snprintf(num, sizeof num, "%d", x); out += num; } };
+        for (size_t s = 0; s < N; s++) {
+            out += '\t';
+            int j = 0;
+            for (; j < n_gt && gt[s * n_gt + j] != INT32_MIN + 1; j++) {
+                const int32_t x = gt[s * n_gt + j];
+                if (j) out += (x & 1) ? '|' : '/';
+                if ((x >> 1) - 1 < 0) out += '.'; else put((x >> 1) - 1);
+            }
+            if (j == 0) out += '.';
+            if (have_gq) { out += ':'; if (n_gq < 1 || gq[s * n_gq] == INT32_MIN + 1) out += '.'; else put(gq[s * n_gq]); }
+            if (have_pl) {
+                out += ':';
+                int g = 0;
+                for (; g < n_pl && pl[s * n_pl + g] != INT32_MIN + 1; g++) { if (g) out += ','; put(pl[s * n_pl + g]); }
+                if (g == 0) out += '.';
+            }
+        }
+        in.lines.emplace_back(begin, (int64_t)out.size());
+        out += '\n';
+    }
+    in.text.assign(out.begin(), out.end());
+}
+
+Input read_input_file(const std::string& fn) {
+    Input in;
+    gzFile fp = gzopen(fn.c_str(), "r");                         // plain text, gzip / BGZF, or BCF inside either
+    if (!fp) die("Could not open file: %s", fn.c_str());
+    gzbuffer(fp, 1 << 20);
+    std::vector<uint8_t> raw, chunk(1 << 22);
+    int k;
+    while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) raw.insert(raw.end(), chunk.begin(), chunk.begin() + k);
+    gzclose(fp);
+    if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) { bcf_lines(raw, in); return in; }
+    in.text = std::move(raw);
+    const char* const t0 = (const char*)in.text.data();
+    const char* p = t0; const char* const end = p + in.text.size();
+    std::vector<std::string> f;
+    while (p < end) {
+        const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
+        const char* le = nl ? nl : end;
+        if (le > p) {
+            if (le - p >= 2 && p[0] == '#' && p[1] == '#') in.header.emplace_back(p, le);
+            else if (p[0] == '#') { split(std::string(p, le), '\t', f); for (size_t i = 9; i < f.size(); i++) in.samples.push_back(f[i]); }
+            else in.lines.emplace_back(p - t0, le - t0);
+        }
+        p = nl ? nl + 1 : end;
+    }
+    return in;
+}
+
+// the first nine columns of a record line
+struct Fixed {
+    std::string bad;                   // why the line cannot be compared (the run stops when it gets there)
+    int64_t pos = 0, s_off = 0, s_len = 0;
+    std::string first;                 // the first character of every allele
+    int gti = -1, gqi = -1, pli = -1;
+    uint64_t map() const { uint64_t m = 0; for (size_t a = 0; a < 16; a++) m |= (uint64_t)(a < first.size() ? gtd::base_of((uint8_t)first[a]) : 15u) << (4 * a); return m; }
+};
+
+Fixed parse_nine(const Input& in, const size_t i, const char* which) {
+    Fixed f;
+    const char* const t0 = (const char*)in.text.data();
+    const char* lb = t0 + in.lines[i].first; const char* le = t0 + in.lines[i].second;
+    const char* col_at[10]; int nc = 0; col_at[0] = lb;
+    for (const char* q = lb; q < le && nc < 9; q++) if (*q == '\t') col_at[++nc] = q + 1;
+    char msg[256];
+    if (nc >= 1) f.pos = atoll(std::string(col_at[1], col_at[2 > nc ? nc : 2]).c_str());
+    if (nc < 9) { snprintf(msg, sizeof msg, "Record %zu of the %s file has fewer than 10 columns (a FORMAT/GT column is required).", i + 1, which); f.bad = msg; return f; }
+    auto col = [&](int k) { return std::string(col_at[k], (size_t)(col_at[k + 1] - 1 - col_at[k])); };
+    const std::string ref = col(3), alt = col(4);
+    std::vector<std::string> g;
+    if (ref.empty()) { snprintf(msg, sizeof msg, "Empty REF at position %lld of the %s file.", (long long)f.pos, which); f.bad = msg; return f; }
+    f.first += ref[0];
+    if (alt != ".") { split(alt, ',', g); for (auto& x : g) f.first += x.empty() ? '?' : x[0]; }
+    split(col(8), ':', g);
+    for (size_t k = 0; k < g.size(); k++) {
+        if (g[k] == "GT" && f.gti < 0) f.gti = (int)k;
+        if (g[k] == "GQ" && f.gqi < 0) f.gqi = (int)k;
+        if (g[k] == "PL" && f.pli < 0) f.pli = (int)k;
+    }
+    if (f.gti < 0) { snprintf(msg, sizeof msg, "Could not find GT tag at position %lld of the %s file.", (long long)f.pos, which); f.bad = msg; return f; }
+    f.s_off = col_at[9] - t0; f.s_len = le - col_at[9];
+    if (f.s_len > INT32_MAX) { snprintf(msg, sizeof msg, "The record at position %lld of the %s file is longer than 2 GiB.", (long long)f.pos, which); f.bad = msg; }
+    return f;
+}
+
+// a call record and the truth record it is compared with
+struct Pair { size_t ci, ti; int32_t nsites1; gtd::Rec rec; };
+
+// ---- the run's state -------------------------------------------------------------------------------------------------------------
+struct Run {
+    Opt o;
+    Input truth, call;
+    std::vector<Fixed> tf, cf;
+    std::vector<Pair> pairs;
+    std::string stop;                  // why the run ends behind the last pair (empty: it does not)
+    int32_t N = 0;
+    int list = 0;
+    std::vector<int64_t> table;        // cells and call-missing counts the host tallied
+    FILE* out_fp = nullptr;
+    std::string list_buf, site_buf;
+    GtdDev* dev = nullptr;
+    long n_host = 0; int64_t text_up = 0;
+    double t_read = 0, t_nine = 0, t_dev = 0, t_host = 0;
+
+    void flush(bool all) {
+        if (all || list_buf.size() > (1u << 22)) { if (!list_buf.empty()) fwrite(list_buf.data(), 1, list_buf.size(), out_fp); list_buf.clear(); }
+        if (all || site_buf.size() > (1u << 22)) { if (!site_buf.empty()) fwrite(site_buf.data(), 1, site_buf.size(), stdout); site_buf.clear(); }
+    }
+    // the run ends here: what the records so far gave is written, nothing stays in flight on the device
+    [[noreturn]] void stop_run(const char* fmt, ...) {
+        if (dev) gtd_dev_quiesce(dev);
+        flush(true); fflush(out_fp);
+        va_list ap; va_start(ap, fmt); die_v(fmt, ap);
+    }
+    void count(const int32_t s, const uint32_t cell, const uint32_t gq) { table[((size_t)s * gtd::N_CELLS + cell) * gtd::N_GQ + gq]++; }
+    void call_missing(const int32_t s) { table[(size_t)N * gtd::N_CELLS * gtd::N_GQ + s]++; }
+    void lines(const Pair& p, const int32_t s, const uint32_t cell, const uint32_t gq) {
+        uint8_t b[gtd::LINE_BOUND];
+        if (list) { gtd::Emit<true> e{b, 0u, (uint32_t)sizeof b}; gtd::list_line(e, list, p.nsites1, (uint32_t)s, cell, gq); list_buf.append((const char*)b, e.n); }
+        if (o.per_site) { gtd::Emit<true> e{b, 0u, (uint32_t)sizeof b}; gtd::site_line(e, p.rec.pos, (uint32_t)s, cell); site_buf.append((const char*)b, e.n); }
+    }
+    void record_permissive(const Pair& p);
+    void record_host(const Pair& p, std::vector<uint8_t>& planes);
+};
+
+// ---- the permissive reader: one record by the tool's own rules, with the run's messages --------------------------------------------
+typedef std::pair<const char*, const char*> Span;
+void split_cols(const char* b, const char* e, std::vector<Span>& out) {
+    out.clear();
+    for (;;) { const char* t = (const char*)memchr(b, '\t', (size_t)(e - b)); if (!t) { out.emplace_back(b, e); return; } out.emplace_back(b, t); b = t + 1; }
+}
+bool nth_field(Span c, const int k, Span& f) {
+    const char* b = c.first;
+    for (int i = 0; i < k; i++) { b = (const char*)memchr(b, ':', (size_t)(c.second - b)); if (!b) return false; b++; }
+    const char* e = (const char*)memchr(b, ':', (size_t)(c.second - b));
+    f = Span(b, e ? e : c.second);
+    return true;
+}
+// an integer of at most nine digits, with or without '-'
+bool host_int(const char* b, const char* e, long& v) {
+    const bool neg = b < e && *b == '-'; if (neg) b++;
+    if (b == e || e - b > 9) return false;
+    v = 0;
+    for (; b < e; b++) { if (*b < '0' || *b > '9') return false; v = v * 10 + (*b - '0'); }
+    if (neg) v = -v;
+    return true;
+}
+// two alleles, each '.' or an index: a0 / a1 = -1 for '.'
+bool host_gt(Span f, long& a0, long& a1) {
+    const char* s = f.first; while (s < f.second && *s != '/' && *s != '|') s++;
+    if (s == f.second) return false;
+    auto one = [](const char* b, const char* e, long& a) { if (e - b == 1 && *b == '.') { a = -1; return true; } return host_int(b, e, a) && a >= 0; };
+    return one(f.first, s, a0) && one(s + 1, f.second, a1);
+}
+
+void Run::record_permissive(const Pair& p) {
+    const Fixed& T = tf[p.ti]; const Fixed& C = cf[p.ci];
+    const gtd::Rec& r = p.rec;
+    const long long pos = (long long)r.pos;
+    std::vector<Span> tc, cc;
+    const char* tt = (const char*)truth.text.data() + T.s_off; const char* ct = (const char*)call.text.data() + C.s_off;
+    split_cols(tt, tt + T.s_len, tc); split_cols(ct, ct + C.s_len, cc);
+    if (tc.size() != (size_t)N) stop_run("The truth record at position %lld has %zu sample columns, the header names %d samples.", pos, tc.size(), N);
+    if (cc.size() != (size_t)N) stop_run("The call record at position %lld has %zu sample columns, the header names %d samples.", pos, cc.size(), N);
+    std::vector<int> pl_gq;
+    if (r.gq_mode == gtd::GQ_PL && r.c_nal > 1) {                 // the tool's loop over every sample before it looks at a genotype
+        pl_gq.resize((size_t)N);
+        for (int32_t s = 0; s < N; s++) {
+            Span f;
+            if (!nth_field(cc[s], r.c_pli, f)) stop_run("Sample %d at position %lld has no PL field.", s, pos);
+            gtd::PlWalk w; int n = 0;
+            for (const char* b = f.first;; n++) {
+                const char* e = (const char*)memchr(b, ',', (size_t)(f.second - b)); if (!e) e = f.second;
+                long v;
+                if (e - b == 1 && *b == '.') w.add(-1);
+                else if (!host_int(b, e, v)) stop_run("Sample %d at position %lld: PL value '%s' is not an integer.", s, pos, std::string(b, e).c_str());
+                else if (v < 0) { if (v < w.second) w.second = (int)v; }      // (the tool takes it for the second best; GQ is then refused below)
+                else w.add((int)v);
+                if (e == f.second) { n++; break; }
+                b = e + 1;
+            }
+            if (n != r.nG) stop_run("Sample %d at position %lld has %d PL values; %d alleles take %d.", s, pos, n, r.c_nal, r.nG);
+            if (!w.zero) stop_run("Sample %d at position %lld: no PL value is 0 or missing (-doGQ 8 takes the lowest PL for 0).", s, pos);
+            pl_gq[s] = w.gq();
+        }
+    }
+    for (int32_t s = 0; s < N; s++) {
+        Span tg, cg; long t0, t1, c0, c1;
+        if (!nth_field(tc[s], r.t_gti, tg) || !host_gt(tg, t0, t1))
+            stop_run("Sample %d at position %lld: the true genotype '%s' is not a diploid genotype.", s, pos, std::string(tc[s].first, tc[s].second).c_str());
+        if (!nth_field(cc[s], r.c_gti, cg) || !host_gt(cg, c0, c1))
+            stop_run("Sample %d at position %lld: the called genotype '%s' is not a diploid genotype.", s, pos, std::string(cc[s].first, cc[s].second).c_str());
+        if (t0 < 0 || t1 < 0) stop_run("Sample %d at position %lld: the true genotype is missing.", s, pos);
+        if (c0 < 0 || c1 < 0) { call_missing(s); continue; }
+        auto base = [&](const Fixed& F, long a, const char* which) {
+            const uint32_t b = a < (long)F.first.size() ? gtd::base_of((uint8_t)F.first[(size_t)a]) : 15u;
+            if (b > 3u) stop_run("Sample %d at position %lld: allele %ld of the %s genotype is not an allele that starts with one of ACGTacgt0123.", s, pos, a, which);
+            return b;
+        };
+        const uint32_t tb = base(T, t0, "true") | base(T, t1, "true") << 4;
+        const uint32_t cb = base(C, c0, "called") | base(C, c1, "called") << 4;
+        long gq = 0;
+        if (r.gq_mode == gtd::GQ_MAX || (r.gq_mode == gtd::GQ_PL && r.c_nal == 1)) gq = gtd::MAX_GQ;
+        else if (r.gq_mode == gtd::GQ_PL) gq = pl_gq[s];
+        else if (r.gq_mode == gtd::GQ_TAG) {
+            Span f;
+            if (!nth_field(cc[s], r.c_gqi, f) || !host_int(f.first, f.second, gq)) gq = 0;
+        }
+        if (r.gq_mode != gtd::GQ_NONE && (gq < 1 || gq > gtd::MAX_GQ)) stop_run("Sample %d at position %lld: GQ is not a value in 1 .. 127.", s, pos);
+        const uint32_t cell = gtd::classify(tb, cb);
+        count(s, cell, (uint32_t)gq);
+        lines(p, s, cell, (uint32_t)gq);
+    }
+}
+
+// --on-device 0: the plain grammar by the routines the kernels run, a column at a time; the permissive reader for the rest
+void Run::record_host(const Pair& p, std::vector<uint8_t>& planes) {
+    uint8_t* tb = planes.data(); uint8_t* cb = tb + N; uint8_t* gq = cb + N;
+    if (gtd::record_plain(truth.text.data(), call.text.data(), p.rec, N, tb, cb, gq) != gtd::ST_OK) { n_host++; record_permissive(p); return; }
+    for (int32_t s = 0; s < N; s++) {
+        if (cb[s] == gtd::CALL_MISSING) { call_missing(s); continue; }
+        const uint32_t cell = gtd::classify(tb[s], cb[s]);
+        count(s, cell, gq[s]);
+        if (list || o.per_site) lines(p, s, cell, gq[s]);
+    }
+}
+
+// ---- the tables of the tool's lines 629-833 ------------------------------------------------------------------------------------------
+void write_tables(Run& R, const long nsites1, const long nsites2) {
+    const int N = R.N, mode = R.o.do_gq;
+    FILE* f = R.out_fp;
+    enum { HH0, HH1, TT0, TT1, HT, TH };
+    auto cell = [&](int s, int c, int k) -> long long { return k < gtd::N_GQ ? (long long)R.table[((size_t)s * gtd::N_CELLS + c) * gtd::N_GQ + k] : 0; };
+    std::vector<long long> compared((size_t)N, 0);
+    for (int s = 0; s < N; s++) for (int c = 0; c < gtd::N_CELLS; c++) for (int k = 0; k < gtd::N_GQ; k++) compared[s] += cell(s, c, k);
+    if (mode == 0) {
+        for (int s = 0; s < N; s++) {
+            long long c[gtd::N_CELLS];
+            for (int j = 0; j < gtd::N_CELLS; j++) { c[j] = 0; for (int k = 0; k < gtd::N_GQ; k++) c[j] += cell(s, j, k); }
+            const long long cmp = compared[s], disc = c[HH1] + c[TT1] + c[HT] + c[TH], mis = (long long)R.table[(size_t)N * gtd::N_CELLS * gtd::N_GQ + s];
+            const double n = (double)cmp;
+            fprintf(f, "%s\t%ld\t%ld\t%lld\t%lld\t%lld\t%ld\t%lld\t%f\t%f\t%f\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%f\t%f\t%f\t%f\t%f\t%f\n",
+                    R.truth.samples[s].c_str(), nsites1, nsites2, cmp, mis, disc, nsites1 - nsites2, cmp - disc,
+                    (double)(1.0 - ((double)cmp / (double)nsites1)), (double)disc / n, (double)(cmp - disc) / n,
+                    c[HH0], c[TT0], c[HH1], c[HT], c[TH], c[TT1],
+                    (double)c[HH0] / n, (double)c[TT0] / n, (double)c[HH1] / n, (double)c[HT] / n, (double)c[TH] / n, (double)c[TT1] / n);
+        }
+        return;
+    }
+    // the eight counts of a -doGQ 4 row: discordant (all, hom->hom, hom->het, het->hom, het->het), concordant (all, hom->hom, het->het)
+    auto row = [&](int s0, int s1, int k, long long r[8]) {
+        for (int j = 0; j < 8; j++) r[j] = 0;
+        for (int s = s0; s < s1; s++) {
+            r[1] += cell(s, HH1, k); r[2] += cell(s, HT, k); r[3] += cell(s, TH, k); r[4] += cell(s, TT1, k);
+            r[6] += cell(s, HH0, k); r[7] += cell(s, TT0, k);
+        }
+        r[0] = r[1] + r[2] + r[3] + r[4]; r[5] = r[6] + r[7];
+    };
+    long long r[8];
+    if (mode == 3 || mode == 4) {
+        for (int k = 1; k < 130; k++) {
+            row(0, N, k, r);
+            if (mode == 3) fprintf(f, "%d\t%lld\t%lld\n", k, r[0], r[5]);
+            else fprintf(f, "%d\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\n", k, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
+        }
+    } else if (mode >= 5) {
+        for (int s = 0; s < N; s++) for (int k = 1; k < 130; k++) {
+            row(s, s + 1, k, r);
+            if (mode == 5) fprintf(f, "%d\t%d\t%lld\t%lld\t%lld\n", s, k, r[0], r[5], compared[s]);
+            else fprintf(f, "%d\t%d\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\n", s, k, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], compared[s]);
+        }
+    }
+}
+
+// ---- --on-device 1 ---------------------------------------------------------------------------------------------------------------
+void run_device(Run& R) {
+    const size_t K = R.pairs.size();
+    const int32_t N = R.N;
+    // a batch's listing is bounded by LINE_BOUND bytes a call: no more records than 64 MiB of it (one at least)
+    int64_t B = R.o.batch;
+    const int64_t per_rec = (int64_t)N * ((R.list || R.o.per_site) ? gtd::LINE_BOUND : 3);
+    B = std::max<int64_t>(1, std::min<int64_t>(B, (64ll << 20) / std::max<int64_t>(per_rec, 1)));
+    const int64_t nb = ((int64_t)K + B - 1) / B;
+    int64_t max_text = 1;
+    for (int64_t b = 0; b < nb; b++) {
+        int64_t t = 0;
+        for (size_t j = (size_t)(b * B); j < std::min(K, (size_t)((b + 1) * B)); j++) t += R.pairs[j].rec.t_len + (int64_t)R.pairs[j].rec.c_len;
+        max_text = std::max(max_text, t);
+    }
+    char err[256];
+    R.dev = gtd_dev_create(R.o.device, N, (int32_t)std::min<int64_t>(B, std::max<size_t>(K, 1)), max_text, R.list, R.o.per_site, err, sizeof err);
+    if (!R.dev) R.stop_run("--on-device 1: %s (device %d; --on-device 0 compares on the host)", err, R.o.device);
+    auto submit = [&](int64_t b) {
+        const double t0 = now_s();
+        const int slot = (int)(b & 1);
+        uint8_t* text = gtd_dev_text(R.dev, slot); gtd::Rec* recs = gtd_dev_recs(R.dev, slot);
+        int64_t at = 0; int32_t n = 0;
+        for (size_t j = (size_t)(b * B); j < std::min(K, (size_t)((b + 1) * B)); j++, n++) {
+            const Pair& p = R.pairs[j];
+            gtd::Rec r = p.rec;
+            memcpy(text + at, R.truth.text.data() + p.rec.t_off, (size_t)r.t_len); r.t_off = at; at += r.t_len;
+            memcpy(text + at, R.call.text.data() + p.rec.c_off, (size_t)r.c_len); r.c_off = at; at += r.c_len;
+            recs[n] = r;
+        }
+        if (gtd_dev_submit(R.dev, slot, n, at) != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
+        R.text_up += at; R.t_dev += now_s() - t0;
+    };
+    auto retire = [&](int64_t b) {
+        double t0 = now_s();
+        GtdBatchOut out;
+        if (gtd_dev_wait(R.dev, (int)(b & 1), &out) != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
+        R.t_dev += now_s() - t0; t0 = now_s();
+        int32_t n = 0;
+        for (size_t j = (size_t)(b * B); j < std::min(K, (size_t)((b + 1) * B)); j++, n++) {
+            if (out.status[n] != gtd::ST_OK) { R.n_host++; R.record_permissive(R.pairs[j]); continue; }
+            if (R.list) R.list_buf.append((const char*)out.list_text + out.list_off[n], (size_t)(out.list_off[n + 1] - out.list_off[n]));
+            if (R.o.per_site) R.site_buf.append((const char*)out.site_text + out.site_off[n], (size_t)(out.site_off[n + 1] - out.site_off[n]));
+            R.flush(false);
+        }
+        R.t_host += now_s() - t0;
+    };
+    two_in_flight(nb, submit, retire);
+    std::vector<int64_t> dt(R.table.size());
+    if (gtd_dev_table(R.dev, dt.data()) != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
+    for (size_t i = 0; i + 2 < dt.size(); i++) R.table[i] += dt[i];
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    Run R;
+    R.o = parse_opt(argc, argv);
+    const Opt& o = R.o;
+    double t0 = now_s();
+    R.truth = read_input_file(o.truth);
+    R.call = read_input_file(o.call);
+    R.out_fp = fopen(o.out.c_str(), "w");
+    if (!R.out_fp) die("Could not open output file %s for writing", o.out.c_str());
+    R.t_read = now_s() - t0; t0 = now_s();
+    if (R.truth.samples.empty()) die("The truth file %s names no sample.", o.truth.c_str());
+    if (R.truth.samples.size() != R.call.samples.size())
+        die("The truth file names %zu samples and the call file %zu: samples are assumed to appear in the same order and quantity in both files.", R.truth.samples.size(), R.call.samples.size());
+    if (R.truth.samples.size() > (size_t)(INT32_MAX / gtd::LINE_BOUND)) die("Too many samples.");
+    R.N = (int32_t)R.truth.samples.size();
+    R.list = o.do_gq == 1 ? gtd::LIST_GQ : o.do_gq == 2 ? gtd::LIST_GQ_TYPE : gtd::LIST_NONE;
+    const bool has_gq = R.call.has_format("GQ"), has_pl = R.call.has_format("PL");
+    if (o.do_gq == 7 && !has_gq) die("-doGQ 7 needs a call file whose header declares the GQ tag.");
+    if (o.do_gq == 8 && !has_gq && !has_pl) die("-doGQ 8 is only supported for genotype calling files with GQ or PL tags");
+    R.table.assign((size_t)vgl_disc_table_len(R.N), 0);
+
+    // the first nine columns, then the tool's merge on POS: nsites1 counts the truth records read so far
+    const size_t nT = R.truth.lines.size(), nC = R.call.lines.size();
+    R.tf.resize(nT); R.cf.resize(nC);
+    for (size_t i = 0; i < nT; i++) R.tf[i] = parse_nine(R.truth, i, "truth");
+    for (size_t i = 0; i < nC; i++) R.cf[i] = parse_nine(R.call, i, "call");
+    size_t ti = 0; long nsites1 = 1; char msg[320];
+    for (size_t ci = 0; ci < nC && R.stop.empty(); ci++) {
+        const Fixed& C = R.cf[ci];
+        if (!C.bad.empty()) { R.stop = C.bad; break; }
+        while (ti < nT && R.tf[ti].bad.empty() && C.pos > R.tf[ti].pos) { ti++; nsites1++; }
+        if (ti < nT && !R.tf[ti].bad.empty()) { R.stop = R.tf[ti].bad; break; }
+        if (ti >= nT || C.pos != R.tf[ti].pos) {
+            snprintf(msg, sizeof msg, "The call file has a record at position %lld and the truth file has none: the truth file must hold every site of the call file.", (long long)C.pos);
+            R.stop = msg; break;
+        }
+        const Fixed& T = R.tf[ti];
+        Pair p; p.ci = ci; p.ti = ti; p.nsites1 = (int32_t)nsites1;
+        gtd::Rec& r = p.rec;
+        memset(&r, 0, sizeof r);
+        r.t_off = T.s_off; r.t_len = (int32_t)T.s_len; r.c_off = C.s_off; r.c_len = (int32_t)C.s_len;
+        r.t_map = T.map(); r.c_map = C.map(); r.pos = C.pos; r.nsites1 = p.nsites1;
+        r.t_nal = (int32_t)T.first.size(); r.c_nal = (int32_t)C.first.size();
+        r.t_gti = T.gti; r.c_gti = C.gti; r.c_gqi = C.gqi; r.c_pli = C.pli;
+        r.nG = gtd::n_genotypes(r.c_nal);
+        if (o.do_gq == 0) r.gq_mode = gtd::GQ_NONE;
+        else if (o.do_gq <= 6) {
+            r.gq_mode = gtd::GQ_TAG;
+            if (C.gqi < 0) { snprintf(msg, sizeof msg, "The call record at position %lld has no GQ tag (-doGQ %d reads it; -doGQ 7 assumes the highest GQ there).", (long long)C.pos, o.do_gq); R.stop = msg; break; }
+        } else if (o.do_gq == 7 || has_gq) r.gq_mode = C.gqi >= 0 ? gtd::GQ_TAG : gtd::GQ_MAX;
+        else {
+            r.gq_mode = gtd::GQ_PL;
+            if (C.pli < 0) { snprintf(msg, sizeof msg, "The call record at position %lld has no PL tag (-doGQ 8 on a call file without GQ reads it).", (long long)C.pos); R.stop = msg; break; }
+            if (r.c_nal > 5) { snprintf(msg, sizeof msg, "The call record at position %lld has %d alleles: -doGQ 8 reads PL for at most 5.", (long long)C.pos, r.c_nal); R.stop = msg; break; }
+        }
+        R.pairs.push_back(p);
+    }
+    const long nsites2 = (long)R.pairs.size();
+    if (R.stop.empty() && nT > 0) nsites1 += (long)(nT - 1 - ti);
+    R.t_nine = now_s() - t0;
+
+    if (o.on_device) run_device(R);
+    else {
+        t0 = now_s();
+        std::vector<uint8_t> planes(3 * (size_t)R.N);
+        for (const Pair& p : R.pairs) { R.record_host(p, planes); R.flush(false); }
+        R.t_host = now_s() - t0;
+    }
+    if (!R.stop.empty()) R.stop_run("%s", R.stop.c_str());
+    R.flush(true);
+
+    fprintf(stderr, "Comparing the genotypes in the truth file %s and the call file %s\n", o.truth.c_str(), o.call.c_str());
+    fprintf(stderr, "Number of sites in truth file: %ld\n", nsites1);
+    fprintf(stderr, "Number of sites in the truth file not in the call file: %ld\n", nsites1 - nsites2);
+    fprintf(stderr, "Number of sites used in comparison: %ld\n", nsites2);
+    if (R.list == gtd::LIST_NONE) write_tables(R, nsites1, nsites2);
+    if (o.verbose)
+        fprintf(stderr, "[gtdisc] on-device %d: records %ld, redone on the host %ld, text bytes sent up %lld; read %.3f s, nine columns and merge %.3f s, device %.3f s, host %.3f s\n",
+                o.on_device, nsites2, R.n_host, (long long)R.text_up, R.t_read, R.t_nine, R.t_dev, R.t_host);
+    fprintf(stderr, "\n\nFinished running gtDiscordance\n\t-> Output file: %s\n", o.out.c_str());
+    if (R.dev) gtd_dev_destroy(R.dev);
+    fclose(R.out_fp);
+    fflush(stdout);
+    return 0;
+}

@@ -4,8 +4,13 @@
 The table is int64: cell[sample][6][128] indexed by GQ, then callmis[sample], then sites[2] = kept, skipped.
 `tally_into` adds one tile of device tensors to a device table; `Simulator.discordance(1)` has a context tally every tile
 it simulates; `format_table` prints a table in the layouts of the reference's misc/gtDiscordance (-doGQ 0, 3, 4, 5, 6).
+
+`compare_files` is the other way in: a call file against a truth file, both on disk, through the program gtdiscordance_hip
+(vcfgl_amd/csrc/misc), which covers every -doGQ mode, the per-call listings included.
 """
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 
@@ -104,3 +109,26 @@ def format_table(table, sample_names, mode=0):
                 r = row(cell[i], k)
                 out.append("\t".join(str(x) for x in ([i, k, r[0], r[5], compared] if mode == 5 else [i, k] + r + [compared])))
     return "".join(x + "\n" for x in out)
+
+
+GTDISC_PROGRAM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "gtdiscordance_hip")
+
+
+def compare_files(truth, call, out, do_gq=0, per_site=False, on_device=True, device=None, batch_records=None, verbose=False,
+                  timeout=None, env=None):
+    """Runs gtdiscordance_hip -t `truth` -i `call` -o `out` -doGQ `do_gq` [-perSite 1] as a fresh child process and returns
+    (returncode, stdout, stderr) as text; stdout holds the -perSite lines, `out` the table or the -doGQ 1 / 2 listing.
+    on_device=False compares on the host and touches no GPU; on_device=True without a GPU fails (returncode 1): there is no
+    fallback.  A missing program is an error (build the package first)."""
+    if not os.path.exists(GTDISC_PROGRAM):
+        raise FileNotFoundError("%s is not built (make -C vcfgl_amd/csrc all)" % GTDISC_PROGRAM)
+    cmd = [GTDISC_PROGRAM, "-t", str(truth), "-i", str(call), "-o", str(out), "-doGQ", str(int(do_gq)), "-perSite", "1" if per_site else "0",
+           "--on-device", "1" if on_device else "0"]
+    if device is not None:
+        cmd += ["--device", str(int(device))]
+    if batch_records is not None:
+        cmd += ["--batch-records", str(int(batch_records))]
+    if verbose:
+        cmd += ["--verbose", "1"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
+    return r.returncode, r.stdout, r.stderr
