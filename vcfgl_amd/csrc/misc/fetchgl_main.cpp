@@ -1,0 +1,385 @@
+// fetchgl_main.cpp -- fetchgl_hip: the reference's misc/fetchGl (one genotype's FORMAT/GL of every sample, as CSV) for this platform.
+//   fetchgl_hip -i file -gt XY [-o out.csv] [--on-device 0|1] [--device INT] [--batch-records INT] [--messages 0|1] [--verbose 0|1]
+// The file is read whole (plain, gzip or bgzip text through zlib, or BCF inside either).  The host finds the records, reads the first
+// nine columns of each (for BCF: the shared block and the FORMAT field headers), finds GL and the genotype's index g, and keeps a small
+// note per record.  The records that get a CSV line are then read by the rules of fgl_core.h -- on the device in batches
+// (--on-device 1: fetchgl.hip) or by the same routines on the host (--on-device 0) -- and a record those rules hand back (a token
+// outside the device grammar, a value index outside the record's values, a wrong column count) is redone whole by the strtod reader
+// below, which owns every message.  Both paths therefore write the same bytes.  A run that has to stop does so at the record where the
+// host path stops: the lines and messages of the records before it are written first.
+#include "../host/vcf_input.h"
+#include "fgl_dev.h"
+
+namespace {
+
+struct Opt {
+    std::string in, gt, out;
+    int on_device = 1, device = 0, batch = 4096, messages = 1, verbose = 0;
+};
+
+const char FGL_USAGE[] =
+    "Usage: fetchgl_hip -i <input vcf> -gt <genotype to fetch>\n"
+    "Example: fetchgl_hip -i input.vcf -gt AA\n"
+    "Options:\n"
+    "  -i, --input <file>        record file (VCF text, gzip / bgzip'd, or BCF)\n"
+    "  -gt, --genotype XY        the genotype: two characters, each the first character of an allele's name\n"
+    "  -o <file>                 the CSV goes to <file> [stdout]\n"
+    "  --on-device 0|1 [1]       1: the sample columns are parsed and the CSV lines formatted on the GPU; 0: on the host, no GPU touched\n"
+    "  --device INT [0]          the GPU\n"
+    "  --batch-records INT [4096] records per device batch (and no more than 64 MiB of text in one)\n"
+    "  --messages 0|1 [1]        the tool's per-record lines on stderr\n"
+    "  --verbose 0|1 [0]         record counts, bytes sent up and received, stage times\n"
+    "  -h, --help                print help\n\n";
+
+Opt parse_opt(int argc, char** argv) {
+    Opt o;
+    if (argc <= 1) { fputs(FGL_USAGE, stderr); exit(0); }
+    for (int i = 1; i < argc; i++) {
+        const char* a = argv[i];
+        if (!strcmp(a, "-h") || !strcmp(a, "--help")) { fputs(FGL_USAGE, stderr); exit(0); }
+        if (i + 1 >= argc) die("Missing value for arg:%s", a);
+        const char* v = argv[++i];
+        auto num = [&](int lo, int hi) {
+            char* e; const long x = strtol(v, &e, 10);
+            if (e == v || *e || x < lo || x > hi) die("%s takes an integer in %d .. %d, not '%s'", a, lo, hi, v);
+            return (int)x;
+        };
+        if (!strcmp(a, "-i") || !strcmp(a, "--input")) o.in = v;
+        else if (!strcmp(a, "-gt") || !strcmp(a, "--genotype")) o.gt = v;
+        else if (!strcmp(a, "-o")) o.out = v;
+        else if (!strcmp(a, "--on-device")) o.on_device = num(0, 1);
+        else if (!strcmp(a, "--device")) o.device = num(0, 1 << 20);
+        else if (!strcmp(a, "--batch-records")) o.batch = num(1, 1 << 24);
+        else if (!strcmp(a, "--messages")) o.messages = num(0, 1);
+        else if (!strcmp(a, "--verbose")) o.verbose = num(0, 1);
+        else die("Unknown arg:%s", a);
+    }
+    if (o.in.empty()) die("Input file not specified. Exiting...");
+    if (o.gt.empty()) die("Genotype to fetch not specified. Exiting...");
+    if (o.gt.size() != 2) die("A genotype is exactly two characters, not '%s'.", o.gt.c_str());
+    return o;
+}
+
+// what the host keeps of a record: where its sample columns (BCF: its GL vectors) lie, GL's place, the two alleles
+struct Note {
+    int64_t pos = 0, off = 0;
+    int32_t len = 0;                   // text: bytes of the sample columns; BCF: the vector length
+    int32_t k = 0;
+    int16_t a0 = -1, a1 = -1;
+    bool halt = false;                 // the run stops at this record, behind its message
+    bool found() const { return a0 >= 0 && a1 >= 0; }
+    bool line() const { return found() && !halt; }
+    int32_t g() const { return fgl::genotype_of(a0, a1); }
+};
+
+struct Run {
+    Opt o;
+    std::vector<uint8_t> raw;          // the file's bytes, inflated
+    bool bcf = false;
+    std::vector<std::string> header, samples;
+    std::vector<Note> notes;           // the records in file order, up to the one the run stops at
+    std::string stop;                  // why the run ends behind the last note (empty: it does not)
+    int64_t N = 0;
+    FILE* out_fp = nullptr;
+    std::string csv_buf, msg_buf;
+    FglDev* dev = nullptr;
+    long n_lines = 0, n_host = 0; int64_t up = 0, down = 0;
+    double t_read = 0, t_nine = 0, t_dev = 0, t_host = 0;
+
+    void flush(bool all) {
+        if (all || csv_buf.size() > (1u << 22)) { if (!csv_buf.empty()) fwrite(csv_buf.data(), 1, csv_buf.size(), out_fp); csv_buf.clear(); }
+        if (all || msg_buf.size() > (1u << 20)) { if (!msg_buf.empty()) fwrite(msg_buf.data(), 1, msg_buf.size(), stderr); msg_buf.clear(); }
+    }
+    // the run ends here: what the records so far gave is written, nothing stays in flight on the device
+    [[noreturn]] void stop_run(const char* fmt, ...) {
+        if (dev) fgl_dev_quiesce(dev);
+        flush(true); fflush(out_fp);
+        va_list ap; va_start(ap, fmt); die_v(fmt, ap);
+    }
+    // the tool's line on stderr for a record
+    void message(const Note& n) {
+        if (!o.messages) return;
+        char b[256];
+        if (!n.found()) snprintf(b, sizeof b, "Requested genotype %s not found at position %lld. Skipping...\n", o.gt.c_str(), (long long)n.pos);
+        else snprintf(b, sizeof b, "Requested genotype's first allele corresponds to allele %d and second allele corresponds to allele %d at position %lld.\n",
+                      (int)n.a0, (int)n.a1, (long long)n.pos);
+        msg_buf += b;
+    }
+    void put_line(const Note& n, const uint32_t* plane) {
+        uint8_t b[fgl::VALUE_BOUND];
+        { vgl_fetchgl::Emit<true> e{b, 0u, (uint32_t)sizeof b}; fgl::put_pos(e, (uint64_t)n.pos); csv_buf.append((const char*)b, e.n); }
+        for (int64_t s = 0; s < N; s++) { vgl_fetchgl::Emit<true> e{b, 0u, (uint32_t)sizeof b}; fgl::put_value(e, plane[s], s == N - 1); csv_buf.append((const char*)b, e.n); }
+        n_lines++;
+    }
+    void record_strtod(const Note& n, std::vector<uint32_t>& plane);
+    void record_host(const Note& n, std::vector<uint32_t>& plane);
+    void notes_text();
+    void notes_bcf();
+};
+
+// ---- the strtod reader: one record of VCF text by the tool's own reading of its values, with the run's messages ---------------------
+void Run::record_strtod(const Note& n, std::vector<uint32_t>& plane) {
+    const char* const t = (const char*)raw.data() + n.off; const char* const end = t + n.len;
+    const long long pos = (long long)n.pos;
+    const int32_t g = n.g();
+    std::vector<std::pair<const char*, const char*>> field;            // the GL field of every column (empty pair: one missing value)
+    for (const char* p = t;;) {
+        const char* ce = (const char*)memchr(p, '\t', (size_t)(end - p)); if (!ce) ce = end;
+        const char* b = p;
+        for (int f = 0; f < n.k && b; f++) { b = (const char*)memchr(b, ':', (size_t)(ce - b)); if (b) b++; }
+        if (!b) field.emplace_back(nullptr, nullptr);
+        else { const char* e = (const char*)memchr(b, ':', (size_t)(ce - b)); field.emplace_back(b, e ? e : ce); }
+        if (ce == end) break;
+        p = ce + 1;
+    }
+    if ((int64_t)field.size() != N) stop_run("The record at position %lld has %zu sample columns, the header names %lld samples.", pos, field.size(), (long long)N);
+    int64_t n_gls = 0;
+    for (const auto& f : field) { int64_t c = 1; for (const char* q = f.first; q && q < f.second; q++) c += *q == ','; n_gls = std::max(n_gls, c); }
+    if (g >= n_gls)
+        stop_run("The genotype %s is value %d of FORMAT/GL at position %lld, and the record's samples carry at most %lld values (the tool reads outside its buffer there).",
+                 o.gt.c_str(), g, pos, (long long)n_gls);
+    for (int64_t s = 0; s < N; s++) {
+        const char* b = field[s].first; const char* const fe = field[s].second;
+        if (!b) { plane[s] = g == 0 ? fgl::MISSING_BITS : fgl::END_BITS; continue; }
+        int32_t i = 0;
+        const char* e = nullptr;
+        for (;; i++) {
+            e = (const char*)memchr(b, ',', (size_t)(fe - b)); if (!e) e = fe;
+            if (i == g || e == fe) break;
+            b = e + 1;
+        }
+        if (i < g) { plane[s] = fgl::END_BITS; continue; }
+        const std::string tok(b, e);
+        if (tok == ".") { plane[s] = fgl::MISSING_BITS; continue; }
+        char* te = nullptr;
+        const double d = strtod(tok.c_str(), &te);
+        if (tok.empty() || te != tok.c_str() + tok.size())
+            stop_run("Sample %lld at position %lld: the GL value '%s' is not a number.", (long long)s, pos, tok.c_str());
+        const float f = (float)d;
+        memcpy(&plane[s], &f, 4);
+    }
+    put_line(n, plane.data());
+}
+
+// --on-device 0: the routines the kernels run, a column at a time; the strtod reader for what they hand back
+void Run::record_host(const Note& n, std::vector<uint32_t>& plane) {
+    if (bcf) {
+        const uint8_t* v = raw.data() + n.off;
+        for (int64_t s = 0; s < N; s++) memcpy(&plane[s], v + ((size_t)s * n.len + n.g()) * 4, 4);
+        put_line(n, plane.data());
+        return;
+    }
+    fgl::Rec r; memset(&r, 0, sizeof r);
+    r.off = n.off; r.len = n.len; r.k = n.k; r.g = n.g(); r.pos = n.pos;
+    const int st = fgl::record_plain(raw.data(), r, N, plane.data(), nullptr);
+    if (st == fgl::ST_OK) { put_line(n, plane.data()); return; }
+    if (st == fgl::ST_HOST) n_host++;
+    record_strtod(n, plane);
+    if (st == fgl::ST_RANGE) stop_run("The record at position %lld was refused by the column rules and taken by the strtod reader.", (long long)n.pos);
+}
+
+// ---- the notes: the first nine columns of every record line ---------------------------------------------------------------------------
+bool header_defines_gl(const std::vector<std::string>& header, std::string* type) {
+    for (const std::string& h : header) if (h.compare(0, 10, "##FORMAT=<") == 0 && BcfIn::attr(h, "ID") == "GL") { if (type) *type = BcfIn::attr(h, "Type"); return true; }
+    return false;
+}
+
+void match_alleles(const Opt& o, const char first, const int j, Note& n) {
+    if (first == o.gt[0]) n.a0 = (int16_t)j;
+    if (first == o.gt[1]) n.a1 = (int16_t)j;
+}
+
+void Run::notes_text() {
+    const char* const t0 = (const char*)raw.data();
+    const char* p = t0; const char* const end = p + raw.size();
+    std::vector<std::pair<const char*, const char*>> lines;
+    std::vector<std::string> f;
+    while (p < end) {
+        const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
+        const char* le = nl ? nl : end;
+        if (le > p) {
+            if (le - p >= 2 && p[0] == '#' && p[1] == '#') header.emplace_back(p, le);
+            else if (p[0] == '#') { split(std::string(p, le), '\t', f); for (size_t i = 9; i < f.size(); i++) samples.push_back(f[i]); }
+            else lines.emplace_back(p, le);
+        }
+        p = nl ? nl + 1 : end;
+    }
+    N = (int64_t)samples.size();
+    const bool defined = header_defines_gl(header, nullptr);
+    char msg[256];
+    notes.reserve(lines.size());
+    for (size_t i = 0; i < lines.size(); i++) {
+        const char* lb = lines[i].first; const char* le = lines[i].second;
+        const char* col_at[10]; int nc = 0; col_at[0] = lb;
+        for (const char* q = lb; q < le && nc < 9; q++) if (*q == '\t') col_at[++nc] = q + 1;
+        Note n;
+        if (nc >= 1) n.pos = atoll(std::string(col_at[1], col_at[2 > nc ? nc : 2]).c_str());
+        if (nc < 9) { snprintf(msg, sizeof msg, "Record %zu has fewer than 10 columns (a FORMAT/GL column is required).", i + 1); stop = msg; return; }
+        // GL must be readable before anything else
+        n.k = -1;
+        { int k = 0; const char* b = col_at[8]; const char* const fe = col_at[9] - 1;
+          for (const char* q = b;; q++) if (q == fe || *q == ':') { if (q - b == 2 && b[0] == 'G' && b[1] == 'L' && n.k < 0) n.k = k; k++; if (q == fe) break; b = q + 1; } }
+        if (!defined || n.k < 0) { snprintf(msg, sizeof msg, "Could not read GL tag at position %lld. Exiting...", (long long)n.pos); stop = msg; return; }
+        const char* const ref = col_at[3]; const char* const alt = col_at[4]; const char* const alt_end = col_at[5] - 1;
+        int j = 0;
+        match_alleles(o, ref < col_at[4] - 1 ? ref[0] : '\0', j++, n);
+        if (!(alt_end - alt == 1 && alt[0] == '.'))
+            for (const char* b = alt;; ) {
+                const char* e = (const char*)memchr(b, ',', (size_t)(alt_end - b)); if (!e) e = alt_end;
+                if (j < INT16_MAX) match_alleles(o, e > b ? b[0] : '\0', j, n);
+                j++;
+                if (e == alt_end) break;
+                b = e + 1;
+            }
+        n.off = col_at[9] - t0;
+        if (le - col_at[9] > INT32_MAX) { snprintf(msg, sizeof msg, "The record at position %lld is longer than 2 GiB.", (long long)n.pos); stop = msg; return; }
+        n.len = (int32_t)(le - col_at[9]);
+        notes.push_back(n);
+    }
+}
+
+// BCF: the shared block -> POS and the alleles; the FORMAT field headers -> where GL's vectors lie
+void Run::notes_bcf() {
+    BcfDict d; BcfIn c; c.buf = raw.data(); c.size = raw.size();
+    Vcf v;
+    bcf_header(c, d, v);
+    header = v.header; samples = v.samples;
+    N = (int64_t)samples.size();
+    std::string type;
+    const bool defined = header_defines_gl(header, &type) && type == "Float";
+    std::vector<int32_t> iv; char msg[256];
+    while (c.off < c.size) {
+        BcfRecAt at; int n_fmt, ty, nv;
+        bcf_scan_record(c, at);
+        Rec r;
+        bcf_shared(c, d, at, (size_t)N, r, n_fmt);
+        Note n; n.pos = r.pos0 + 1; n.k = -1;
+        bool is_float = false;
+        for (int k = 0; k < n_fmt; k++) {
+            c.typed(ty, nv); c.ints(ty, nv, iv);
+            const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
+            if (key == d.dict.end()) c.fail("BCF: undefined FORMAT key");
+            c.typed(ty, nv);
+            const size_t w = ty == 1 ? 1 : ty == 2 ? 2 : (ty == 3 || ty == 5) ? 4 : ty == 7 ? 1 : 0;
+            if (c.off + w * nv * (size_t)N > c.size) c.fail("truncated BCF record");
+            if (key->second == "GL" && n.k < 0) { n.k = k; is_float = ty == 5 && nv >= 1; n.off = (int64_t)c.off; n.len = nv; }
+            c.off += w * nv * (size_t)N;
+        }
+        c.off = at.rec_end;
+        if (!defined || n.k < 0 || !is_float) { snprintf(msg, sizeof msg, "Could not read GL tag at position %lld. Exiting...", (long long)n.pos); stop = msg; return; }
+        for (size_t j = 0; j < r.alleles.size() && j < (size_t)INT16_MAX; j++) match_alleles(o, r.alleles[j].empty() ? '\0' : r.alleles[j][0], (int)j, n);
+        if (n.found() && n.g() >= n.len) {
+            n.halt = true; notes.push_back(n);                          // (its message comes first, as on the text path)
+            snprintf(msg, sizeof msg, "The genotype %s is value %d of FORMAT/GL at position %lld, and the record's samples carry at most %lld values (the tool reads outside its buffer there).",
+                     o.gt.c_str(), n.g(), (long long)n.pos, (long long)n.len);
+            stop = msg;
+            return;
+        }
+        notes.push_back(n);
+    }
+}
+
+// ---- --on-device 1 ---------------------------------------------------------------------------------------------------------------
+void run_device(Run& R, std::vector<uint32_t>& plane) {
+    const std::vector<Note>& notes = R.notes;
+    std::vector<size_t> sent;
+    for (size_t i = 0; i < notes.size(); i++) if (notes[i].line()) sent.push_back(i);
+    auto bytes_of = [&](const Note& n) { return R.bcf ? ((int64_t)R.N * n.len * 4) : (int64_t)n.len; };
+    // a batch: at most --batch-records records, 64 MiB of CSV bound and 64 MiB of text (one record at least)
+    const int64_t TEXT_MOST = 64ll << 20;
+    int64_t B = std::max<int64_t>(1, std::min<int64_t>(R.o.batch, TEXT_MOST / fgl_dev_line_bound((int32_t)R.N)));
+    std::vector<std::pair<size_t, size_t>> batches;                     // [j0, j1) of sent
+    int64_t max_text = 1; int64_t max_recs = 1;
+    for (size_t j = 0; j < sent.size();) {
+        size_t j1 = j; int64_t t = 0;
+        while (j1 < sent.size() && (int64_t)(j1 - j) < B && (j1 == j || t + bytes_of(notes[sent[j1]]) <= TEXT_MOST)) t += bytes_of(notes[sent[j1++]]);
+        batches.emplace_back(j, j1);
+        max_text = std::max(max_text, t); max_recs = std::max<int64_t>(max_recs, (int64_t)(j1 - j));
+        j = j1;
+    }
+    char err[256];
+    R.dev = fgl_dev_create(R.o.device, (int32_t)R.N, (int32_t)max_recs, max_text, err, sizeof err);
+    if (!R.dev) { R.notes.clear(); R.stop_run("--on-device 1: %s (device %d; --on-device 0 reads on the host)", err, R.o.device); }
+    auto submit = [&](int64_t b) {
+        const double t0 = now_s();
+        const int slot = (int)(b & 1);
+        uint8_t* text = fgl_dev_text(R.dev, slot); fgl::Rec* recs = fgl_dev_recs(R.dev, slot);
+        int64_t at = 0; int32_t n = 0;
+        for (size_t j = batches[b].first; j < batches[b].second; j++, n++) {
+            const Note& nt = notes[sent[j]];
+            fgl::Rec r; memset(&r, 0, sizeof r);
+            r.off = at; r.len = nt.len; r.k = nt.k; r.g = nt.g(); r.pos = nt.pos;
+            memcpy(text + at, R.raw.data() + nt.off, (size_t)bytes_of(nt)); at += bytes_of(nt);
+            recs[n] = r;
+        }
+        if (fgl_dev_submit(R.dev, slot, n, at, R.bcf ? 1 : 0) != 0) R.stop_run("--on-device 1: %s", fgl_dev_error(R.dev));
+        R.up += at + (int64_t)n * (int64_t)sizeof(fgl::Rec); R.t_dev += now_s() - t0;
+    };
+    size_t cur = 0;                                                    // the next record in file order
+    auto retire = [&](int64_t b) {
+        double t0 = now_s();
+        FglBatchOut out;
+        if (fgl_dev_wait(R.dev, (int)(b & 1), &out) != 0) R.stop_run("--on-device 1: %s", fgl_dev_error(R.dev));
+        R.t_dev += now_s() - t0; t0 = now_s();
+        int32_t n = 0;
+        for (size_t j = batches[b].first; j < batches[b].second; j++, n++) {
+            for (; cur < sent[j]; cur++) R.message(notes[cur]);
+            const Note& nt = notes[cur++];
+            R.message(nt);
+            if (out.status[n] == fgl::ST_OK) { R.csv_buf.append((const char*)out.csv + out.off[n], (size_t)(out.off[n + 1] - out.off[n])); R.n_lines++; }
+            else {
+                if (out.status[n] == fgl::ST_HOST) R.n_host++;
+                R.record_strtod(nt, plane);
+                if (out.status[n] == fgl::ST_RANGE) R.stop_run("The record at position %lld was refused by the column rules and taken by the strtod reader.", (long long)nt.pos);
+            }
+            R.flush(false);
+        }
+        R.down += out.off[n] + (int64_t)n * 12 + 8;
+        R.t_host += now_s() - t0;
+    };
+    two_in_flight((int64_t)batches.size(), submit, retire);
+    for (; cur < notes.size(); cur++) R.message(notes[cur]);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    Run R;
+    R.o = parse_opt(argc, argv);
+    const Opt& o = R.o;
+    double t0 = now_s();
+    {
+        gzFile fp = gzopen(o.in.c_str(), "r");                         // plain text, gzip / BGZF, or BCF inside either
+        if (!fp) die("Could not open file: %s", o.in.c_str());
+        gzbuffer(fp, 1 << 20);
+        std::vector<uint8_t> chunk(1 << 22);
+        int k;
+        while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) R.raw.insert(R.raw.end(), chunk.begin(), chunk.begin() + k);
+        gzclose(fp);
+    }
+    R.out_fp = o.out.empty() ? stdout : fopen(o.out.c_str(), "w");
+    if (!R.out_fp) die("Could not open output file %s for writing", o.out.c_str());
+    R.t_read = now_s() - t0; t0 = now_s();
+    R.bcf = R.raw.size() >= 3 && !memcmp(R.raw.data(), "BCF", 3);
+    if (R.bcf) R.notes_bcf(); else R.notes_text();
+    if (R.N <= 0) die("The file %s names no sample.", o.in.c_str());
+    if (R.N > (int64_t)(INT32_MAX / fgl::VALUE_BOUND)) die("Too many samples.");
+    R.t_nine = now_s() - t0;
+
+    std::vector<uint32_t> plane((size_t)R.N);
+    if (o.on_device) run_device(R, plane);
+    else {
+        t0 = now_s();
+        for (const Note& n : R.notes) { R.message(n); if (n.line()) R.record_host(n, plane); R.flush(false); }
+        R.t_host = now_s() - t0;
+    }
+    if (!R.stop.empty()) R.stop_run("%s", R.stop.c_str());
+    R.flush(true);
+    if (o.verbose)
+        fprintf(stderr, "[fetchgl] on-device %d: records %zu, with a CSV line %ld, redone on the host %ld, bytes sent up %lld, received %lld; read %.3f s, nine columns %.3f s, device %.3f s, host %.3f s\n",
+                o.on_device, R.notes.size(), R.n_lines, R.n_host, (long long)R.up, (long long)R.down, R.t_read, R.t_nine, R.t_dev, R.t_host);
+    if (R.dev) fgl_dev_destroy(R.dev);
+    if (R.out_fp != stdout) fclose(R.out_fp);
+    fflush(stdout);
+    return 0;
+}

@@ -2,7 +2,7 @@
 // A batch is the text of the sample columns of up to max_recs matched truth / call lines and one gtd::Rec per record; the per-sample
 // rules are gtdisc_core.h.
 //   k_gtd_parse       one workgroup of 256 lanes per record, the truth region and then the call region.  A region is walked in chunks of
-//                     256 x 16 bytes on 16-byte address boundaries as k_vcfin_parse walks a line: a lane whose 16 bytes lie inside the
+//                     256 x 16 bytes on 16-byte address boundaries as k_vcfin_parse walks a line (column_walk.hip.h, shared with fetchgl.hip): a lane whose 16 bytes lie inside the
 //                     region loads them at once, the lanes at the two ends read their bytes one by one -- no byte outside the region is
 //                     read.  A scan of the tab counts numbers the columns; the lane that owns the tab before column s parses that column
 //                     (gtd::sample_true / gtd::sample_call, bounded by the region's end) and stores one byte per plane: true bases,
@@ -24,12 +24,13 @@
 
 #include "../../../include/vcfgl_hip.h"
 #include "gtdisc_dev.h"
+#include "column_walk.hip.h"
 
 namespace {
 
-constexpr int NT = 256;                  // lanes per workgroup of the parser and the listing kernels
-constexpr int LB = 16;                   // bytes per lane and chunk
-constexpr int CHUNK = NT * LB;
+using colwalk::NT;                       // lanes per workgroup of the parser and the listing kernels (column_walk.hip.h)
+using colwalk::LB;                       // bytes per lane and chunk
+using colwalk::scan_columns;
 constexpr int TNT = 1024;                // lanes per workgroup of the tally
 constexpr int SG = 64;                   // samples per tally workgroup
 constexpr int NCELL = gtd::N_CELLS, NGQ = gtd::N_GQ;
@@ -43,49 +44,6 @@ struct ParseArgs {
     const gtd::Rec* recs; int32_t n_recs, N;
     uint8_t* tb; uint8_t* cb; uint8_t* gq; int32_t* status;
 };
-
-// the columns of the region [lb, le): f(col, q) for every column that starts at q; returns the number of columns.  One __syncthreads
-// per chunk on s_tot[parity]; every lane of the workgroup takes part.
-template <typename F>
-__device__ __forceinline__ int32_t scan_columns(const uint8_t* __restrict__ text, const int64_t lb, const int64_t le, int32_t (*s_tot)[NT / 64], F f) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int64_t mis = (int64_t)((uintptr_t)(text + lb) & (LB - 1));
-    const int64_t o0 = lb - mis;                                       // the 16-byte boundary at or below the region's first byte
-    const int64_t n_chunks = (le - o0 + CHUNK - 1) / CHUNK;
-    int32_t base = 0;
-    if (t == 0) f(0, lb);                                              // column 0 starts at the region's first byte
-    for (int64_t c = 0; c < n_chunks; c++) {
-        const int64_t o = o0 + c * CHUNK + (int64_t)t * LB;            // this lane's 16 bytes: [o, o + 16)
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (o >= lb && o + LB <= le) {
-            const uint4 v = *reinterpret_cast<const uint4*>(text + o);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        } else if (o + LB > lb && o < le) {
-#pragma unroll
-            for (int i = 0; i < LB; i++) { const int64_t at = o + i; if (at >= lb && at < le) w[i >> 2] |= (uint32_t)text[at] << (8 * (i & 3)); }
-        }
-        uint32_t mask = 0;                                             // bit i: byte i is a tab (a byte outside the region is 0 here)
-#pragma unroll
-        for (int i = 0; i < LB; i++) mask |= (((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) == (uint32_t)'\t' ? 1u : 0u) << i;
-        const int cnt = __popc(mask);
-        int inc = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(inc, d, 64); if (lane >= d) inc += y; }
-        if (lane == 63) s_tot[c & 1][wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < NT / 64; k++) { const int x = s_tot[c & 1][k]; if (k < wave) before += x; total += x; }
-        int32_t col = base + before + inc - cnt + 1;                   // the column after this lane's first tab
-        base += total;
-        while (mask) {
-            const int i = __ffs(mask) - 1; mask &= mask - 1;
-            f(col, o + i + 1);
-            col++;
-        }
-    }
-    return base + 1;
-}
 
 __global__ void __launch_bounds__(NT) k_gtd_parse(const ParseArgs A) {
     __shared__ int32_t s_tot[2][NT / 64];

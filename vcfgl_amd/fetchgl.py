@@ -2,8 +2,13 @@
 genotype's FORMAT/GL as CSV text"): what the reference's misc/fetchGl prints for a record, from a tile's arrays.
 
 `format_into` runs the kernels on device tensors; `lines` puts "POS," in front of every site that has a line.
+
+`fetch_file` is the other way in: a record file on disk (VCF text, gzip / bgzip'd, or BCF) through the program fetchgl_hip
+(vcfgl_amd/csrc/misc), which takes any two characters for the genotype, as the tool does.
 """
 import ctypes as C
+import os
+import subprocess
 
 from . import _abi
 
@@ -56,3 +61,25 @@ def lines(pos, text, offsets):
         if e > b:
             out.append(b"%d," % int(pos[i]) + raw[b:e])
     return b"".join(out)
+
+
+FETCHGL_PROGRAM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "fetchgl_hip")
+
+
+def fetch_file(path, gt, out=None, on_device=True, device=None, batch_records=None, messages=True, verbose=False, timeout=None, env=None):
+    """Runs fetchgl_hip -i `path` -gt `gt` [-o `out`] as a fresh child process and returns (returncode, stdout, stderr) as text;
+    the CSV is in stdout, or in `out` when that is given.  on_device=False reads on the host and touches no GPU; on_device=True
+    without a GPU fails (returncode 1): there is no fallback.  A missing program is an error (build the package first)."""
+    if not os.path.exists(FETCHGL_PROGRAM):
+        raise FileNotFoundError("%s is not built (make -C vcfgl_amd/csrc all)" % FETCHGL_PROGRAM)
+    cmd = [FETCHGL_PROGRAM, "-i", str(path), "-gt", str(gt), "--on-device", "1" if on_device else "0", "--messages", "1" if messages else "0"]
+    if out is not None:
+        cmd += ["-o", str(out)]
+    if device is not None:
+        cmd += ["--device", str(int(device))]
+    if batch_records is not None:
+        cmd += ["--batch-records", str(int(batch_records))]
+    if verbose:
+        cmd += ["--verbose", "1"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
+    return r.returncode, r.stdout, r.stderr
