@@ -6,6 +6,8 @@ target entries of the ABI, `apply_into` runs the kernels on device tensors.  `Si
 simulator.
 """
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 
@@ -93,3 +95,28 @@ def apply_into(targets, site_status, n_alleles, alleles2acgt, n_samples, qs=None
     if rc != _abi.VGL_OK:
         raise RuntimeError("vgl_setal_apply_device: %d: %s" % (rc, lib.vgl_last_error().decode()))
     return bad_site, workspace
+
+
+SETALLELES_PROGRAM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "setalleles_hip")
+
+
+def set_file(path, alleles, out_prefix, mode="v", on_device=True, device=None, batch_records=None, threads=None, verbose=False, timeout=3600,
+             env=None):
+    """Runs setalleles_hip -i `path` -a `alleles` -O `mode` -o `out_prefix` as a fresh child process under `timeout` seconds
+    (subprocess.TimeoutExpired when it runs out) and returns (returncode, stdout, stderr) as text.  The records are in `out_prefix`.vcf
+    (mode v) or .vcf.gz (mode z) for VCF text input, in `out_prefix`.bcf (modes u, b) for BCF input.  on_device=True works BCF input on
+    the GPU, fails without one and is refused for text input (returncode 1): there is no fallback; on_device=False works on the host
+    and touches no GPU.  A missing program is an error (build the package first)."""
+    if not os.path.exists(SETALLELES_PROGRAM):
+        raise FileNotFoundError("%s is not built (make -C vcfgl_amd/csrc all)" % SETALLELES_PROGRAM)
+    cmd = [SETALLELES_PROGRAM, "-i", str(path), "-a", str(alleles), "-O", str(mode), "-o", str(out_prefix), "--on-device", "1" if on_device else "0"]
+    if device is not None:
+        cmd += ["--device", str(int(device))]
+    if batch_records is not None:
+        cmd += ["--batch-records", str(int(batch_records))]
+    if threads is not None:
+        cmd += ["--threads", str(int(threads))]
+    if verbose:
+        cmd += ["--verbose", "1"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
+    return r.returncode, r.stdout, r.stderr
