@@ -16,11 +16,10 @@ import numpy as np
 import pytest
 
 import gl_tail_model as M
-from vcfgl_amd import Simulator, VcfglArgs, _abi
+from gl_cases import TILE_CASES, case_ids, simulate_case              # (the case table: shared with test_gpu_gl_body.py)
+from vcfgl_amd import _abi
 
 pytestmark = pytest.mark.gpu
-
-SITES = {1: 33, 5: 29, 63: 17, 65: 9, 130: 7}
 
 
 # ------------------------------------------------------------------------------------------------ dumps
@@ -164,65 +163,7 @@ def test_log10_unit_against_mpmath():
 
 
 # ------------------------------------------------------------------------------------------------ tiles
-BETA = dict(error_qs=2, beta_variance=1e-5)
-# name: (flags, which build: (fused, gl_wpb, hooks env), layouts, sample counts, fields beyond the standard ones, what must occur)
-#   occur: "alleles" -> the n_alleles values that must all be seen at N >= 63 (N = 1: a single sample shows at most two alleles);
-#          "inf" -inf next to 0; "cap" a PL of 255; "sub" a GL in (-45.15, -37.93): 10^GL a float32 subnormal; "skip" a skipped site
-PATHS = {
-    # k_gl<4, 2, false>: -doUnobserved 0, one to four alleles per site (NG 1, 3, 6, 10); -addQS keeps N = 130 off the fused build
-    "k_gl-A4": (dict(seed=21, depth=6.0, error_rate=0.001, do_unobserved=0, add_qs=1), (0, 8, None), (0, 1), (1, 63, 65, 130), dict(alleles={1, 2, 3, 4}, cap=1)),
-    # k_gl<5, 2, false>: -doUnobserved 1, two to five alleles (NG 3, 6, 10, 15)
-    "k_gl-A5": (dict(seed=22, depth=6.0, error_rate=0.001, do_unobserved=1, add_qs=1), (0, 8, None), (0, 1), (1, 63, 65, 130), dict(alleles={2, 3, 4, 5}, cap=1)),
-    # k_gl<5, 1, false>: GL model 1 (errmod)
-    "k_gl-model1": (dict(seed=23, depth=8.0, error_rate=0.01, gl_model=1, add_qs=1), (0, 4, None), (0, 1), (1, 63, 65, 130), dict()),
-    # k_gl<5, 2, true>: --precise-gl 1 with per-read error probabilities
-    "precise": (dict(seed=24, depth=7.0, error_rate=0.01, precise_gl=1, **BETA), (0, 8, None), (0, 1), (1, 63, 65, 130), dict(cap=1)),
-    # --precise-gl 1 at --error-rate 0: a mismatching read's term is log10(0) = -inf, which stands next to the 0 of the matching genotype
-    "precise-error-rate-0": (dict(seed=25, depth=4.0, error_rate=0.0, precise_gl=1, add_qs=1), (0, 8, None), (0, 1), (1, 63, 65, 130), dict(inf=1, cap=1)),
-    # --error-rate 0.9: score 0, whose homT term is -inf in the table of k_gl<., 2, false>
-    "k_gl-score-0": (dict(seed=26, depth=4.0, error_rate=0.9, add_qs=1), (0, 8, None), (0, 1), (65, 130), dict(inf=1, cap=1)),
-    # depth 40 at --error-rate 0.001 (score 30, 3.0 per mismatching read): GL passes -37.9 ... -45.2 and goes on beyond -100; PL caps
-    # (the planes context is eligible for k_gl2, gl_wpb 16, but a tile with GP stays with k_gl: vgl_launch_gl)
-    "k_gl-depth40-score-30": (dict(seed=27, depth=40.0, error_rate=0.001, add_qs=1), (0, {0: 16, 1: 8}, None), (0, 1), (63, 130), dict(sub=1, cap=1)),
-    # --rm-empty-sites 1 at depth 0.3: skipped sites at N = 1 and 5, readless samples everywhere
-    "rm-empty-sites": (dict(seed=28, depth=0.3, error_rate=0.01, rm_empty_sites=1), (0, 4, None), (0, 1), (1, 5, 63), dict(skip=1)),
-    # k_gl2<5> with every tag (hooks build, VGL_GL2X=2; planes layout only) at depth 20, score 20: 2.0 per mismatching read, GL passes
-    # the subnormal range of 10^x in a tenth of the values
-    "k_gl2": (dict(seed=29, depth=20.0, error_rate=0.01), (0, 16, {"VGL_GL2X": "2"}), (0,), (1, 63, 65, 130), dict(sub=1, cap=1)),
-    # ... with the pool's limit at 1: every workgroup with a three-base evaluation is written again by k_gl_redo (k_gl's body)
-    "k_gl_redo": (dict(seed=31, depth=20.0, error_rate=0.05), (0, 16, {"VGL_GL2X": "2", "VGL_DEBUG_GL2_OVC": "1"}), (0,), (1, 63, 65, 130), dict(sub=1, cap=1)),
-    # the shipped library's own choice of k_gl2: a tile without GP (its epilogue there carries PL and pl_u8 only)
-    "k_gl2-shipped": (dict(seed=32, depth=20.0, error_rate=0.01), (0, 16, None), (0,), (65, 130), dict(cap=1, no_gp=1)),
-    # the fused build (N > 128, mean depth below 12, one fixed score): the plain build writes no GP -- PL and pl_u8 are checked there --,
-    # the general build (GP asked for, or sample-major records) does
-    "fused-plain": (dict(seed=33, depth=5.0, error_rate=0.01), (1, 8, None), (0,), (130,), dict(no_gp=1)),
-    "fused-general": (dict(seed=34, depth=5.0, error_rate=0.01), (1, 8, None), (0, 1), (130,), dict(cap=1)),
-}
-TILE_CASES = [(name, sm, N) for name, v in PATHS.items() for sm in v[2] for N in v[3]]
-
-
-def simulate_case(name, sm, N, monkeypatch):
-    kw, (fused, wpb, env), _, _, occur = PATHS[name]
-    args = VcfglArgs(add_pl=1, add_gp=0 if occur.get("no_gp") else 1, **kw)
-    args.rng_mode, args.beta_sampler = _abi.VGL_RNG_TILE, _abi.VGL_BETA_RAND48
-    if sm:
-        args.out_layout = _abi.VGL_LAYOUT_SAMPLE_MAJOR
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    S = SITES[N]
-    sim = Simulator(args, N, device=0, max_sites_per_tile=S, hooks=env is not None)
-    info = sim.info()
-    if isinstance(wpb, dict):
-        wpb = wpb[sm]
-    want_wpb = 4 if (args.gl_model == 1 or kw["depth"] < 1.0) else wpb      # (no lane sort below a mean depth of 1: four wavefronts)
-    assert (info["fused"], info["gl_wpb"], info["test_hooks"]) == (fused, want_wpb, 1 if env is not None else 0), (name, info)
-    fields = ["fmt_dp", "gl", "pl", "pl_u8"] + ([] if occur.get("no_gp") else ["gp"])
-    t = sim.simulate(3, M.mixed_sites(S, N, seed=1000 + N), fields=fields)
-    sim.close()
-    return t, occur
-
-
-@pytest.mark.parametrize("name,sm,N", TILE_CASES, ids=[f"{n}-{'sm' if s else 'planes'}-N{N}" for n, s, N in TILE_CASES])
+@pytest.mark.parametrize("name,sm,N", TILE_CASES, ids=case_ids(TILE_CASES))
 def test_tile_tags_are_exact_functions_of_the_gl_written(name, sm, N, monkeypatch):
     """every PL and pl_u8 equals the exact rounding of -10 GL, every GP lies within 18 x 2^-24 exact + 2^-149 of the exact
     10^gl_i / sum 10^gl_j (mpmath for the -inf / subnormal evaluations, a stride of the rest and whatever float64 cannot settle), GL

@@ -1,7 +1,7 @@
 """GL model 1 beyond the depth the reference's golden files reach (n <= 3): the oracle's restatement of htslib's errmod
 (oracle/vgl_oracle.c errmod_make / errmod_cal5) against an INDEPENDENT evaluation of the published model ("revised MAQ",
-Li 2011) written here from its definition in exact rational arithmetic -- not from errmod.c's
-recurrences:
+Li 2011) written from its definition in exact rational arithmetic -- not from errmod.c's
+recurrences (tests/gl_body_model.py: gl1_costs, which test_gpu_gl_body.py applies to the kernels as well):
 
     beta(q, n, k) = -10 log10( P(X >= k+1) / P(X >= k) ),   X ~ Binomial(n, e),  e = 10^(-q/10)
     fk(w)         = (1 - depcorr)^w (1 - eta) + eta,  eta = 0.03
@@ -13,51 +13,11 @@ recurrences:
 This pins the MODEL at depth up to 255; what stays unpinned is htslib's own floating-point evaluation order (its source is
 not in the reference tree), which can move the float32 results in their last bits only."""
 import ctypes as C
-import math
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
-
-def binom_tail_ratios(n, e):
-    """[P(X >= k+1) / P(X >= k) for k = 0..n-1] exactly, X ~ Binomial(n, e), e a Fraction"""
-    pmf = [Fraction(math.comb(n, j)) * e ** j * (1 - e) ** (n - j) for j in range(n + 1)]
-    tail = [Fraction(0)] * (n + 2)
-    for j in range(n, -1, -1):
-        tail[j] = tail[j + 1] + pmf[j]
-    return [tail[k + 1] / tail[k] for k in range(n)]
-
-
-def model_errmod(depcorr, codes):
-    """codes: qual << 5 | base (strand 0).  Returns the 5x5 matrix of phred-scaled costs (float64)."""
-    n_all = len(codes)
-    assert n_all <= 255
-    eta = 0.03
-    fk = lambda w: (1.0 - depcorr) ** w * (1.0 - eta) + eta
-    order = sorted(codes, reverse=True)
-    c, w, bsum = [0] * 5, [0] * 5, [0.0] * 5
-    cache = {}
-    for code in order:
-        q = min(max(code >> 5, 4), 63)
-        b = code & 0xF
-        if q not in cache:
-            e = Fraction(10.0 ** (-q / 10.0))
-            cache[q] = [-10.0 * math.log10(float(r)) for r in binom_tail_ratios(n_all, e)]
-        bsum[b] += fk(w[b]) * cache[q][c[b]]
-        c[b] += 1; w[b] += 1
-    out = np.zeros((5, 5))
-    for j in range(5):
-        others = [k for k in range(5) if k != j]
-        out[j, j] = sum(bsum[k] for k in others) if sum(c[k] for k in others) else 0.0
-        for k in range(j + 1, 5):
-            rest = [i for i in range(5) if i not in (j, k)]
-            cjk = c[j] + c[k]
-            lhet = math.log(math.comb(cjk, c[k])) - cjk * math.log(2.0)
-            v = -4.343 * lhet + (sum(bsum[i] for i in rest) if sum(c[i] for i in rest) else 0.0)
-            out[j, k] = out[k, j] = max(v, 0.0)
-        out[j, j] = max(out[j, j], 0.0)
-    return out
+from gl_body_model import gl1_costs as model_errmod                # (the model: tests/gl_body_model.py, shared with test_gpu_gl_body.py)
 
 
 def oracle_errmod(oracle, depcorr, codes):
