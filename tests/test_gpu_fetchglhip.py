@@ -173,3 +173,15 @@ def test_tie_to_the_simulators_fetch_gl(gt, extra, tmp_path):
         rh, rd = _same(tmp_path, o + ext, gt)
         assert rd[0] == 0 and rd[1] == csv, rd[2][-2000:]
         assert csv.count("\n") > 0 or gt != "AC"
+
+
+@pytest.mark.parametrize("n_records", [1023, 1024, 1025, 2049, 4097])
+def test_scan_chunk_boundaries(n_records, tmp_path):
+    """the offsets scan takes 1024 records a chunk: the default --batch-records gives one batch of up to 4096 records -- 1, 2, 3 and 4
+    chunks, the carry from chunk to chunk and both parities of its LDS rows -- and, of 4097 records, a batch of one behind it"""
+    for n, container in ((1, "vcf"), (2, "bcf")):
+        recs = gm.make_records(n, n_records, seed=5000 + n_records + n, first_pos=8, fixed_alleles=True)
+        path = gm.write_file(str(tmp_path / ("in." + container)), recs, n, container)
+        rh, rd = _same(tmp_path, path, gm.GENOTYPES[(n_records + n) % 15])
+        assert rh[0] == 0, rh[2][-2000:]
+        assert _counts(rd[2])[:3] == (n_records, n_records, 0)

@@ -193,3 +193,17 @@ def test_tie_to_the_tally_of_the_simulator(tmp_path):
     rh, rd = _same(tmp_path, o + ".truth.vcf", call, do_gq=8)
     assert rd[0] == 0, rd[2][-2000:]
     assert open(str(tmp_path / "dev.tsv")).read() == open(o + ".discordance.tsv").read()
+
+
+@pytest.mark.parametrize("n_records", [1023, 1024, 1025, 2049, 4097])
+def test_scan_chunk_boundaries(n_records, tmp_path):
+    """the offsets scan takes 1024 records a chunk: the default --batch-records gives one batch of up to 4096 records -- 1, 2, 3 and 4
+    chunks, the carry from chunk to chunk and both parities of its LDS rows -- and, of 4097 records, a batch of one behind it.
+    -doGQ 2 with -perSite 1: both rows of the scan carry lengths; -doGQ 0 with -perSite 1: the listing's row is all zeros"""
+    truth, call = str(tmp_path / "truth.vcf"), str(tmp_path / "call.vcf")
+    for n, mode in ((1, 2), (2, 0)):
+        gm.write_pair(truth, call, n, n_records, "GT:GQ", seed=3000 + n_records + n, invariant=False)
+        rh, rd = _same(tmp_path, truth, call, do_gq=mode, per_site=True)
+        assert rh[0] == 0, rh[2][-2000:]
+        assert _redone(rd[2])[:2] == (n_records, 0)
+        assert len(rd[1]) > 0 and len(open(str(tmp_path / "dev.tsv")).read()) > 0      # -perSite lines; the listing or the table

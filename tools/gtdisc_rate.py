@@ -78,9 +78,9 @@ assert r.returncode == 0, r.stderr[-800:]
 stats = glob.glob(os.path.join(prof, "**", "*kernel_stats.csv"), recursive=True)
 assert stats, "rocprofv3 wrote no kernel statistics"
 for row in csv.DictReader(open(stats[0])):
-    if "k_gtd_" not in row["Name"]:
+    if "k_gtd_" not in row["Name"] and "k_offsets_scan" not in row["Name"]:
         continue
-    name = re.search(r"k_gtd_\w+", row["Name"]).group(0)
+    name = re.search(r"k_gtd_\w+|k_offsets_scan", row["Name"]).group(0)
     line = f"  {name:18s} {int(row['Calls']):5d} batches  average {float(row['AverageNs']) / 1e3:9.1f} us  min {int(row['MinNs']) / 1e3:9.1f}  max {int(row['MaxNs']) / 1e3:9.1f}  total {int(row['TotalDurationNs']) / 1e6:8.3f} ms"
     if name == "k_gtd_parse":
         line += f"  {up / int(row['TotalDurationNs']):.1f} GB/s of text"

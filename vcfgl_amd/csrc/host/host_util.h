@@ -47,6 +47,19 @@ template <typename Submit, typename Retire> static void two_in_flight(int64_t n_
     if (n_batches > 0) retire(n_batches - 1);
 }
 
+// a file's bytes through zlib: plain text, gzip / BGZF, or BCF inside either
+static std::vector<uint8_t> read_whole(const std::string& fn) {
+    std::vector<uint8_t> raw;
+    gzFile fp = gzopen(fn.c_str(), "r");
+    if (!fp) die("Could not open file: %s", fn.c_str());
+    gzbuffer(fp, 1 << 20);
+    std::vector<uint8_t> chunk(1 << 22);
+    int k;
+    while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) raw.insert(raw.end(), chunk.begin(), chunk.begin() + k);
+    gzclose(fp);
+    return raw;
+}
+
 static void split(const std::string& s, char c, std::vector<std::string>& out) {
     out.clear(); size_t b = 0;
     while (true) { size_t e = s.find(c, b); if (e == std::string::npos) { out.push_back(s.substr(b)); break; } out.push_back(s.substr(b, e - b)); b = e + 1; }

@@ -574,15 +574,7 @@ static bool inflate_on_device(const std::string& fn, const InputOpt& opt, std::v
 static Vcf read_vcf(const std::string& fn, bool keep_gt_text, int threads, const InputOpt& opt = InputOpt(), InputStats* stats = nullptr) {
     InputStats st; double t0 = now_s();
     std::vector<uint8_t> raw;
-    if (!opt.device_inflate || !inflate_on_device(fn, opt, raw, st)) {
-        gzFile fp = gzopen(fn.c_str(), "r");               // plain text, gzip / BGZF, or BCF inside either
-        if (!fp) die("Could not open file: %s", fn.c_str());
-        gzbuffer(fp, 1 << 20);
-        std::vector<uint8_t> chunk(1 << 22);
-        int k;
-        while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) raw.insert(raw.end(), chunk.begin(), chunk.begin() + k);
-        gzclose(fp);
-    }
+    if (!opt.device_inflate || !inflate_on_device(fn, opt, raw, st)) raw = read_whole(fn);
     if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) {
         if (opt.device_input) die("--device-input 1 is not supported with BCF input (its genotypes are binary already: there is no text to parse).");
         st.t_read = now_s() - t0;

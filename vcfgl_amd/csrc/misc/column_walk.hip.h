@@ -1,10 +1,12 @@
 // column_walk.hip.h -- the walk over the tab-separated columns of a text region that k_gtd_parse (gtdisc.hip) and k_fgl_parse
 // (fetchgl.hip) share: a workgroup of NT lanes reads the region in chunks of NT x LB bytes on LB-byte address boundaries -- a lane
 // whose LB bytes lie inside the region loads them at once, the lanes at the two ends read their bytes one by one, so no byte outside
-// the region is read -- and a scan of the tab counts numbers the columns.
+// the region is read -- and a scan of the tab counts (wg_scan.hip.h) numbers the columns.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "wg_scan.hip.h"
 
 namespace colwalk {
 
@@ -16,7 +18,7 @@ constexpr int CHUNK = NT * LB;
 // per chunk on s_tot[parity]; every lane of the workgroup takes part.
 template <typename F>
 __device__ __forceinline__ int32_t scan_columns(const uint8_t* __restrict__ text, const int64_t lb, const int64_t le, int32_t (*s_tot)[NT / 64], F f) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int64_t mis = (int64_t)((uintptr_t)(text + lb) & (LB - 1));
     const int64_t o0 = lb - mis;                                       // the 16-byte boundary at or below the region's first byte
     const int64_t n_chunks = (le - o0 + CHUNK - 1) / CHUNK;
@@ -36,16 +38,9 @@ __device__ __forceinline__ int32_t scan_columns(const uint8_t* __restrict__ text
 #pragma unroll
         for (int i = 0; i < LB; i++) mask |= (((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) == (uint32_t)'\t' ? 1u : 0u) << i;
         const int cnt = __popc(mask);
-        int inc = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(inc, d, 64); if (lane >= d) inc += y; }
-        if (lane == 63) s_tot[c & 1][wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < NT / 64; k++) { const int x = s_tot[c & 1][k]; if (k < wave) before += x; total += x; }
-        int32_t col = base + before + inc - cnt + 1;                   // the column after this lane's first tab
-        base += total;
+        const wgscan::Sums<int> s = wgscan::step<NT>(cnt, s_tot, c & 1);
+        int32_t col = base + s.before + s.inc - cnt + 1;               // the column after this lane's first tab
+        base += s.total;
         while (mask) {
             const int i = __ffs(mask) - 1; mask &= mask - 1;
             f(col, o + i + 1);

@@ -10,7 +10,7 @@
 //                 OK, HOST (a picked token outside the device grammar) or RANGE (g >= n_gls, or a column count other than N).  No atomics.
 //   k_fgl_pick    BCF: a workgroup per record, a lane per sample: value g of the sample's vector into the same plane
 //   k_fgl_plan    a workgroup per record: the byte count of its line, "POS," included (0 for a record that is not OK)
-//   k_fgl_scan    one workgroup: the exclusive prefix sums of the counts over the batch's records
+//   k_offsets_scan (wg_scan.hip.h) one workgroup: the exclusive prefix sums of the counts over the batch's records
 //   k_fgl_write   a workgroup per record, a lane per value: the values' lengths are scanned across the workgroup, chunk by chunk, and
 //                 every lane formats its value at its offset, never past the text's capacity
 // The plane never leaves the device: the status, the offsets and the CSV text come back.
@@ -22,13 +22,13 @@
 #include "../../../include/vcfgl_hip.h"
 #include "fgl_dev.h"
 #include "column_walk.hip.h"
+#include "batch_dev.hip.h"
 
 namespace {
 
 using colwalk::NT;                       // lanes per workgroup of the parser, the planner and the writer (column_walk.hip.h)
 using colwalk::LB;                       // bytes per lane and chunk
 using colwalk::scan_columns;
-constexpr int SNT = 1024;                // lanes of the scan
 
 struct ParseArgs {
     const uint8_t* text; int64_t text_bytes;
@@ -118,32 +118,9 @@ __global__ void __launch_bounds__(NT) k_fgl_plan(const LineArgs A) {
     }
 }
 
-// off[0 .. n_recs] = exclusive prefix sums of len[0 .. n_recs)
-__global__ void __launch_bounds__(SNT) k_fgl_scan(const LineArgs A) {
-    __shared__ long long s_tot[2][SNT / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    long long base = 0;
-    const int n_chunks = (A.n_recs + SNT - 1) / SNT;
-    for (int c = 0; c < n_chunks; c++) {
-        const int i = c * SNT + t;
-        const long long v = i < A.n_recs ? (long long)A.len[i] : 0;
-        long long inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const long long y = __shfl_up(inc, d, 64); if (lane >= d) inc += y; }
-        if (lane == 63) s_tot[c & 1][wave] = inc;
-        __syncthreads();
-        long long before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < SNT / 64; k++) { const long long x = s_tot[c & 1][k]; if (k < wave) before += x; total += x; }
-        if (i < A.n_recs) A.off[i] = (int64_t)(base + before + inc - v);
-        base += total;
-    }
-    if (t == 0) A.off[A.n_recs] = (int64_t)base;
-}
-
 __global__ void __launch_bounds__(NT) k_fgl_write(const LineArgs A) {
     __shared__ uint32_t s_tot[2][NT / 64];
-    const int rec = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int rec = blockIdx.x, t = threadIdx.x;
     if (rec >= A.n_recs || A.status[rec] != fgl::ST_OK) return;        // (uniform over the workgroup)
     const uint32_t* __restrict__ row = A.plane + (size_t)rec * (size_t)A.N;
     const int64_t pos = A.recs[rec].pos;
@@ -159,149 +136,98 @@ __global__ void __launch_bounds__(NT) k_fgl_write(const LineArgs A) {
         const int32_t s = c * NT + t;
         uint32_t bits = 0, l = 0;
         if (s < A.N) { bits = row[s]; l = fgl::value_len(bits); }
-        uint32_t inc = l;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(inc, d, 64); if (lane >= d) inc += y; }
-        if (lane == 63) s_tot[c & 1][wave] = inc;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < NT / 64; k++) { const uint32_t x = s_tot[c & 1][k]; if (k < wave) before += x; total += x; }
+        const wgscan::Sums<uint32_t> sc = wgscan::step<NT>(l, s_tot, c & 1);
         if (l) {
-            const int64_t at = at0 + before + inc - l;
+            const int64_t at = at0 + sc.before + sc.inc - l;
             if (at >= 0 && at < A.cap) {
                 const int64_t room = A.cap - at;
                 vgl_fetchgl::Emit<true> e{A.csv + at, 0u, (uint32_t)(room < fgl::VALUE_BOUND ? room : fgl::VALUE_BOUND)};
                 fgl::put_value(e, bits, s == A.N - 1);
             }
         }
-        at0 += total;
+        at0 += sc.total;
     }
 }
 
 }  // namespace
 
-// ---- the handle --------------------------------------------------------------------------------------------------------------
-struct FglSlot {
-    uint8_t* h_text = nullptr; fgl::Rec* h_recs = nullptr;              // page-locked staging (vgl_host_alloc_on)
-    int32_t* h_status = nullptr; int64_t* h_off = nullptr; uint8_t* h_csv = nullptr;
-    uint8_t* d_text = nullptr; fgl::Rec* d_recs = nullptr;
-    uint32_t* d_plane = nullptr; int32_t* d_status = nullptr; int64_t* d_len = nullptr; int64_t* d_off = nullptr; uint8_t* d_csv = nullptr;
-    hipEvent_t done = nullptr;
-    int32_t n_recs = 0; bool busy = false;
+// ---- the handle (batch_dev.hip.h) ------------------------------------------------------------------------------------------------
+struct FglDev : batchdev::BatchDev {
+    int32_t N = 0, max_recs = 0; int64_t max_text = 0, cap = 0;
+    struct Slot {
+        batchdev::PinMem<uint8_t> h_text; batchdev::PinMem<fgl::Rec> h_recs;
+        batchdev::PinMem<int32_t> h_status; batchdev::PinMem<int64_t> h_off; batchdev::PinMem<uint8_t> h_csv;
+        batchdev::DevMem<uint8_t> d_text; batchdev::DevMem<fgl::Rec> d_recs;
+        batchdev::DevMem<uint32_t> d_plane; batchdev::DevMem<int32_t> d_status; batchdev::DevMem<int64_t> d_len, d_off; batchdev::DevMem<uint8_t> d_csv;
+    } slot[2];
 };
-struct FglDev {
-    int device = 0; int32_t N = 0, max_recs = 0; int64_t max_text = 0, cap = 0;
-    hipStream_t stream = nullptr;
-    FglSlot slot[2];
-    char err[256] = {0};
-};
-
-static int fgl_fail(FglDev* d, const char* what, hipError_t e) {
-    snprintf(d->err, sizeof d->err, "%s: %s", what, hipGetErrorString(e));
-    return -1;
-}
-#define FGL_HIP(d, call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return fgl_fail(d, #call, e_); } while (0)
 
 const char* fgl_dev_error(FglDev* d) { return d->err; }
 int64_t fgl_dev_line_bound(int32_t n_samples) { return (int64_t)fgl::MAX_POS_LEN + 1 + (int64_t)n_samples * fgl::VALUE_BOUND; }
 
-static int fgl_dev_setup(FglDev* d) {
-    FGL_HIP(d, hipSetDevice(d->device));
-    FGL_HIP(d, hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    const size_t R = (size_t)d->max_recs, N = (size_t)d->N;
-    for (FglSlot& s : d->slot) {
-        auto pinned = [&](size_t bytes) { return vgl_host_alloc_on(d->device, bytes ? bytes : 1); };
-        s.h_text = (uint8_t*)pinned((size_t)d->max_text); s.h_recs = (fgl::Rec*)pinned(R * sizeof(fgl::Rec));
-        s.h_status = (int32_t*)pinned(R * 4); s.h_off = (int64_t*)pinned((R + 1) * 8); s.h_csv = (uint8_t*)pinned((size_t)d->cap);
-        if (!s.h_text || !s.h_recs || !s.h_status || !s.h_off || !s.h_csv) {
-            snprintf(d->err, sizeof d->err, "page-locked host memory could not be allocated: %s", vgl_last_error());
-            return -1;
-        }
-        FGL_HIP(d, hipMalloc((void**)&s.d_text, (size_t)d->max_text + LB));
-        FGL_HIP(d, hipMalloc((void**)&s.d_recs, R * sizeof(fgl::Rec)));
-        FGL_HIP(d, hipMalloc((void**)&s.d_plane, R * N * 4));
-        FGL_HIP(d, hipMalloc((void**)&s.d_status, R * 4));
-        FGL_HIP(d, hipMalloc((void**)&s.d_len, R * 8));
-        FGL_HIP(d, hipMalloc((void**)&s.d_off, (R + 1) * 8));
-        FGL_HIP(d, hipMalloc((void**)&s.d_csv, (size_t)d->cap + 1));
-        FGL_HIP(d, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    }
-    return 0;
-}
-
 FglDev* fgl_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, char* err, size_t err_len) {
-    auto refuse = [&](const char* why) { snprintf(err, err_len, "%s", why); return (FglDev*)nullptr; };
-    if (n_samples <= 0 || max_recs <= 0 || max_text < 0) return refuse("bad batch shape");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return refuse("no HIP device is available");
-    if (device < 0 || device >= nd) return refuse("no such device");
-    FglDev* d = new FglDev();
-    d->device = device; d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text;
-    d->cap = (int64_t)max_recs * fgl_dev_line_bound(n_samples);
-    if (fgl_dev_setup(d) != 0) { snprintf(err, err_len, "%s", d->err); fgl_dev_destroy(d); return nullptr; }
-    return d;
+    if (n_samples <= 0 || max_recs <= 0 || max_text < 0) { snprintf(err, err_len, "bad batch shape"); return nullptr; }
+    return batchdev::create<FglDev>(device, err, err_len, [&](FglDev* d) {
+        d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text;
+        d->cap = (int64_t)max_recs * fgl_dev_line_bound(n_samples);
+        const size_t R = (size_t)d->max_recs, N = (size_t)d->N;
+        for (FglDev::Slot& s : d->slot) {
+            bool ok = s.h_text.alloc(d->device, (size_t)d->max_text); ok &= s.h_recs.alloc(d->device, R * sizeof(fgl::Rec));
+            ok &= s.h_status.alloc(d->device, R * 4); ok &= s.h_off.alloc(d->device, (R + 1) * 8); ok &= s.h_csv.alloc(d->device, (size_t)d->cap);
+            if (!ok) return d->no_pinned();
+            BATCH_HIP(d, s.d_text.alloc((size_t)d->max_text + LB));
+            BATCH_HIP(d, s.d_recs.alloc(R * sizeof(fgl::Rec)));
+            BATCH_HIP(d, s.d_plane.alloc(R * N * 4));
+            BATCH_HIP(d, s.d_status.alloc(R * 4));
+            BATCH_HIP(d, s.d_len.alloc(R * 8));
+            BATCH_HIP(d, s.d_off.alloc((R + 1) * 8));
+            BATCH_HIP(d, s.d_csv.alloc((size_t)d->cap + 1));
+        }
+        return 0;
+    });
 }
 
 uint8_t* fgl_dev_text(FglDev* d, int slot) { return d->slot[slot & 1].h_text; }
 fgl::Rec* fgl_dev_recs(FglDev* d, int slot) { return d->slot[slot & 1].h_recs; }
 
 int fgl_dev_submit(FglDev* d, int slot, int32_t n_recs, int64_t text_bytes, int bcf) {
-    FglSlot& s = d->slot[slot & 1];
-    if (s.busy || n_recs < 0 || n_recs > d->max_recs || text_bytes < 0 || text_bytes > d->max_text) {
-        snprintf(d->err, sizeof d->err, "a batch outside the shape the handle was made for, or a slot still in flight");
-        return -1;
-    }
-    s.n_recs = n_recs; s.busy = true;
+    FglDev::Slot& s = d->slot[slot & 1];
+    if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && text_bytes >= 0 && text_bytes <= d->max_text) != 0) return -1;
     if (n_recs == 0) return 0;
     hipStream_t st = d->stream;
     const size_t R = (size_t)n_recs;
-    if (text_bytes > 0) FGL_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
-    FGL_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(fgl::Rec), hipMemcpyHostToDevice, st));
+    if (text_bytes > 0) BATCH_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
+    BATCH_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(fgl::Rec), hipMemcpyHostToDevice, st));
     const ParseArgs P{s.d_text, text_bytes, s.d_recs, n_recs, d->N, s.d_plane, s.d_status};
     if (bcf) hipLaunchKernelGGL(k_fgl_pick, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
     else hipLaunchKernelGGL(k_fgl_parse, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
-    FGL_HIP(d, hipGetLastError());
+    BATCH_HIP(d, hipGetLastError());
     const LineArgs L{d->N, n_recs, s.d_recs, s.d_plane, s.d_status, s.d_len, s.d_off, s.d_csv, d->cap};
     hipLaunchKernelGGL(k_fgl_plan, dim3((unsigned)n_recs), dim3(NT), 0, st, L);
-    FGL_HIP(d, hipGetLastError());
-    hipLaunchKernelGGL(k_fgl_scan, dim3(1), dim3(SNT), 0, st, L);
-    FGL_HIP(d, hipGetLastError());
+    BATCH_HIP(d, hipGetLastError());
+    hipLaunchKernelGGL(wgscan::k_offsets_scan, dim3(1), dim3(wgscan::SCAN_NT), 0, st, (const int64_t*)s.d_len, (int64_t*)s.d_off, n_recs);
+    BATCH_HIP(d, hipGetLastError());
     hipLaunchKernelGGL(k_fgl_write, dim3((unsigned)n_recs), dim3(NT), 0, st, L);
-    FGL_HIP(d, hipGetLastError());
-    FGL_HIP(d, hipMemcpyAsync(s.h_off, s.d_off, (R + 1) * 8, hipMemcpyDeviceToHost, st));
-    FGL_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, R * 4, hipMemcpyDeviceToHost, st));
-    FGL_HIP(d, hipEventRecord(s.done, st));
-    return 0;
+    BATCH_HIP(d, hipGetLastError());
+    BATCH_HIP(d, hipMemcpyAsync(s.h_off, s.d_off, (R + 1) * 8, hipMemcpyDeviceToHost, st));
+    BATCH_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, R * 4, hipMemcpyDeviceToHost, st));
+    return d->end_submit(slot);
 }
 
 int fgl_dev_wait(FglDev* d, int slot, FglBatchOut* out) {
-    FglSlot& s = d->slot[slot & 1];
-    if (!s.busy) { snprintf(d->err, sizeof d->err, "nothing in flight in this slot"); return -1; }
-    s.busy = false;
-    const size_t R = (size_t)s.n_recs;
-    if (s.n_recs > 0) FGL_HIP(d, hipEventSynchronize(s.done));
-    else s.h_off[0] = 0;
+    FglDev::Slot& s = d->slot[slot & 1];
+    if (d->begin_wait(slot) != 0) return -1;
+    const size_t R = (size_t)d->head[slot & 1].n_recs;
+    if (R == 0) s.h_off[0] = 0;
     const int64_t n_csv = s.h_off[R];
-    if (n_csv < 0 || n_csv > d->cap) { snprintf(d->err, sizeof d->err, "a batch's CSV text is longer than its bound"); return -1; }
+    if (n_csv < 0 || n_csv > d->cap) return d->refuse("a batch's CSV text is longer than its bound");
     if (n_csv > 0) {
-        FGL_HIP(d, hipMemcpyAsync(s.h_csv, s.d_csv, (size_t)n_csv, hipMemcpyDeviceToHost, d->stream));
-        FGL_HIP(d, hipStreamSynchronize(d->stream));
+        BATCH_HIP(d, hipMemcpyAsync(s.h_csv, s.d_csv, (size_t)n_csv, hipMemcpyDeviceToHost, d->stream));
+        BATCH_HIP(d, hipStreamSynchronize(d->stream));
     }
     out->status = s.h_status; out->off = s.h_off; out->csv = s.h_csv;
     return 0;
 }
 
-void fgl_dev_quiesce(FglDev* d) { if (d && d->stream) (void)hipStreamSynchronize(d->stream); }
-
-void fgl_dev_destroy(FglDev* d) {
-    if (!d) return;
-    fgl_dev_quiesce(d);
-    for (FglSlot& s : d->slot) {
-        for (void* p : {(void*)s.h_text, (void*)s.h_recs, (void*)s.h_status, (void*)s.h_off, (void*)s.h_csv}) if (p) vgl_host_free(p);
-        for (void* p : {(void*)s.d_text, (void*)s.d_recs, (void*)s.d_plane, (void*)s.d_status, (void*)s.d_len, (void*)s.d_off, (void*)s.d_csv}) if (p) (void)hipFree(p);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    delete d;
-}
+void fgl_dev_quiesce(FglDev* d) { if (d) d->quiesce(); }
+void fgl_dev_destroy(FglDev* d) { batchdev::destroy(d); }

@@ -7,7 +7,8 @@
 // outside the device grammar, a value index outside the record's values, a wrong column count) is redone whole by the strtod reader
 // below, which owns every message.  Both paths therefore write the same bytes.  A run that has to stop does so at the record where the
 // host path stops: the lines and messages of the records before it are written first.
-#include "../host/vcf_input.h"
+#include "record_file.h"
+#include "batch_plan.h"
 #include "fgl_dev.h"
 
 namespace {
@@ -39,19 +40,14 @@ Opt parse_opt(int argc, char** argv) {
         if (!strcmp(a, "-h") || !strcmp(a, "--help")) { fputs(FGL_USAGE, stderr); exit(0); }
         if (i + 1 >= argc) die("Missing value for arg:%s", a);
         const char* v = argv[++i];
-        auto num = [&](int lo, int hi) {
-            char* e; const long x = strtol(v, &e, 10);
-            if (e == v || *e || x < lo || x > hi) die("%s takes an integer in %d .. %d, not '%s'", a, lo, hi, v);
-            return (int)x;
-        };
         if (!strcmp(a, "-i") || !strcmp(a, "--input")) o.in = v;
         else if (!strcmp(a, "-gt") || !strcmp(a, "--genotype")) o.gt = v;
         else if (!strcmp(a, "-o")) o.out = v;
-        else if (!strcmp(a, "--on-device")) o.on_device = num(0, 1);
-        else if (!strcmp(a, "--device")) o.device = num(0, 1 << 20);
-        else if (!strcmp(a, "--batch-records")) o.batch = num(1, 1 << 24);
-        else if (!strcmp(a, "--messages")) o.messages = num(0, 1);
-        else if (!strcmp(a, "--verbose")) o.verbose = num(0, 1);
+        else if (!strcmp(a, "--on-device")) o.on_device = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--device")) o.device = option_int(a, v, 0, 1 << 20);
+        else if (!strcmp(a, "--batch-records")) o.batch = option_int(a, v, 1, 1 << 24);
+        else if (!strcmp(a, "--messages")) o.messages = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
         else die("Unknown arg:%s", a);
     }
     if (o.in.empty()) die("Input file not specified. Exiting...");
@@ -191,34 +187,22 @@ void match_alleles(const Opt& o, const char first, const int j, Note& n) {
 
 void Run::notes_text() {
     const char* const t0 = (const char*)raw.data();
-    const char* p = t0; const char* const end = p + raw.size();
-    std::vector<std::pair<const char*, const char*>> lines;
-    std::vector<std::string> f;
-    while (p < end) {
-        const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
-        const char* le = nl ? nl : end;
-        if (le > p) {
-            if (le - p >= 2 && p[0] == '#' && p[1] == '#') header.emplace_back(p, le);
-            else if (p[0] == '#') { split(std::string(p, le), '\t', f); for (size_t i = 9; i < f.size(); i++) samples.push_back(f[i]); }
-            else lines.emplace_back(p, le);
-        }
-        p = nl ? nl + 1 : end;
-    }
+    TextLines tl = scan_text(raw);
+    header = std::move(tl.header); samples = std::move(tl.samples);
+    const std::vector<std::pair<int64_t, int64_t>>& lines = tl.lines;
     N = (int64_t)samples.size();
     const bool defined = header_defines_gl(header, nullptr);
     char msg[256];
     notes.reserve(lines.size());
     for (size_t i = 0; i < lines.size(); i++) {
-        const char* lb = lines[i].first; const char* le = lines[i].second;
-        const char* col_at[10]; int nc = 0; col_at[0] = lb;
-        for (const char* q = lb; q < le && nc < 9; q++) if (*q == '\t') col_at[++nc] = q + 1;
+        const char* lb = t0 + lines[i].first; const char* le = t0 + lines[i].second;
+        const char* col_at[10]; int nc;
+        nine_columns(lb, le, col_at, nc);
         Note n;
-        if (nc >= 1) n.pos = atoll(std::string(col_at[1], col_at[2 > nc ? nc : 2]).c_str());
+        n.pos = pos_column(col_at, nc);
         if (nc < 9) { snprintf(msg, sizeof msg, "Record %zu has fewer than 10 columns (a FORMAT/GL column is required).", i + 1); stop = msg; return; }
         // GL must be readable before anything else
-        n.k = -1;
-        { int k = 0; const char* b = col_at[8]; const char* const fe = col_at[9] - 1;
-          for (const char* q = b;; q++) if (q == fe || *q == ':') { if (q - b == 2 && b[0] == 'G' && b[1] == 'L' && n.k < 0) n.k = k; k++; if (q == fe) break; b = q + 1; } }
+        n.k = format_key_index(col_at[8], col_at[9] - 1, "GL");
         if (!defined || n.k < 0) { snprintf(msg, sizeof msg, "Could not read GL tag at position %lld. Exiting...", (long long)n.pos); stop = msg; return; }
         const char* const ref = col_at[3]; const char* const alt = col_at[4]; const char* const alt_end = col_at[5] - 1;
         int j = 0;
@@ -247,24 +231,17 @@ void Run::notes_bcf() {
     N = (int64_t)samples.size();
     std::string type;
     const bool defined = header_defines_gl(header, &type) && type == "Float";
-    std::vector<int32_t> iv; char msg[256];
+    char msg[256];
     while (c.off < c.size) {
-        BcfRecAt at; int n_fmt, ty, nv;
+        BcfRecAt at; int n_fmt;
         bcf_scan_record(c, at);
         Rec r;
         bcf_shared(c, d, at, (size_t)N, r, n_fmt);
         Note n; n.pos = r.pos0 + 1; n.k = -1;
         bool is_float = false;
-        for (int k = 0; k < n_fmt; k++) {
-            c.typed(ty, nv); c.ints(ty, nv, iv);
-            const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
-            if (key == d.dict.end()) c.fail("BCF: undefined FORMAT key");
-            c.typed(ty, nv);
-            const size_t w = ty == 1 ? 1 : ty == 2 ? 2 : (ty == 3 || ty == 5) ? 4 : ty == 7 ? 1 : 0;
-            if (c.off + w * nv * (size_t)N > c.size) c.fail("truncated BCF record");
-            if (key->second == "GL" && n.k < 0) { n.k = k; is_float = ty == 5 && nv >= 1; n.off = (int64_t)c.off; n.len = nv; }
-            c.off += w * nv * (size_t)N;
-        }
+        bcf_format_fields(c, d, n_fmt, (size_t)N, [&](int k, const std::string& key, int ty, int nv, size_t data_off) {
+            if (key == "GL" && n.k < 0) { n.k = k; is_float = ty == 5 && nv >= 1; n.off = (int64_t)data_off; n.len = nv; }
+        });
         c.off = at.rec_end;
         if (!defined || n.k < 0 || !is_float) { snprintf(msg, sizeof msg, "Could not read GL tag at position %lld. Exiting...", (long long)n.pos); stop = msg; return; }
         for (size_t j = 0; j < r.alleles.size() && j < (size_t)INT16_MAX; j++) match_alleles(o, r.alleles[j].empty() ? '\0' : r.alleles[j][0], (int)j, n);
@@ -287,16 +264,10 @@ void run_device(Run& R, std::vector<uint32_t>& plane) {
     auto bytes_of = [&](const Note& n) { return R.bcf ? ((int64_t)R.N * n.len * 4) : (int64_t)n.len; };
     // a batch: at most --batch-records records, 64 MiB of CSV bound and 64 MiB of text (one record at least)
     const int64_t TEXT_MOST = 64ll << 20;
-    int64_t B = std::max<int64_t>(1, std::min<int64_t>(R.o.batch, TEXT_MOST / fgl_dev_line_bound((int32_t)R.N)));
-    std::vector<std::pair<size_t, size_t>> batches;                     // [j0, j1) of sent
-    int64_t max_text = 1; int64_t max_recs = 1;
-    for (size_t j = 0; j < sent.size();) {
-        size_t j1 = j; int64_t t = 0;
-        while (j1 < sent.size() && (int64_t)(j1 - j) < B && (j1 == j || t + bytes_of(notes[sent[j1]]) <= TEXT_MOST)) t += bytes_of(notes[sent[j1++]]);
-        batches.emplace_back(j, j1);
-        max_text = std::max(max_text, t); max_recs = std::max<int64_t>(max_recs, (int64_t)(j1 - j));
-        j = j1;
-    }
+    const int64_t B = std::max<int64_t>(1, std::min<int64_t>(R.o.batch, TEXT_MOST / fgl_dev_line_bound((int32_t)R.N)));
+    const BatchPlan plan = plan_batches(sent.size(), B, {TEXT_MOST}, [&](size_t j, size_t) { return bytes_of(notes[sent[j]]); });
+    const std::vector<std::pair<size_t, size_t>>& batches = plan.ranges;     // [j0, j1) of sent
+    const int64_t max_text = std::max<int64_t>(1, plan.max_cost[0]), max_recs = std::max<int64_t>(1, plan.max_recs);
     char err[256];
     R.dev = fgl_dev_create(R.o.device, (int32_t)R.N, (int32_t)max_recs, max_text, err, sizeof err);
     if (!R.dev) { R.notes.clear(); R.stop_run("--on-device 1: %s (device %d; --on-device 0 reads on the host)", err, R.o.device); }
@@ -348,15 +319,7 @@ int main(int argc, char** argv) {
     R.o = parse_opt(argc, argv);
     const Opt& o = R.o;
     double t0 = now_s();
-    {
-        gzFile fp = gzopen(o.in.c_str(), "r");                         // plain text, gzip / BGZF, or BCF inside either
-        if (!fp) die("Could not open file: %s", o.in.c_str());
-        gzbuffer(fp, 1 << 20);
-        std::vector<uint8_t> chunk(1 << 22);
-        int k;
-        while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) R.raw.insert(R.raw.end(), chunk.begin(), chunk.begin() + k);
-        gzclose(fp);
-    }
+    R.raw = read_whole(o.in);
     R.out_fp = o.out.empty() ? stdout : fopen(o.out.c_str(), "w");
     if (!R.out_fp) die("Could not open output file %s for writing", o.out.c_str());
     R.t_read = now_s() - t0; t0 = now_s();

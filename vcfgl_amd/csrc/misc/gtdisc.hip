@@ -13,7 +13,7 @@
 //                     counters -- a counter belongs to one sample and a run has at most 32768 records, so none can wrap -- and once per
 //                     workgroup the non-zero counters are added to the int64 table (layout of vgl_disc_table_len) with 64-bit atomics.
 //   k_gtd_list_plan   a workgroup per record: the byte counts of its -doGQ 1 / 2 lines and of its -perSite lines (0 for a ST_HOST record)
-//   k_gtd_list_scan   one workgroup: the exclusive prefix sums of both counts over the batch's records
+//   k_offsets_scan    (wg_scan.hip.h) a workgroup per count: the exclusive prefix sums of both counts over the batch's records
 //   k_gtd_list_write  a workgroup per record, a lane per line: the lines' lengths are scanned across the workgroup, chunk by chunk, and
 //                     every lane formats its line at its offset, never past the text's capacity
 // The planes never leave the device; the table is read once, the listing text per batch.
@@ -25,6 +25,7 @@
 #include "../../../include/vcfgl_hip.h"
 #include "gtdisc_dev.h"
 #include "column_walk.hip.h"
+#include "batch_dev.hip.h"
 
 namespace {
 
@@ -37,7 +38,6 @@ constexpr int NCELL = gtd::N_CELLS, NGQ = gtd::N_GQ;
 constexpr int HIST = NCELL * NGQ * SG;   // 16-bit counters
 constexpr int MAX_RUN = 32768;           // records per tally workgroup: below 2^16
 constexpr size_t TALLY_LDS = (size_t)HIST * 2 + SG * sizeof(uint32_t);
-constexpr int SNT = 1024;                // lanes of the scan
 
 struct ParseArgs {
     const uint8_t* text; int64_t text_bytes;
@@ -176,31 +176,7 @@ __global__ void __launch_bounds__(NT) k_gtd_list_plan(const ListArgs A) {
     }
 }
 
-// off[w][0 .. n_recs] = exclusive prefix sums of len[w][0 .. n_recs), w = blockIdx.x
-__global__ void __launch_bounds__(SNT) k_gtd_list_scan(const ListArgs A) {
-    __shared__ long long s_tot[2][SNT / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int64_t* len = A.len + (size_t)blockIdx.x * A.n_recs;
-    int64_t* off = A.off + (size_t)blockIdx.x * ((size_t)A.n_recs + 1);
-    long long base = 0;
-    const int n_chunks = (A.n_recs + SNT - 1) / SNT;
-    for (int c = 0; c < n_chunks; c++) {
-        const int i = c * SNT + t;
-        const long long v = i < A.n_recs ? (long long)len[i] : 0;
-        long long inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const long long y = __shfl_up(inc, d, 64); if (lane >= d) inc += y; }
-        if (lane == 63) s_tot[c & 1][wave] = inc;
-        __syncthreads();
-        long long before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < SNT / 64; k++) { const long long x = s_tot[c & 1][k]; if (k < wave) before += x; total += x; }
-        if (i < A.n_recs) off[i] = (int64_t)(base + before + inc - v);
-        base += total;
-    }
-    if (t == 0) off[A.n_recs] = (int64_t)base;
-}
-
+// (two values a lane go through one step here, with one __syncthreads a chunk: the step is written out, not wgscan::step twice)
 __global__ void __launch_bounds__(NT) k_gtd_list_write(const ListArgs A) {
     __shared__ uint32_t s_tot[2][2][NT / 64];
     const int rec = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -247,95 +223,65 @@ __global__ void __launch_bounds__(NT) k_gtd_list_write(const ListArgs A) {
 
 }  // namespace
 
-// ---- the handle --------------------------------------------------------------------------------------------------------------
-struct GtdSlot {
-    uint8_t* h_text = nullptr; gtd::Rec* h_recs = nullptr;              // page-locked staging (vgl_host_alloc_on)
-    int32_t* h_status = nullptr; int64_t* h_off = nullptr; uint8_t* h_list = nullptr; uint8_t* h_site = nullptr;
-    uint8_t* d_text = nullptr; gtd::Rec* d_recs = nullptr;
-    uint8_t* d_planes = nullptr; int32_t* d_status = nullptr; int64_t* d_len = nullptr; int64_t* d_off = nullptr;
-    uint8_t* d_list = nullptr; uint8_t* d_site = nullptr;
-    hipEvent_t done = nullptr;
-    int32_t n_recs = 0; bool busy = false;
-};
-struct GtdDev {
-    int device = 0; int32_t N = 0, max_recs = 0; int64_t max_text = 0; int list = 0, per_site = 0;
+// ---- the handle (batch_dev.hip.h) ------------------------------------------------------------------------------------------------
+struct GtdDev : batchdev::BatchDev {
+    int32_t N = 0, max_recs = 0; int64_t max_text = 0; int list = 0, per_site = 0;
     int64_t list_cap = 0, site_cap = 0;
-    hipStream_t stream = nullptr;
-    unsigned long long* d_table = nullptr; int64_t table_len = 0;
-    GtdSlot slot[2];
-    char err[256] = {0};
+    batchdev::DevMem<unsigned long long> d_table; int64_t table_len = 0;
+    struct Slot {
+        batchdev::PinMem<uint8_t> h_text; batchdev::PinMem<gtd::Rec> h_recs;
+        batchdev::PinMem<int32_t> h_status; batchdev::PinMem<int64_t> h_off; batchdev::PinMem<uint8_t> h_list, h_site;
+        batchdev::DevMem<uint8_t> d_text; batchdev::DevMem<gtd::Rec> d_recs;
+        batchdev::DevMem<uint8_t> d_planes; batchdev::DevMem<int32_t> d_status; batchdev::DevMem<int64_t> d_len, d_off;
+        batchdev::DevMem<uint8_t> d_list, d_site;
+    } slot[2];
 };
-
-static int gtd_fail(GtdDev* d, const char* what, hipError_t e) {
-    snprintf(d->err, sizeof d->err, "%s: %s", what, hipGetErrorString(e));
-    return -1;
-}
-#define GTD_HIP(d, call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return gtd_fail(d, #call, e_); } while (0)
 
 const char* gtd_dev_error(GtdDev* d) { return d->err; }
 
-static int gtd_dev_setup(GtdDev* d) {
-    GTD_HIP(d, hipSetDevice(d->device));
-    GTD_HIP(d, hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    d->table_len = vgl_disc_table_len(d->N);
-    GTD_HIP(d, hipMalloc((void**)&d->d_table, (size_t)d->table_len * 8));
-    GTD_HIP(d, hipMemsetAsync(d->d_table, 0, (size_t)d->table_len * 8, d->stream));
-    const size_t R = (size_t)d->max_recs, N = (size_t)d->N;
-    for (GtdSlot& s : d->slot) {
-        auto pinned = [&](size_t bytes) { return vgl_host_alloc_on(d->device, bytes ? bytes : 1); };
-        s.h_text = (uint8_t*)pinned((size_t)d->max_text); s.h_recs = (gtd::Rec*)pinned(R * sizeof(gtd::Rec));
-        s.h_status = (int32_t*)pinned(R * 4); s.h_off = (int64_t*)pinned(2 * (R + 1) * 8);
-        s.h_list = (uint8_t*)pinned((size_t)d->list_cap); s.h_site = (uint8_t*)pinned((size_t)d->site_cap);
-        if (!s.h_text || !s.h_recs || !s.h_status || !s.h_off || !s.h_list || !s.h_site) {
-            snprintf(d->err, sizeof d->err, "page-locked host memory could not be allocated: %s", vgl_last_error());
-            return -1;
-        }
-        GTD_HIP(d, hipMalloc((void**)&s.d_text, (size_t)d->max_text + LB));
-        GTD_HIP(d, hipMalloc((void**)&s.d_recs, R * sizeof(gtd::Rec)));
-        GTD_HIP(d, hipMalloc((void**)&s.d_planes, 3 * R * N));
-        GTD_HIP(d, hipMalloc((void**)&s.d_status, R * 4));
-        GTD_HIP(d, hipMalloc((void**)&s.d_len, 2 * R * 8));
-        GTD_HIP(d, hipMalloc((void**)&s.d_off, 2 * (R + 1) * 8));
-        GTD_HIP(d, hipMalloc((void**)&s.d_list, (size_t)d->list_cap + 1));
-        GTD_HIP(d, hipMalloc((void**)&s.d_site, (size_t)d->site_cap + 1));
-        GTD_HIP(d, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    }
-    return 0;
-}
-
 GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, char* err, size_t err_len) {
-    auto refuse = [&](const char* why) { snprintf(err, err_len, "%s", why); return (GtdDev*)nullptr; };
-    if (n_samples <= 0 || max_recs <= 0 || max_text < 0) return refuse("bad batch shape");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return refuse("no HIP device is available");
-    if (device < 0 || device >= nd) return refuse("no such device");
-    GtdDev* d = new GtdDev();
-    d->device = device; d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->list = list; d->per_site = per_site;
-    d->list_cap = list ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
-    d->site_cap = per_site ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
-    if (gtd_dev_setup(d) != 0) { snprintf(err, err_len, "%s", d->err); gtd_dev_destroy(d); return nullptr; }
-    return d;
+    if (n_samples <= 0 || max_recs <= 0 || max_text < 0) { snprintf(err, err_len, "bad batch shape"); return nullptr; }
+    return batchdev::create<GtdDev>(device, err, err_len, [&](GtdDev* d) {
+        d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->list = list; d->per_site = per_site;
+        d->list_cap = list ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
+        d->site_cap = per_site ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
+        d->table_len = vgl_disc_table_len(d->N);
+        BATCH_HIP(d, d->d_table.alloc((size_t)d->table_len * 8));
+        BATCH_HIP(d, hipMemsetAsync(d->d_table, 0, (size_t)d->table_len * 8, d->stream));
+        const size_t R = (size_t)d->max_recs, N = (size_t)d->N;
+        for (GtdDev::Slot& s : d->slot) {
+            bool ok = s.h_text.alloc(d->device, (size_t)d->max_text); ok &= s.h_recs.alloc(d->device, R * sizeof(gtd::Rec));
+            ok &= s.h_status.alloc(d->device, R * 4); ok &= s.h_off.alloc(d->device, 2 * (R + 1) * 8);
+            ok &= s.h_list.alloc(d->device, (size_t)d->list_cap); ok &= s.h_site.alloc(d->device, (size_t)d->site_cap);
+            if (!ok) return d->no_pinned();
+            BATCH_HIP(d, s.d_text.alloc((size_t)d->max_text + LB));
+            BATCH_HIP(d, s.d_recs.alloc(R * sizeof(gtd::Rec)));
+            BATCH_HIP(d, s.d_planes.alloc(3 * R * N));
+            BATCH_HIP(d, s.d_status.alloc(R * 4));
+            BATCH_HIP(d, s.d_len.alloc(2 * R * 8));
+            BATCH_HIP(d, s.d_off.alloc(2 * (R + 1) * 8));
+            BATCH_HIP(d, s.d_list.alloc((size_t)d->list_cap + 1));
+            BATCH_HIP(d, s.d_site.alloc((size_t)d->site_cap + 1));
+        }
+        return 0;
+    });
 }
 
 uint8_t* gtd_dev_text(GtdDev* d, int slot) { return d->slot[slot & 1].h_text; }
 gtd::Rec* gtd_dev_recs(GtdDev* d, int slot) { return d->slot[slot & 1].h_recs; }
 
 int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
-    GtdSlot& s = d->slot[slot & 1];
-    if (s.busy || n_recs < 0 || n_recs > d->max_recs || text_bytes < 0 || text_bytes > d->max_text) {
-        snprintf(d->err, sizeof d->err, "a batch outside the shape the handle was made for, or a slot still in flight");
-        return -1;
-    }
-    s.n_recs = n_recs; s.busy = true;
+    GtdDev::Slot& s = d->slot[slot & 1];
+    if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && text_bytes >= 0 && text_bytes <= d->max_text) != 0) return -1;
     if (n_recs == 0) return 0;
     hipStream_t st = d->stream;
     const size_t R = (size_t)n_recs, N = (size_t)d->N;
-    GTD_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
-    GTD_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(gtd::Rec), hipMemcpyHostToDevice, st));
+    BATCH_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
+    BATCH_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(gtd::Rec), hipMemcpyHostToDevice, st));
     uint8_t* tb = s.d_planes; uint8_t* cb = tb + (size_t)d->max_recs * N; uint8_t* gq = cb + (size_t)d->max_recs * N;
     const ParseArgs P{s.d_text, text_bytes, s.d_recs, n_recs, d->N, tb, cb, gq, s.d_status};
     hipLaunchKernelGGL(k_gtd_parse, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
-    GTD_HIP(d, hipGetLastError());
+    BATCH_HIP(d, hipGetLastError());
     // the tally: about two workgroups per CU where the batch has them, runs of at least 16 records, never more than MAX_RUN
     const int groups = (d->N + SG - 1) / SG;
     int runs = 512 / groups;
@@ -346,57 +292,42 @@ int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
     if (run > MAX_RUN) run = MAX_RUN;
     runs = (n_recs + run - 1) / run;
     const TallyArgs T{d->N, n_recs, run, tb, cb, gq, s.d_status, d->d_table};
-    if (runs > 65535) { snprintf(d->err, sizeof d->err, "too many records for one batch"); return -1; }
+    if (runs > 65535) return d->refuse("too many records for one batch");
     hipLaunchKernelGGL(k_gtd_tally, dim3((unsigned)groups, (unsigned)runs), dim3(TNT), TALLY_LDS, st, T);
-    GTD_HIP(d, hipGetLastError());
+    BATCH_HIP(d, hipGetLastError());
     if (d->list || d->per_site) {
         const ListArgs L{d->N, n_recs, d->list, d->per_site, s.d_recs, tb, cb, gq, s.d_status, s.d_len, s.d_off, s.d_list, s.d_site, d->list_cap, d->site_cap};
         hipLaunchKernelGGL(k_gtd_list_plan, dim3((unsigned)n_recs), dim3(NT), 0, st, L);
-        GTD_HIP(d, hipGetLastError());
-        hipLaunchKernelGGL(k_gtd_list_scan, dim3(2), dim3(SNT), 0, st, L);
-        GTD_HIP(d, hipGetLastError());
+        BATCH_HIP(d, hipGetLastError());
+        hipLaunchKernelGGL(wgscan::k_offsets_scan, dim3(2), dim3(wgscan::SCAN_NT), 0, st, (const int64_t*)s.d_len, (int64_t*)s.d_off, n_recs);
+        BATCH_HIP(d, hipGetLastError());
         hipLaunchKernelGGL(k_gtd_list_write, dim3((unsigned)n_recs), dim3(NT), 0, st, L);
-        GTD_HIP(d, hipGetLastError());
-        GTD_HIP(d, hipMemcpyAsync(s.h_off, s.d_off, 2 * (R + 1) * 8, hipMemcpyDeviceToHost, st));
+        BATCH_HIP(d, hipGetLastError());
+        BATCH_HIP(d, hipMemcpyAsync(s.h_off, s.d_off, 2 * (R + 1) * 8, hipMemcpyDeviceToHost, st));
     }
-    GTD_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, R * 4, hipMemcpyDeviceToHost, st));
-    GTD_HIP(d, hipEventRecord(s.done, st));
-    return 0;
+    BATCH_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, R * 4, hipMemcpyDeviceToHost, st));
+    return d->end_submit(slot);
 }
 
 int gtd_dev_wait(GtdDev* d, int slot, GtdBatchOut* out) {
-    GtdSlot& s = d->slot[slot & 1];
-    if (!s.busy) { snprintf(d->err, sizeof d->err, "nothing in flight in this slot"); return -1; }
-    s.busy = false;
-    const size_t R = (size_t)s.n_recs;
-    if (s.n_recs > 0) GTD_HIP(d, hipEventSynchronize(s.done));
-    if (!(d->list || d->per_site) || s.n_recs == 0) for (size_t i = 0; i < 2 * (R + 1); i++) s.h_off[i] = 0;
+    GtdDev::Slot& s = d->slot[slot & 1];
+    if (d->begin_wait(slot) != 0) return -1;
+    const size_t R = (size_t)d->head[slot & 1].n_recs;
+    if (!(d->list || d->per_site) || R == 0) for (size_t i = 0; i < 2 * (R + 1); i++) s.h_off[i] = 0;
     const int64_t n_list = s.h_off[R], n_site = s.h_off[2 * R + 1];
-    if (n_list < 0 || n_list > d->list_cap || n_site < 0 || n_site > d->site_cap) { snprintf(d->err, sizeof d->err, "a batch's listing is longer than its bound"); return -1; }
-    if (n_list > 0) GTD_HIP(d, hipMemcpyAsync(s.h_list, s.d_list, (size_t)n_list, hipMemcpyDeviceToHost, d->stream));
-    if (n_site > 0) GTD_HIP(d, hipMemcpyAsync(s.h_site, s.d_site, (size_t)n_site, hipMemcpyDeviceToHost, d->stream));
-    if (n_list > 0 || n_site > 0) GTD_HIP(d, hipStreamSynchronize(d->stream));
+    if (n_list < 0 || n_list > d->list_cap || n_site < 0 || n_site > d->site_cap) return d->refuse("a batch's listing is longer than its bound");
+    if (n_list > 0) BATCH_HIP(d, hipMemcpyAsync(s.h_list, s.d_list, (size_t)n_list, hipMemcpyDeviceToHost, d->stream));
+    if (n_site > 0) BATCH_HIP(d, hipMemcpyAsync(s.h_site, s.d_site, (size_t)n_site, hipMemcpyDeviceToHost, d->stream));
+    if (n_list > 0 || n_site > 0) BATCH_HIP(d, hipStreamSynchronize(d->stream));
     out->status = s.h_status; out->list_off = s.h_off; out->site_off = s.h_off + R + 1; out->list_text = s.h_list; out->site_text = s.h_site;
     return 0;
 }
 
 int gtd_dev_table(GtdDev* d, int64_t* table) {
-    GTD_HIP(d, hipMemcpyAsync(table, d->d_table, (size_t)d->table_len * 8, hipMemcpyDeviceToHost, d->stream));
-    GTD_HIP(d, hipStreamSynchronize(d->stream));
+    BATCH_HIP(d, hipMemcpyAsync(table, d->d_table, (size_t)d->table_len * 8, hipMemcpyDeviceToHost, d->stream));
+    BATCH_HIP(d, hipStreamSynchronize(d->stream));
     return 0;
 }
 
-void gtd_dev_quiesce(GtdDev* d) { if (d && d->stream) (void)hipStreamSynchronize(d->stream); }
-
-void gtd_dev_destroy(GtdDev* d) {
-    if (!d) return;
-    gtd_dev_quiesce(d);
-    for (GtdSlot& s : d->slot) {
-        for (void* p : {(void*)s.h_text, (void*)s.h_recs, (void*)s.h_status, (void*)s.h_off, (void*)s.h_list, (void*)s.h_site}) if (p) vgl_host_free(p);
-        for (void* p : {(void*)s.d_text, (void*)s.d_recs, (void*)s.d_planes, (void*)s.d_status, (void*)s.d_len, (void*)s.d_off, (void*)s.d_list, (void*)s.d_site}) if (p) (void)hipFree(p);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    if (d->d_table) (void)hipFree(d->d_table);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    delete d;
-}
+void gtd_dev_quiesce(GtdDev* d) { if (d) d->quiesce(); }
+void gtd_dev_destroy(GtdDev* d) { batchdev::destroy(d); }

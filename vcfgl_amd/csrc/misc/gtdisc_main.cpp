@@ -7,7 +7,8 @@
 // Both paths therefore write the same bytes.  A run that has to stop does so at the record the tool would stop at: what the records
 // before it gave is written first.
 #include <strings.h>
-#include "../host/vcf_input.h"
+#include "record_file.h"
+#include "batch_plan.h"
 #include "gtdisc_dev.h"
 
 namespace {
@@ -46,20 +47,15 @@ Opt parse_opt(int argc, char** argv) {
         if (!strcmp(a, "-h") || !strcmp(a, "--help")) { fputs(GTD_USAGE, stderr); exit(0); }
         if (i + 1 >= argc) die("Missing value for arg:%s", a);
         const char* v = argv[++i];
-        auto num = [&](int lo, int hi) {
-            char* e; const long x = strtol(v, &e, 10);
-            if (e == v || *e || x < lo || x > hi) die("%s takes an integer in %d .. %d, not '%s'", a, lo, hi, v);
-            return (int)x;
-        };
         if (!strcmp(a, "-i") || !strcmp(a, "--input")) o.call = v;
         else if (!strcmp(a, "-t") || !strcmp(a, "--truth")) o.truth = v;
         else if (!strcmp(a, "-o") || !strcmp(a, "--output")) o.out = v;
         else if (!strcasecmp(a, "-doGQ")) { o.do_gq = atoi(v); if (o.do_gq < 0 || o.do_gq > 8) die("Unknown doGq:%d", o.do_gq); }
-        else if (!strcasecmp(a, "-perSite")) o.per_site = num(0, 1);
-        else if (!strcmp(a, "--on-device")) o.on_device = num(0, 1);
-        else if (!strcmp(a, "--device")) o.device = num(0, 1 << 20);
-        else if (!strcmp(a, "--batch-records")) o.batch = num(1, 1 << 24);
-        else if (!strcmp(a, "--verbose")) o.verbose = num(0, 1);
+        else if (!strcasecmp(a, "-perSite")) o.per_site = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--on-device")) o.on_device = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--device")) o.device = option_int(a, v, 0, 1 << 20);
+        else if (!strcmp(a, "--batch-records")) o.batch = option_int(a, v, 1, 1 << 24);
+        else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
         else die("Unknown arg:%s", a);
     }
     if (o.call.empty()) die("Input file not specified. Please use -i/--input <file>.");
@@ -87,25 +83,20 @@ void bcf_lines(std::vector<uint8_t>& raw, Input& in) {
     bcf_header(c, d, v);
     in.header = v.header; in.samples = v.samples;
     const size_t N = v.samples.size();
-    std::string out; std::vector<int32_t> iv, gt, gq, pl; char num[16];
+    std::string out; std::vector<int32_t> gt, gq, pl; char num[16];
     while (c.off < c.size) {
-        BcfRecAt at; int n_fmt, type, n;
+        BcfRecAt at; int n_fmt;
         bcf_scan_record(c, at);
         Rec r;
         bcf_shared(c, d, at, N, r, n_fmt);
         int n_gt = 0, n_gq = 0, n_pl = 0; bool have_gt = false, have_gq = false, have_pl = false;
-        for (int k = 0; k < n_fmt; k++) {
-            c.typed(type, n); c.ints(type, n, iv);
-            const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
-            if (key == d.dict.end()) c.fail("BCF: undefined FORMAT key");
-            c.typed(type, n);
-            const size_t w = type == 1 ? 1 : type == 2 ? 2 : (type == 3 || type == 5) ? 4 : type == 7 ? 1 : 0;
-            const bool ints = type >= 1 && type <= 3;
-            if (ints && key->second == "GT") { c.ints(type, (int)(n * N), gt); n_gt = n; have_gt = true; }
-            else if (ints && key->second == "GQ") { c.ints(type, (int)(n * N), gq); n_gq = n; have_gq = true; }
-            else if (ints && key->second == "PL") { c.ints(type, (int)(n * N), pl); n_pl = n; have_pl = true; }
-            else { if (c.off + w * n * N > c.size) c.fail("truncated BCF record"); c.off += w * n * N; }
-        }
+        bcf_format_fields(c, d, n_fmt, N, [&](int, const std::string& key, int type, int n, size_t data_off) {
+            if (type < 1 || type > 3) return;
+            BcfIn v = c; v.off = data_off;                              // (the walker has checked that the vectors lie inside the file)
+            if (key == "GT") { v.ints(type, (int)(n * N), gt); n_gt = n; have_gt = true; }
+            else if (key == "GQ") { v.ints(type, (int)(n * N), gq); n_gq = n; have_gq = true; }
+            else if (key == "PL") { v.ints(type, (int)(n * N), pl); n_pl = n; have_pl = true; }
+        });
         if (!have_gt) die("Could not find GT tag at position %ld.", r.pos0 + 1);
         c.off = at.rec_end;
         const int64_t begin = (int64_t)out.size();
@@ -139,28 +130,11 @@ void bcf_lines(std::vector<uint8_t>& raw, Input& in) {
 
 Input read_input_file(const std::string& fn) {
     Input in;
-    gzFile fp = gzopen(fn.c_str(), "r");                         // plain text, gzip / BGZF, or BCF inside either
-    if (!fp) die("Could not open file: %s", fn.c_str());
-    gzbuffer(fp, 1 << 20);
-    std::vector<uint8_t> raw, chunk(1 << 22);
-    int k;
-    while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) raw.insert(raw.end(), chunk.begin(), chunk.begin() + k);
-    gzclose(fp);
+    std::vector<uint8_t> raw = read_whole(fn);
     if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) { bcf_lines(raw, in); return in; }
     in.text = std::move(raw);
-    const char* const t0 = (const char*)in.text.data();
-    const char* p = t0; const char* const end = p + in.text.size();
-    std::vector<std::string> f;
-    while (p < end) {
-        const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
-        const char* le = nl ? nl : end;
-        if (le > p) {
-            if (le - p >= 2 && p[0] == '#' && p[1] == '#') in.header.emplace_back(p, le);
-            else if (p[0] == '#') { split(std::string(p, le), '\t', f); for (size_t i = 9; i < f.size(); i++) in.samples.push_back(f[i]); }
-            else in.lines.emplace_back(p - t0, le - t0);
-        }
-        p = nl ? nl + 1 : end;
-    }
+    TextLines tl = scan_text(in.text);
+    in.header = std::move(tl.header); in.samples = std::move(tl.samples); in.lines = std::move(tl.lines);
     return in;
 }
 
@@ -177,10 +151,10 @@ Fixed parse_nine(const Input& in, const size_t i, const char* which) {
     Fixed f;
     const char* const t0 = (const char*)in.text.data();
     const char* lb = t0 + in.lines[i].first; const char* le = t0 + in.lines[i].second;
-    const char* col_at[10]; int nc = 0; col_at[0] = lb;
-    for (const char* q = lb; q < le && nc < 9; q++) if (*q == '\t') col_at[++nc] = q + 1;
+    const char* col_at[10]; int nc;
+    nine_columns(lb, le, col_at, nc);
     char msg[256];
-    if (nc >= 1) f.pos = atoll(std::string(col_at[1], col_at[2 > nc ? nc : 2]).c_str());
+    f.pos = pos_column(col_at, nc);
     if (nc < 9) { snprintf(msg, sizeof msg, "Record %zu of the %s file has fewer than 10 columns (a FORMAT/GT column is required).", i + 1, which); f.bad = msg; return f; }
     auto col = [&](int k) { return std::string(col_at[k], (size_t)(col_at[k + 1] - 1 - col_at[k])); };
     const std::string ref = col(3), alt = col(4);
@@ -188,12 +162,8 @@ Fixed parse_nine(const Input& in, const size_t i, const char* which) {
     if (ref.empty()) { snprintf(msg, sizeof msg, "Empty REF at position %lld of the %s file.", (long long)f.pos, which); f.bad = msg; return f; }
     f.first += ref[0];
     if (alt != ".") { split(alt, ',', g); for (auto& x : g) f.first += x.empty() ? '?' : x[0]; }
-    split(col(8), ':', g);
-    for (size_t k = 0; k < g.size(); k++) {
-        if (g[k] == "GT" && f.gti < 0) f.gti = (int)k;
-        if (g[k] == "GQ" && f.gqi < 0) f.gqi = (int)k;
-        if (g[k] == "PL" && f.pli < 0) f.pli = (int)k;
-    }
+    const char* const fmt_end = col_at[9] - 1;
+    f.gti = format_key_index(col_at[8], fmt_end, "GT"); f.gqi = format_key_index(col_at[8], fmt_end, "GQ"); f.pli = format_key_index(col_at[8], fmt_end, "PL");
     if (f.gti < 0) { snprintf(msg, sizeof msg, "Could not find GT tag at position %lld of the %s file.", (long long)f.pos, which); f.bad = msg; return f; }
     f.s_off = col_at[9] - t0; f.s_len = le - col_at[9];
     if (f.s_len > INT32_MAX) { snprintf(msg, sizeof msg, "The record at position %lld of the %s file is longer than 2 GiB.", (long long)f.pos, which); f.bad = msg; }
@@ -397,13 +367,10 @@ void run_device(Run& R) {
     int64_t B = R.o.batch;
     const int64_t per_rec = (int64_t)N * ((R.list || R.o.per_site) ? gtd::LINE_BOUND : 3);
     B = std::max<int64_t>(1, std::min<int64_t>(B, (64ll << 20) / std::max<int64_t>(per_rec, 1)));
-    const int64_t nb = ((int64_t)K + B - 1) / B;
-    int64_t max_text = 1;
-    for (int64_t b = 0; b < nb; b++) {
-        int64_t t = 0;
-        for (size_t j = (size_t)(b * B); j < std::min(K, (size_t)((b + 1) * B)); j++) t += R.pairs[j].rec.t_len + (int64_t)R.pairs[j].rec.c_len;
-        max_text = std::max(max_text, t);
-    }
+    const BatchPlan plan = plan_batches(K, B, {BATCH_NO_CAP}, [&](size_t j, size_t) { return R.pairs[j].rec.t_len + (int64_t)R.pairs[j].rec.c_len; });
+    const std::vector<std::pair<size_t, size_t>>& batches = plan.ranges;     // blocks of B records: the text has no cap of its own
+    const int64_t nb = (int64_t)batches.size();
+    const int64_t max_text = std::max<int64_t>(1, plan.max_cost[0]);
     char err[256];
     R.dev = gtd_dev_create(R.o.device, N, (int32_t)std::min<int64_t>(B, std::max<size_t>(K, 1)), max_text, R.list, R.o.per_site, err, sizeof err);
     if (!R.dev) R.stop_run("--on-device 1: %s (device %d; --on-device 0 compares on the host)", err, R.o.device);
@@ -412,7 +379,7 @@ void run_device(Run& R) {
         const int slot = (int)(b & 1);
         uint8_t* text = gtd_dev_text(R.dev, slot); gtd::Rec* recs = gtd_dev_recs(R.dev, slot);
         int64_t at = 0; int32_t n = 0;
-        for (size_t j = (size_t)(b * B); j < std::min(K, (size_t)((b + 1) * B)); j++, n++) {
+        for (size_t j = batches[b].first; j < batches[b].second; j++, n++) {
             const Pair& p = R.pairs[j];
             gtd::Rec r = p.rec;
             memcpy(text + at, R.truth.text.data() + p.rec.t_off, (size_t)r.t_len); r.t_off = at; at += r.t_len;
@@ -428,7 +395,7 @@ void run_device(Run& R) {
         if (gtd_dev_wait(R.dev, (int)(b & 1), &out) != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
         R.t_dev += now_s() - t0; t0 = now_s();
         int32_t n = 0;
-        for (size_t j = (size_t)(b * B); j < std::min(K, (size_t)((b + 1) * B)); j++, n++) {
+        for (size_t j = batches[b].first; j < batches[b].second; j++, n++) {
             if (out.status[n] != gtd::ST_OK) { R.n_host++; R.record_permissive(R.pairs[j]); continue; }
             if (R.list) R.list_buf.append((const char*)out.list_text + out.list_off[n], (size_t)(out.list_off[n + 1] - out.list_off[n]));
             if (R.o.per_site) R.site_buf.append((const char*)out.site_text + out.site_off[n], (size_t)(out.site_off[n + 1] - out.site_off[n]));

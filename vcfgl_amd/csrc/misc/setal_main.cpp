@@ -12,7 +12,8 @@
 // BCF input (raw or BGZF) is written as BCF (-O u, -O b): the shared block is rewritten (n_allele, the allele strings, QS resized, rlen),
 // GL / GP become N x nG_new floats, PL is re-typed to the narrowest of int8 / int16 / int32 over the record's values (--on-device 1: k_sal_bcf_apply
 // in batches, two in flight; --on-device 0: the same routines on the host, so both settings write the same bytes), the untouched fields are copied.  Text is written as text (-O v, -O z); a request across is refused.
-#include "../host/vcf_input.h"
+#include "record_file.h"
+#include "batch_plan.h"
 #include "sal_dev.h"
 
 namespace {
@@ -50,11 +51,6 @@ Opt parse_opt(int argc, char** argv) {
         if (!strcmp(a, "-v") || !strcmp(a, "--version")) { fprintf(stderr, "setalleles_hip [version: %s]\n\n", SAL_VERSION); exit(0); }
         if (i + 1 >= argc || !argv[i + 1][0]) die("Argument '%s' requires a value.", a);
         const char* v = argv[++i];
-        auto num = [&](int lo, int hi) {
-            char* e; const long x = strtol(v, &e, 10);
-            if (e == v || *e || x < lo || x > hi) die("%s takes an integer in %d .. %d, not '%s'", a, lo, hi, v);
-            return (int)x;
-        };
         if (!strcmp(a, "-i") || !strcmp(a, "--input")) o.in = v;
         else if (!strcmp(a, "-a") || !strcmp(a, "--alleles")) o.alleles = v;
         else if (!strcmp(a, "-O") || !strcmp(a, "--output-mode")) {
@@ -62,11 +58,11 @@ Opt parse_opt(int argc, char** argv) {
             o.mode = v[0];
         }
         else if (!strcmp(a, "-o") || !strcmp(a, "--output")) o.prefix = v;
-        else if (!strcmp(a, "--on-device")) o.on_device = num(0, 1);
-        else if (!strcmp(a, "--device")) o.device = num(0, 1 << 20);
-        else if (!strcmp(a, "--batch-records")) o.batch = num(1, 1 << 24);
-        else if (!strcmp(a, "--threads")) o.threads = num(1, 1024);
-        else if (!strcmp(a, "--verbose")) o.verbose = num(0, 1);
+        else if (!strcmp(a, "--on-device")) o.on_device = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--device")) o.device = option_int(a, v, 0, 1 << 20);
+        else if (!strcmp(a, "--batch-records")) o.batch = option_int(a, v, 1, 1 << 24);
+        else if (!strcmp(a, "--threads")) o.threads = option_int(a, v, 1, 1024);
+        else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
         else die("Unknown arg:%s", a);
     }
     if (o.in.empty()) die("Input file is required. Please provide a record file using the -i flag (e.g. -i input.vcf)");
@@ -77,18 +73,6 @@ Opt parse_opt(int argc, char** argv) {
     }
     o.out_fn = o.prefix + (o.mode == 'v' ? ".vcf" : o.mode == 'z' ? ".vcf.gz" : ".bcf");
     return o;
-}
-
-std::vector<uint8_t> read_whole(const std::string& fn) {
-    std::vector<uint8_t> raw;
-    gzFile fp = gzopen(fn.c_str(), "r");                               // plain text, gzip / BGZF
-    if (!fp) die("Could not open file: %s", fn.c_str());
-    gzbuffer(fp, 1 << 20);
-    std::vector<uint8_t> chunk(1 << 22);
-    int k;
-    while ((k = gzread(fp, chunk.data(), (unsigned)chunk.size())) > 0) raw.insert(raw.end(), chunk.begin(), chunk.begin() + k);
-    gzclose(fp);
-    return raw;
 }
 
 // ---- the alleles file: one list of 2 .. 5 names per line, REF first ---------------------------------------------------------------
@@ -325,6 +309,8 @@ void allele_maps(const std::vector<std::string>& names, const std::vector<std::s
 }
 
 // ---- the notes: the first nine columns of every record line ---------------------------------------------------------------------------
+// (the line loop is this program's own, not scan_text: the header is copied to the output as its bytes, so its length is kept; N is the
+// #CHROM line's tab count, no name is read; and once a record has been seen every line that is not empty is a record, '#' or not)
 void Run::notes_text() {
     const char* const t0 = (const char*)raw.data();
     const char* p = t0; const char* const end = p + raw.size();
@@ -342,11 +328,11 @@ void Run::notes_text() {
         in_header = false;
         if (le == p) { p = next; continue; }
         const size_t i = notes.size();                                  // the record's index: its TSV line
-        const char* c[10]; int nc = 0; c[0] = p;
-        for (const char* q = p; q < le && nc < 9; q++) if (*q == '\t') c[++nc] = q + 1;
+        const char* c[10]; int nc;
+        nine_columns(p, le, c, nc);
         Note n;
         if (nc < 7) die("Record %zu has fewer than 8 columns.", i + 1);
-        n.pos = atoll(std::string(c[1], c[2] - 1).c_str());
+        n.pos = pos_column(c, nc);
         const long long pos = (long long)n.pos;
         auto col_end = [&](int k) { return k < nc ? c[k + 1] - 1 : le; };
         if (i >= tsv.size()) { notes.push_back(n); p = next; continue; }  // (the count is compared behind the loop)
@@ -383,16 +369,9 @@ void Run::notes_text() {
         }
         if (nc >= 8) {
             fx += '\t'; fx.append(c[8], col_end(8));
-            int k = 0; const char* b = c[8]; const char* const fe = col_end(8);
-            for (const char* q = b;; q++)
-                if (q == fe || *q == ':') {
-                    if (q - b == 2 && b[0] == 'G' && b[1] == 'L' && n.rec.k[0] < 0) n.rec.k[0] = (int16_t)k;
-                    if (q - b == 2 && b[0] == 'P' && b[1] == 'L' && n.rec.k[1] < 0) n.rec.k[1] = (int16_t)k;
-                    if (q - b == 2 && b[0] == 'G' && b[1] == 'P' && n.rec.k[2] < 0) n.rec.k[2] = (int16_t)k;
-                    if (++k > INT16_MAX) die("The record at position %lld has too many FORMAT fields.", pos);
-                    if (q == fe) break;
-                    b = q + 1;
-                }
+            int n_fields = 0;
+            for (int f = 0; f < sal::NF; f++) n.rec.k[f] = (int16_t)format_key_index(c[8], col_end(8), FIELD_NAME[f], &n_fields);
+            if (n_fields > INT16_MAX) die("The record at position %lld has too many FORMAT fields.", pos);
         }
         if (nc >= 9) {
             fx += '\t';
@@ -416,7 +395,6 @@ void Run::notes_bcf() {
     header_bytes = c.off;
     N = (int64_t)v.samples.size();
     std::vector<int32_t> iv; std::vector<std::string> names;
-    auto width = [](int ty) { return ty == 1 ? 1 : ty == 2 ? 2 : (ty == 3 || ty == 5) ? 4 : ty == 7 ? 1 : 0; };
     while (c.off < c.size) {
         const size_t i = bnotes.size();
         BcfRecAt at; int ty, n;
@@ -428,13 +406,13 @@ void Run::notes_bcf() {
         const long long pos = (long long)bn.pos;
         if ((int64_t)(nfs & 0xFFFFFF) != N) die("Record at position %lld has %u samples, the header names %lld samples.", pos, nfs & 0xFFFFFF, (long long)N);
         auto skip = [&](size_t k) { if (c.off + k > at.shared_end) c.fail("BCF record: shared block length mismatch at position %lld", pos); c.off += k; };
-        const size_t id_at = c.off; c.typed(ty, n); skip((size_t)width(ty) * n);
+        const size_t id_at = c.off; c.typed(ty, n); skip((size_t)bcf_type_width(ty) * n);
         const size_t id_end = c.off;
         names.clear();
         for (int a = 0; a < n_allele; a++) { c.typed(ty, n); if (ty != 7 || c.off + n > at.shared_end) c.fail("BCF: allele string expected"); names.push_back(c.str(n)); }
-        const size_t filt_at = c.off; c.typed(ty, n); skip((size_t)width(ty) * n);
+        const size_t filt_at = c.off; c.typed(ty, n); skip((size_t)bcf_type_width(ty) * n);
         const size_t filt_end = c.off;
-        if (i >= tsv.size()) { for (int k = 0; k < n_info; k++) { c.typed(ty, n); skip((size_t)width(ty) * n); c.typed(ty, n); skip((size_t)width(ty) * n); }
+        if (i >= tsv.size()) { for (int k = 0; k < n_info; k++) { c.typed(ty, n); skip((size_t)bcf_type_width(ty) * n); c.typed(ty, n); skip((size_t)bcf_type_width(ty) * n); }
                                c.off = at.rec_end; bnotes.push_back(bn); continue; }     // (the count is compared behind the loop)
         const std::vector<std::string>& tgt = tsv[i];
         const int n_old = (int)names.size(), n_new = (int)tgt.size();
@@ -443,12 +421,12 @@ void Run::notes_bcf() {
         std::string info; bool has_end = false;
         for (int k = 0; k < n_info; k++) {
             const size_t e_at = c.off;
-            c.typed(ty, n); if (c.off + (size_t)width(ty) * n > at.shared_end) c.fail("truncated BCF record"); c.ints(ty, n, iv);
+            c.typed(ty, n); if (c.off + (size_t)bcf_type_width(ty) * n > at.shared_end) c.fail("truncated BCF record"); c.ints(ty, n, iv);
             const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
             if (key == d.dict.end()) c.fail("BCF: undefined INFO key");
             const size_t val_at = c.off;
             c.typed(ty, n);
-            const size_t data_at = c.off; skip((size_t)width(ty) * n);
+            const size_t data_at = c.off; skip((size_t)bcf_type_width(ty) * n);
             if (key->second == "END") has_end = true;
             if (key->second != "QS") { info.append((const char*)raw.data() + e_at, c.off - e_at); continue; }
             if (ty != 5) die("INFO/QS at position %lld is not a float vector.", pos);
@@ -471,15 +449,17 @@ void Run::notes_bcf() {
         for (int b2 = 0, h = 0; b2 < n_new; b2++) for (int b1 = 0; b1 <= b2; b1++, h++) n2o[h] = (int8_t)vgl_setal::alleles2gt(new2old[b1], new2old[b2]);
         bn.rec.n2o = sal::pack_o2n(n2o);
         bn.rec.n_old_g = (int8_t)(n_old * (n_old + 1) / 2); bn.rec.n_new_g = (int8_t)(n_new * (n_new + 1) / 2);
+        // (the loop is this program's own, not bcf_format_fields: a field ends with the record here, not with the file, the key's bytes
+        // are held to that end as well, and where every field starts is kept for the copy)
         for (int k = 0; k < n_fmt; k++) {
             BField bf; bf.at = c.off;
-            c.typed(ty, n); if (c.off + (size_t)width(ty) * n > at.rec_end) c.fail("truncated BCF record"); c.ints(ty, n, iv);
+            c.typed(ty, n); if (c.off + (size_t)bcf_type_width(ty) * n > at.rec_end) c.fail("truncated BCF record"); c.ints(ty, n, iv);
             const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
             if (key == d.dict.end()) c.fail("BCF: undefined FORMAT key");
             c.typed(ty, n);
             bf.data_at = c.off;
-            if (c.off + (size_t)width(ty) * n * (size_t)N > at.rec_end) c.fail("truncated BCF record");
-            c.off += (size_t)width(ty) * n * (size_t)N;
+            if (c.off + (size_t)bcf_type_width(ty) * n * (size_t)N > at.rec_end) c.fail("truncated BCF record");
+            c.off += (size_t)bcf_type_width(ty) * n * (size_t)N;
             bf.end = c.off;
             const int f = key->second == "GL" ? sal::F_GL : key->second == "PL" ? sal::F_PL : key->second == "GP" ? sal::F_GP : -1;
             if (f >= 0 && n > 0 && bn.rec.nv[f] == 0) {
@@ -557,21 +537,13 @@ void run_device_bcf(Run& R, std::vector<uint32_t>& planes, std::vector<uint32_t>
         for (int f = 0; f < sal::NF; f++) if (n.rec.nv[f] > 0) b += ((int64_t)R.N * n.rec.nv[f] * sal::type_width(n.rec.ty[f]) + 3) & ~3ll;
         return b;
     };
-    const int64_t MOST = 64ll << 20;
-    std::vector<std::pair<size_t, size_t>> batches;
-    int64_t max_text = 4, max_vals = 1, max_recs = 1;
-    for (size_t j = 0; j < sent.size();) {
-        size_t j1 = j; int64_t t = 0, v = 0;
-        while (j1 < sent.size() && (int64_t)(j1 - j) < R.o.batch) {
-            const BNote& nt = notes[sent[j1]];
-            const int64_t tb = up_bytes(nt), vb = sal::b_plane_vals(nt.rec, R.N);
-            if (j1 > j && (t + tb > MOST || (v + vb) * 4 > MOST)) break;
-            t += tb; v += vb; j1++;
-        }
-        batches.emplace_back(j, j1);
-        max_text = std::max(max_text, t); max_vals = std::max(max_vals, v); max_recs = std::max<int64_t>(max_recs, (int64_t)(j1 - j));
-        j = j1;
-    }
+    const int64_t MOST = 64ll << 20;                                   // of staged bytes up, and of plane values x 4 down
+    const BatchPlan plan = plan_batches(sent.size(), R.o.batch, {MOST, MOST}, [&](size_t j, size_t c) {
+        const BNote& nt = notes[sent[j]];
+        return c == 0 ? up_bytes(nt) : sal::b_plane_vals(nt.rec, R.N) * 4;
+    });
+    const std::vector<std::pair<size_t, size_t>>& batches = plan.ranges;
+    const int64_t max_text = std::max<int64_t>(4, plan.max_cost[0]), max_vals = std::max<int64_t>(1, plan.max_cost[1] / 4), max_recs = std::max<int64_t>(1, plan.max_recs);
     char err[256];
     R.dev = sal_dev_create(R.o.device, (int32_t)R.N, (int32_t)max_recs, max_text, max_vals, err, sizeof err);
     if (!R.dev) R.stop_run("--on-device 1: %s (device %d; --on-device 0 works on the host)", err, R.o.device);

@@ -9,6 +9,7 @@
 
 #include "../../../include/vcfgl_hip.h"
 #include "sal_dev.h"
+#include "batch_dev.hip.h"
 
 namespace {
 
@@ -83,110 +84,67 @@ __global__ void __launch_bounds__(NT) k_sal_bcf_apply(const BArgs A) {
 
 }  // namespace
 
-// ---- the handle --------------------------------------------------------------------------------------------------------------
-struct SalSlot {
-    uint8_t* h_text = nullptr; sal::BRec* h_recs = nullptr;             // page-locked staging (vgl_host_alloc_on)
-    int32_t* h_status = nullptr; uint32_t* h_planes = nullptr;         // h_status: n status words, n over words, n PL widths
-    uint8_t* d_text = nullptr; sal::BRec* d_recs = nullptr;
-    uint32_t* d_planes = nullptr; uint32_t* d_work = nullptr; int32_t* d_status = nullptr;
-    hipEvent_t done = nullptr;
-    int32_t n_recs = 0; bool busy = false;
+// ---- the handle (batch_dev.hip.h) ------------------------------------------------------------------------------------------------
+struct SalDev : batchdev::BatchDev {
+    int32_t N = 0, max_recs = 0; int64_t max_text = 0, max_vals = 0;
+    struct Slot {
+        batchdev::PinMem<uint8_t> h_text; batchdev::PinMem<sal::BRec> h_recs;
+        batchdev::PinMem<int32_t> h_status; batchdev::PinMem<uint32_t> h_planes;      // h_status: n status words, n over words, n PL widths
+        batchdev::DevMem<uint8_t> d_text; batchdev::DevMem<sal::BRec> d_recs;
+        batchdev::DevMem<uint32_t> d_planes, d_work; batchdev::DevMem<int32_t> d_status;
+    } slot[2];
 };
-struct SalDev {
-    int device = 0; int32_t N = 0, max_recs = 0; int64_t max_text = 0, max_vals = 0;
-    hipStream_t stream = nullptr;
-    SalSlot slot[2];
-    char err[256] = {0};
-};
-
-static int sal_fail(SalDev* d, const char* what, hipError_t e) {
-    snprintf(d->err, sizeof d->err, "%s: %s", what, hipGetErrorString(e));
-    return -1;
-}
-#define SAL_HIP(d, call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return sal_fail(d, #call, e_); } while (0)
 
 const char* sal_dev_error(SalDev* d) { return d->err; }
 
-static int sal_dev_setup(SalDev* d) {
-    SAL_HIP(d, hipSetDevice(d->device));
-    SAL_HIP(d, hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    const size_t R = (size_t)d->max_recs, V = (size_t)d->max_vals;
-    for (SalSlot& s : d->slot) {
-        auto pinned = [&](size_t bytes) { return vgl_host_alloc_on(d->device, bytes ? bytes : 1); };
-        s.h_text = (uint8_t*)pinned((size_t)d->max_text); s.h_recs = (sal::BRec*)pinned(R * sizeof(sal::BRec));
-        s.h_status = (int32_t*)pinned(3 * R * 4); s.h_planes = (uint32_t*)pinned(V * 4);
-        if (!s.h_text || !s.h_recs || !s.h_status || !s.h_planes) {
-            snprintf(d->err, sizeof d->err, "page-locked host memory could not be allocated: %s", vgl_last_error());
-            return -1;
-        }
-        SAL_HIP(d, hipMalloc((void**)&s.d_text, (size_t)d->max_text + 16));
-        SAL_HIP(d, hipMalloc((void**)&s.d_recs, R * sizeof(sal::BRec)));
-        SAL_HIP(d, hipMalloc((void**)&s.d_planes, (V ? V : 1) * 4));
-        SAL_HIP(d, hipMalloc((void**)&s.d_work, (V ? V : 1) * 4));
-        SAL_HIP(d, hipMalloc((void**)&s.d_status, 3 * R * 4));
-        SAL_HIP(d, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    }
-    return 0;
-}
-
 SalDev* sal_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int64_t max_vals, char* err, size_t err_len) {
-    auto refuse = [&](const char* why) { snprintf(err, err_len, "%s", why); return (SalDev*)nullptr; };
-    if (n_samples < 0 || max_recs <= 0 || max_text < 0 || max_vals < 0) return refuse("bad batch shape");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return refuse("no HIP device is available");
-    if (device < 0 || device >= nd) return refuse("no such device");
-    SalDev* d = new SalDev();
-    d->device = device; d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->max_vals = max_vals;
-    if (sal_dev_setup(d) != 0) { snprintf(err, err_len, "%s", d->err); sal_dev_destroy(d); return nullptr; }
-    return d;
+    if (n_samples < 0 || max_recs <= 0 || max_text < 0 || max_vals < 0) { snprintf(err, err_len, "bad batch shape"); return nullptr; }
+    return batchdev::create<SalDev>(device, err, err_len, [&](SalDev* d) {
+        d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->max_vals = max_vals;
+        const size_t R = (size_t)d->max_recs, V = (size_t)d->max_vals;
+        for (SalDev::Slot& s : d->slot) {
+            bool ok = s.h_text.alloc(d->device, (size_t)d->max_text); ok &= s.h_recs.alloc(d->device, R * sizeof(sal::BRec));
+            ok &= s.h_status.alloc(d->device, 3 * R * 4); ok &= s.h_planes.alloc(d->device, V * 4);
+            if (!ok) return d->no_pinned();
+            BATCH_HIP(d, s.d_text.alloc((size_t)d->max_text + 16));
+            BATCH_HIP(d, s.d_recs.alloc(R * sizeof(sal::BRec)));
+            BATCH_HIP(d, s.d_planes.alloc((V ? V : 1) * 4));
+            BATCH_HIP(d, s.d_work.alloc((V ? V : 1) * 4));
+            BATCH_HIP(d, s.d_status.alloc(3 * R * 4));
+        }
+        return 0;
+    });
 }
 
 uint8_t* sal_dev_text(SalDev* d, int slot) { return d->slot[slot & 1].h_text; }
 sal::BRec* sal_dev_brecs(SalDev* d, int slot) { return d->slot[slot & 1].h_recs; }
 
 int sal_dev_submit(SalDev* d, int slot, int32_t n_recs, int64_t text_bytes, int64_t vals) {
-    SalSlot& s = d->slot[slot & 1];
-    if (s.busy || n_recs < 0 || n_recs > d->max_recs || text_bytes < 0 || text_bytes > d->max_text || vals < 0 || vals > d->max_vals) {
-        snprintf(d->err, sizeof d->err, "a batch outside the shape the handle was made for, or a slot still in flight");
-        return -1;
-    }
-    s.n_recs = n_recs; s.busy = true;
+    SalDev::Slot& s = d->slot[slot & 1];
+    if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && text_bytes >= 0 && text_bytes <= d->max_text && vals >= 0 && vals <= d->max_vals) != 0) return -1;
     if (n_recs == 0) return 0;
     hipStream_t st = d->stream;
     const size_t R = (size_t)n_recs;
-    if (text_bytes > 0) SAL_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
-    SAL_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(sal::BRec), hipMemcpyHostToDevice, st));
-    SAL_HIP(d, hipMemsetAsync(s.d_status, 0, 3 * R * 4, st));
-    const BArgs B{s.d_text, text_bytes, s.d_recs, n_recs, d->N, s.d_planes, s.d_work, vals, s.d_status, s.d_status + R, s.d_status + 2 * R};
+    if (text_bytes > 0) BATCH_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
+    BATCH_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(sal::BRec), hipMemcpyHostToDevice, st));
+    BATCH_HIP(d, hipMemsetAsync(s.d_status, 0, 3 * R * 4, st));
+    const BArgs B{s.d_text, text_bytes, s.d_recs, n_recs, d->N, s.d_planes, s.d_work, vals, s.d_status, s.d_status.p + R, s.d_status.p + 2 * R};
     hipLaunchKernelGGL(k_sal_bcf_apply, dim3((unsigned)n_recs, sal::NF), dim3(NT), 0, st, B);
-    SAL_HIP(d, hipGetLastError());
-    SAL_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, 3 * R * 4, hipMemcpyDeviceToHost, st));
-    if (vals > 0) SAL_HIP(d, hipMemcpyAsync(s.h_planes, s.d_planes, (size_t)vals * 4, hipMemcpyDeviceToHost, st));
-    SAL_HIP(d, hipEventRecord(s.done, st));
-    return 0;
+    BATCH_HIP(d, hipGetLastError());
+    BATCH_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, 3 * R * 4, hipMemcpyDeviceToHost, st));
+    if (vals > 0) BATCH_HIP(d, hipMemcpyAsync(s.h_planes, s.d_planes, (size_t)vals * 4, hipMemcpyDeviceToHost, st));
+    return d->end_submit(slot);
 }
 
 int sal_dev_wait(SalDev* d, int slot, SalBatchOut* out) {
-    SalSlot& s = d->slot[slot & 1];
-    if (!s.busy) { snprintf(d->err, sizeof d->err, "nothing in flight in this slot"); return -1; }
-    s.busy = false;
-    if (s.n_recs > 0) SAL_HIP(d, hipEventSynchronize(s.done));
-    for (int32_t i = 0; i < s.n_recs; i++)                             // a sample whose PL cast would overflow: the record is the host's
-        if (s.h_status[i] == sal::ST_OK && s.h_status[s.n_recs + i]) s.h_status[i] = sal::ST_RANGE;
-    out->status = s.h_status; out->planes = s.h_planes; out->width = s.h_status + 2 * (size_t)s.n_recs;
+    SalDev::Slot& s = d->slot[slot & 1];
+    if (d->begin_wait(slot) != 0) return -1;
+    const int32_t n = d->head[slot & 1].n_recs;
+    for (int32_t i = 0; i < n; i++)                                    // a sample whose PL cast would overflow: the record is the host's
+        if (s.h_status[i] == sal::ST_OK && s.h_status[n + i]) s.h_status[i] = sal::ST_RANGE;
+    out->status = s.h_status; out->planes = s.h_planes; out->width = s.h_status.p + 2 * (size_t)n;
     return 0;
 }
 
-void sal_dev_quiesce(SalDev* d) { if (d && d->stream) (void)hipStreamSynchronize(d->stream); }
-
-void sal_dev_destroy(SalDev* d) {
-    if (!d) return;
-    sal_dev_quiesce(d);
-    for (SalSlot& s : d->slot) {
-        for (void* p : {(void*)s.h_text, (void*)s.h_recs, (void*)s.h_status, (void*)s.h_planes}) if (p) vgl_host_free(p);
-        for (void* p : {(void*)s.d_text, (void*)s.d_recs, (void*)s.d_planes, (void*)s.d_work, (void*)s.d_status}) if (p) (void)hipFree(p);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    delete d;
-}
+void sal_dev_quiesce(SalDev* d) { if (d) d->quiesce(); }
+void sal_dev_destroy(SalDev* d) { batchdev::destroy(d); }
