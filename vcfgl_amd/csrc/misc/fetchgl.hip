@@ -190,15 +190,15 @@ FglDev* fgl_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t 
 uint8_t* fgl_dev_text(FglDev* d, int slot) { return d->slot[slot & 1].h_text; }
 fgl::Rec* fgl_dev_recs(FglDev* d, int slot) { return d->slot[slot & 1].h_recs; }
 
-int fgl_dev_submit(FglDev* d, int slot, int32_t n_recs, int64_t text_bytes, int bcf) {
+// the copies of a batch up and its launch sequence; text [text_bytes] is what the parser reads (the slot's staging, or a resident file)
+static int submit_on(FglDev* d, int slot, int32_t n_recs, const uint8_t* staged, const uint8_t* text, int64_t text_bytes, int bcf) {
     FglDev::Slot& s = d->slot[slot & 1];
-    if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && text_bytes >= 0 && text_bytes <= d->max_text) != 0) return -1;
     if (n_recs == 0) return 0;
     hipStream_t st = d->stream;
     const size_t R = (size_t)n_recs;
-    if (text_bytes > 0) BATCH_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
+    if (staged && text_bytes > 0) BATCH_HIP(d, hipMemcpyAsync(s.d_text, staged, (size_t)text_bytes, hipMemcpyHostToDevice, st));
     BATCH_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(fgl::Rec), hipMemcpyHostToDevice, st));
-    const ParseArgs P{s.d_text, text_bytes, s.d_recs, n_recs, d->N, s.d_plane, s.d_status};
+    const ParseArgs P{text, text_bytes, s.d_recs, n_recs, d->N, s.d_plane, s.d_status};
     if (bcf) hipLaunchKernelGGL(k_fgl_pick, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
     else hipLaunchKernelGGL(k_fgl_parse, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
     BATCH_HIP(d, hipGetLastError());
@@ -212,6 +212,17 @@ int fgl_dev_submit(FglDev* d, int slot, int32_t n_recs, int64_t text_bytes, int 
     BATCH_HIP(d, hipMemcpyAsync(s.h_off, s.d_off, (R + 1) * 8, hipMemcpyDeviceToHost, st));
     BATCH_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, R * 4, hipMemcpyDeviceToHost, st));
     return d->end_submit(slot);
+}
+
+int fgl_dev_submit(FglDev* d, int slot, int32_t n_recs, int64_t text_bytes, int bcf) {
+    FglDev::Slot& s = d->slot[slot & 1];
+    if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && text_bytes >= 0 && text_bytes <= d->max_text) != 0) return -1;
+    return submit_on(d, slot, n_recs, s.h_text, s.d_text, text_bytes, bcf);
+}
+
+int fgl_dev_submit_resident(FglDev* d, int slot, int32_t n_recs, const uint8_t* d_text, int64_t text_bytes) {
+    if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && d_text && text_bytes >= 0) != 0) return -1;
+    return submit_on(d, slot, n_recs, nullptr, d_text, text_bytes, 0);
 }
 
 int fgl_dev_wait(FglDev* d, int slot, FglBatchOut* out) {

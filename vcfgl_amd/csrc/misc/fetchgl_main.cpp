@@ -1,8 +1,14 @@
 // fetchgl_main.cpp -- fetchgl_hip: the reference's misc/fetchGl (one genotype's FORMAT/GL of every sample, as CSV) for this platform.
 //   fetchgl_hip -i file -gt XY [-o out.csv] [--on-device 0|1] [--device INT] [--batch-records INT] [--messages 0|1] [--verbose 0|1]
-// The file is read whole (plain, gzip or bgzip text through zlib, or BCF inside either).  The host finds the records, reads the first
-// nine columns of each (for BCF: the shared block and the FORMAT field headers), finds GL and the genotype's index g, and keeps a small
-// note per record.  The records that get a CSV line are then read by the rules of fgl_core.h -- on the device in batches
+//               [--device-inflate 0|1] [--resident 0|1] [--resident-max-bytes INT]
+// The file is read whole (plain, gzip or bgzip text through zlib, or BCF inside either; --device-inflate 1: BGZF members on the GPU,
+// record_file.h).  --resident 1 (with --device-inflate 1 and --on-device 1): a BGZF file of VCF text is inflated into device memory
+// and stays there (resident_file.h) -- the device finds the lines, only their heads (the first nine columns) come down for the notes
+// below, and the batches' descriptors point into the resident text; a record the device hands back has its sample columns copied
+// down for the strtod reader.  Whatever keeps the file from being resident (not BGZF, a member left to the host, BCF, too large, a
+// line whose ninth tab is too far, too many lines) is named in the [input] line, and the run goes on as with --resident 0.
+// The host finds the records, reads the first nine columns of each (for BCF: the shared block and the FORMAT field headers), finds GL
+// and the genotype's index g, and keeps a small note per record.  The records that get a CSV line are then read by the rules of fgl_core.h -- on the device in batches
 // (--on-device 1: fetchgl.hip) or by the same routines on the host (--on-device 0) -- and a record those rules hand back (a token
 // outside the device grammar, a value index outside the record's values, a wrong column count) is redone whole by the strtod reader
 // below, which owns every message.  Both paths therefore write the same bytes.  A run that has to stop does so at the record where the
@@ -10,12 +16,15 @@
 #include "record_file.h"
 #include "batch_plan.h"
 #include "fgl_dev.h"
+#include "resident_file.h"
 
 namespace {
 
 struct Opt {
     std::string in, gt, out;
     int on_device = 1, device = 0, batch = 4096, messages = 1, verbose = 0;
+    int device_inflate = 0, resident = 0;
+    int64_t resident_max = -1;         // --resident-max-bytes (-1: the device's free memory less 1 GiB)
 };
 
 const char FGL_USAGE[] =
@@ -30,6 +39,11 @@ const char FGL_USAGE[] =
     "  --batch-records INT [4096] records per device batch (and no more than 64 MiB of text in one)\n"
     "  --messages 0|1 [1]        the tool's per-record lines on stderr\n"
     "  --verbose 0|1 [0]         record counts, bytes sent up and received, stage times\n"
+    "  --device-inflate 0|1 [0]  " DEVICE_INFLATE_HELP "\n"
+    "  --resident 0|1 [0]        1: a BGZF file of VCF text stays in GPU memory once inflated: the GPU finds the lines, their first nine\n"
+    "                            columns alone come down, the sample columns are parsed where they lie (needs --device-inflate 1 and\n"
+    "                            --on-device 1; any other file is read as with 0, the reason is in the [input] line of --verbose 1)\n"
+    "  --resident-max-bytes INT  the most bytes, inflated and compressed together, a resident file may take [the GPU's free memory less 1 GiB]\n"
     "  -h, --help                print help\n\n";
 
 Opt parse_opt(int argc, char** argv) {
@@ -48,11 +62,19 @@ Opt parse_opt(int argc, char** argv) {
         else if (!strcmp(a, "--batch-records")) o.batch = option_int(a, v, 1, 1 << 24);
         else if (!strcmp(a, "--messages")) o.messages = option_int(a, v, 0, 1);
         else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--device-inflate")) o.device_inflate = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--resident")) o.resident = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--resident-max-bytes")) {
+            char* e; const long long x = strtoll(v, &e, 10);
+            if (e == v || *e || x < 0) die("%s takes an integer of at least 0, not '%s'", a, v);
+            o.resident_max = x;
+        }
         else die("Unknown arg:%s", a);
     }
     if (o.in.empty()) die("Input file not specified. Exiting...");
     if (o.gt.empty()) die("Genotype to fetch not specified. Exiting...");
     if (o.gt.size() != 2) die("A genotype is exactly two characters, not '%s'.", o.gt.c_str());
+    if (o.resident && !(o.device_inflate && o.on_device)) die("--resident 1 needs --device-inflate 1 and --on-device 1.");
     return o;
 }
 
@@ -79,6 +101,8 @@ struct Run {
     FILE* out_fp = nullptr;
     std::string csv_buf, msg_buf;
     FglDev* dev = nullptr;
+    RfFile* rf = nullptr;              // --resident 1: the file's text in device memory (raw is then the head stream)
+    rf::Split split;
     long n_lines = 0, n_host = 0; int64_t up = 0, down = 0;
     double t_read = 0, t_nine = 0, t_dev = 0, t_host = 0;
 
@@ -107,15 +131,23 @@ struct Run {
         for (int64_t s = 0; s < N; s++) { vgl_fetchgl::Emit<true> e{b, 0u, (uint32_t)sizeof b}; fgl::put_value(e, plane[s], s == N - 1); csv_buf.append((const char*)b, e.n); }
         n_lines++;
     }
-    void record_strtod(const Note& n, std::vector<uint32_t>& plane);
+    void record_strtod(const Note& n, const char* t, std::vector<uint32_t>& plane);
+    // a record for the strtod reader: its sample columns where the host holds them, or copied down from the resident text
+    void record_redo(const Note& n, std::vector<uint32_t>& plane) {
+        if (!rf) { record_strtod(n, (const char*)raw.data() + n.off, plane); return; }
+        std::vector<uint8_t> cols((size_t)n.len + 1);
+        if (rf_fetch(rf, n.off, n.len, cols.data()) != 0) stop_run("--resident 1: %s", rf_error(rf));
+        record_strtod(n, (const char*)cols.data(), plane);
+    }
+    bool load_resident(FileReader& reader);
     void record_host(const Note& n, std::vector<uint32_t>& plane);
     void notes_text();
     void notes_bcf();
 };
 
 // ---- the strtod reader: one record of VCF text by the tool's own reading of its values, with the run's messages ---------------------
-void Run::record_strtod(const Note& n, std::vector<uint32_t>& plane) {
-    const char* const t = (const char*)raw.data() + n.off; const char* const end = t + n.len;
+void Run::record_strtod(const Note& n, const char* const t, std::vector<uint32_t>& plane) {
+    const char* const end = t + n.len;
     const long long pos = (long long)n.pos;
     const int32_t g = n.g();
     std::vector<std::pair<const char*, const char*>> field;            // the GL field of every column (empty pair: one missing value)
@@ -170,7 +202,7 @@ void Run::record_host(const Note& n, std::vector<uint32_t>& plane) {
     const int st = fgl::record_plain(raw.data(), r, N, plane.data(), nullptr);
     if (st == fgl::ST_OK) { put_line(n, plane.data()); return; }
     if (st == fgl::ST_HOST) n_host++;
-    record_strtod(n, plane);
+    record_redo(n, plane);
     if (st == fgl::ST_RANGE) stop_run("The record at position %lld was refused by the column rules and taken by the strtod reader.", (long long)n.pos);
 }
 
@@ -194,7 +226,9 @@ void Run::notes_text() {
     const bool defined = header_defines_gl(header, nullptr);
     char msg[256];
     notes.reserve(lines.size());
+    size_t ln = 0;                                                     // --resident 1: raw is the head stream, and record i is line ln of the file
     for (size_t i = 0; i < lines.size(); i++) {
+        if (rf) while (split.hoff[ln] < lines[i].first) ln++;
         const char* lb = t0 + lines[i].first; const char* le = t0 + lines[i].second;
         const char* col_at[10]; int nc;
         nine_columns(lb, le, col_at, nc);
@@ -215,11 +249,58 @@ void Run::notes_text() {
                 if (e == alt_end) break;
                 b = e + 1;
             }
-        n.off = col_at[9] - t0;
-        if (le - col_at[9] > INT32_MAX) { snprintf(msg, sizeof msg, "The record at position %lld is longer than 2 GiB.", (long long)n.pos); stop = msg; return; }
-        n.len = (int32_t)(le - col_at[9]);
+        n.off = rf ? split.s_off[ln] : col_at[9] - t0;
+        const int64_t len = rf ? split.s_len[ln] : le - col_at[9];
+        if (len > INT32_MAX) { snprintf(msg, sizeof msg, "The record at position %lld is longer than 2 GiB.", (long long)n.pos); stop = msg; return; }
+        n.len = (int32_t)len;
         notes.push_back(n);
     }
+}
+
+// --resident 1: the file into device memory and its split (resident_file.h).  true: the file is resident and raw is its head stream;
+// false: raw holds the file's bytes as --resident 0 reads them, and the [input] line says why
+bool Run::load_resident(FileReader& reader) {
+    char err[256];
+    { FILE* fp = fopen(o.in.c_str(), "rb"); if (!fp) die("Could not open file: %s", o.in.c_str()); fclose(fp); }   // the file first, as without the flag
+    rf = rf_create(o.device, err, sizeof err);
+    if (!rf) die("--resident 1: %s (device %d)", err, o.device);
+    const int64_t most = o.resident_max >= 0 ? o.resident_max : rf_default_max_bytes(rf);
+    auto failed = [&]() { const std::string why = rf_error(rf); if (why.compare(0, 14, "Could not open") == 0) die("%s", why.c_str()); die("--resident 1: %s", why.c_str()); };
+    RfWhy why;
+    if (rf_load(rf, o.in.c_str(), most, &why) != 0) failed();
+    const char* reason = nullptr;
+    bool have = false;                                                 // raw was copied down from the device
+    if (why == RF_NOT_BGZF) reason = "the file is not a series of BGZF members";
+    else if (why == RF_MEMBER_HOST) reason = "a member was left to the host (VGL_INFLATE_HOST)";
+    else if (why == RF_TOO_LARGE) reason = "the inflated and the compressed bytes exceed --resident-max-bytes";
+    else {
+        const int64_t total = rf_total(rf);
+        uint8_t first[3] = {0, 0, 0};
+        if (rf_fetch(rf, 0, std::min<int64_t>(3, total), first) != 0) failed();
+        bool more_lines = false;
+        if (total >= 3 && !memcmp(first, "BCF", 3)) reason = "the file is BCF";
+        else {
+            if (rf_split(rf, rf::RF_HEAD_MOST, &split, &more_lines) != 0) failed();
+            if (more_lines) reason = "the file has more lines than the offsets scan takes (INT32_MAX - 1024)";
+            else if (split.over) reason = "a line's ninth tab is not within RF_HEAD_MOST bytes";
+        }
+        if (reason) {                                                  // the inflated bytes are on the device: they come down whole
+            raw.resize((size_t)total);
+            if (rf_fetch(rf, 0, total, raw.data()) != 0) failed();
+            have = true;
+        }
+    }
+    const RfStats st = *rf_stats(rf);
+    if (o.verbose) {
+        fprintf(stderr, "[input] %s: resident %d%s%s%s, RF_CHUNK %lld, members %lld, lines %lld, head bytes received %lld, compressed bytes sent up %lld; upload %.3f s, inflate %.3f s, split %.3f s\n",
+                o.in.c_str(), reason ? 0 : 1, reason ? " (" : "", reason ? reason : "", reason ? ")" : "", (long long)rf::RF_CHUNK, (long long)st.members, (long long)st.lines,
+                (long long)st.head_bytes, (long long)st.compressed_up, st.t_upload, st.t_inflate, st.t_split);
+        if (have) FileReader::report(o.in, (long)st.members, st.compressed_up, st.total, st.t_inflate, nullptr);
+    }
+    if (!reason) { raw = std::move(split.heads); return true; }
+    rf_destroy(rf); rf = nullptr; split = rf::Split();
+    if (!have) raw = reader.read(o.in);
+    return false;
 }
 
 // BCF: the shared block -> POS and the alleles; the FORMAT field headers -> where GL's vectors lie
@@ -261,7 +342,8 @@ void run_device(Run& R, std::vector<uint32_t>& plane) {
     const std::vector<Note>& notes = R.notes;
     std::vector<size_t> sent;
     for (size_t i = 0; i < notes.size(); i++) if (notes[i].line()) sent.push_back(i);
-    auto bytes_of = [&](const Note& n) { return R.bcf ? ((int64_t)R.N * n.len * 4) : (int64_t)n.len; };
+    // (--resident 1: the text is on the device already, a batch stages descriptors alone)
+    auto bytes_of = [&](const Note& n) { return R.rf ? (int64_t)0 : R.bcf ? ((int64_t)R.N * n.len * 4) : (int64_t)n.len; };
     // a batch: at most --batch-records records, 64 MiB of CSV bound and 64 MiB of text (one record at least)
     const int64_t TEXT_MOST = 64ll << 20;
     const int64_t B = std::max<int64_t>(1, std::min<int64_t>(R.o.batch, TEXT_MOST / fgl_dev_line_bound((int32_t)R.N)));
@@ -279,11 +361,12 @@ void run_device(Run& R, std::vector<uint32_t>& plane) {
         for (size_t j = batches[b].first; j < batches[b].second; j++, n++) {
             const Note& nt = notes[sent[j]];
             fgl::Rec r; memset(&r, 0, sizeof r);
-            r.off = at; r.len = nt.len; r.k = nt.k; r.g = nt.g(); r.pos = nt.pos;
-            memcpy(text + at, R.raw.data() + nt.off, (size_t)bytes_of(nt)); at += bytes_of(nt);
+            r.off = R.rf ? nt.off : at; r.len = nt.len; r.k = nt.k; r.g = nt.g(); r.pos = nt.pos;
+            if (!R.rf) { memcpy(text + at, R.raw.data() + nt.off, (size_t)bytes_of(nt)); at += bytes_of(nt); }
             recs[n] = r;
         }
-        if (fgl_dev_submit(R.dev, slot, n, at, R.bcf ? 1 : 0) != 0) R.stop_run("--on-device 1: %s", fgl_dev_error(R.dev));
+        const int rc = R.rf ? fgl_dev_submit_resident(R.dev, slot, n, rf_device_text(R.rf), rf_total(R.rf)) : fgl_dev_submit(R.dev, slot, n, at, R.bcf ? 1 : 0);
+        if (rc != 0) R.stop_run("--on-device 1: %s", fgl_dev_error(R.dev));
         R.up += at + (int64_t)n * (int64_t)sizeof(fgl::Rec); R.t_dev += now_s() - t0;
     };
     size_t cur = 0;                                                    // the next record in file order
@@ -300,7 +383,7 @@ void run_device(Run& R, std::vector<uint32_t>& plane) {
             if (out.status[n] == fgl::ST_OK) { R.csv_buf.append((const char*)out.csv + out.off[n], (size_t)(out.off[n + 1] - out.off[n])); R.n_lines++; }
             else {
                 if (out.status[n] == fgl::ST_HOST) R.n_host++;
-                R.record_strtod(nt, plane);
+                R.record_redo(nt, plane);
                 if (out.status[n] == fgl::ST_RANGE) R.stop_run("The record at position %lld was refused by the column rules and taken by the strtod reader.", (long long)nt.pos);
             }
             R.flush(false);
@@ -319,7 +402,9 @@ int main(int argc, char** argv) {
     R.o = parse_opt(argc, argv);
     const Opt& o = R.o;
     double t0 = now_s();
-    R.raw = read_whole(o.in);
+    FileReader reader; reader.device_inflate = o.device_inflate; reader.device = o.device; reader.verbose = o.verbose;
+    if (o.resident) R.load_resident(reader);
+    else R.raw = reader.read(o.in);
     R.out_fp = o.out.empty() ? stdout : fopen(o.out.c_str(), "w");
     if (!R.out_fp) die("Could not open output file %s for writing", o.out.c_str());
     R.t_read = now_s() - t0; t0 = now_s();
@@ -342,6 +427,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "[fetchgl] on-device %d: records %zu, with a CSV line %ld, redone on the host %ld, bytes sent up %lld, received %lld; read %.3f s, nine columns %.3f s, device %.3f s, host %.3f s\n",
                 o.on_device, R.notes.size(), R.n_lines, R.n_host, (long long)R.up, (long long)R.down, R.t_read, R.t_nine, R.t_dev, R.t_host);
     if (R.dev) fgl_dev_destroy(R.dev);
+    if (R.rf) rf_destroy(R.rf);
     if (R.out_fp != stdout) fclose(R.out_fp);
     fflush(stdout);
     return 0;

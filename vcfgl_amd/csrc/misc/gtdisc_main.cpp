@@ -1,5 +1,5 @@
 // gtdisc_main.cpp -- gtdiscordance_hip: the reference's misc/gtDiscordance (a call file against -printTruth's file) for this platform.
-//   gtdiscordance_hip -t truth -i call -o out [-doGQ 0..8] [-perSite 0|1] [--on-device 0|1] [--device INT] [--batch-records INT] [--verbose 0|1]
+//   gtdiscordance_hip -t truth -i call -o out [-doGQ 0..8] [-perSite 0|1] [--on-device 0|1] [--device INT] [--batch-records INT] [--verbose 0|1] [--device-inflate 0|1]
 // Both files are read whole (plain, gzip or bgzip text through zlib; BCF records are decoded into the same text lines on the host), their
 // first nine columns are parsed on the host and the records matched by the tool's sequential merge on POS.  Every matched pair is then
 // judged by the PLAIN grammar of gtdisc_core.h -- on the device in batches (--on-device 1: gtdisc.hip) or by the same routines on the
@@ -15,7 +15,7 @@ namespace {
 
 struct Opt {
     std::string truth, call, out;
-    int do_gq = 0, per_site = 0, on_device = 1, device = 0, batch = 4096, verbose = 0;
+    int do_gq = 0, per_site = 0, on_device = 1, device = 0, batch = 4096, verbose = 0, device_inflate = 0;
 };
 
 const char GTD_USAGE[] =
@@ -37,6 +37,7 @@ const char GTD_USAGE[] =
     "  --device INT [0]          the GPU\n"
     "  --batch-records INT [4096] call records per device batch\n"
     "  --verbose 0|1 [0]         record counts, bytes sent up and stage times\n"
+    "  --device-inflate 0|1 [0]  " DEVICE_INFLATE_HELP "\n"
     "  -h, --help                print help\n\n";
 
 Opt parse_opt(int argc, char** argv) {
@@ -56,6 +57,7 @@ Opt parse_opt(int argc, char** argv) {
         else if (!strcmp(a, "--device")) o.device = option_int(a, v, 0, 1 << 20);
         else if (!strcmp(a, "--batch-records")) o.batch = option_int(a, v, 1, 1 << 24);
         else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--device-inflate")) o.device_inflate = option_int(a, v, 0, 1);
         else die("Unknown arg:%s", a);
     }
     if (o.call.empty()) die("Input file not specified. Please use -i/--input <file>.");
@@ -128,9 +130,9 @@ void bcf_lines(std::vector<uint8_t>& raw, Input& in) {
     in.text.assign(out.begin(), out.end());
 }
 
-Input read_input_file(const std::string& fn) {
+Input read_input_file(FileReader& reader, const std::string& fn) {
     Input in;
-    std::vector<uint8_t> raw = read_whole(fn);
+    std::vector<uint8_t> raw = reader.read(fn);
     if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) { bcf_lines(raw, in); return in; }
     in.text = std::move(raw);
     TextLines tl = scan_text(in.text);
@@ -416,8 +418,11 @@ int main(int argc, char** argv) {
     R.o = parse_opt(argc, argv);
     const Opt& o = R.o;
     double t0 = now_s();
-    R.truth = read_input_file(o.truth);
-    R.call = read_input_file(o.call);
+    {
+        FileReader reader; reader.device_inflate = o.device_inflate; reader.device = o.device; reader.verbose = o.verbose;
+        R.truth = read_input_file(reader, o.truth);
+        R.call = read_input_file(reader, o.call);
+    }
     R.out_fp = fopen(o.out.c_str(), "w");
     if (!R.out_fp) die("Could not open output file %s for writing", o.out.c_str());
     R.t_read = now_s() - t0; t0 = now_s();

@@ -1,9 +1,44 @@
 // record_file.h -- what the mains of the misc programs share of reading a record file (gtdisc_main.cpp, fetchgl_main.cpp, setal_main.cpp):
 // the lines of VCF text, the first nine columns of a record line, a key's place in the FORMAT column, the FORMAT fields of a BCF record,
-// and the integer options of the command lines.  The file's bytes come from read_whole (host/host_util.h).  Every refusal of a record
-// stays with the program that words it.
+// and the integer options of the command lines.  The file's bytes come from FileReader below: read_whole (host/host_util.h), or the
+// device inflater of vcfgl_hip (--device-inflate 1).  Every refusal of a record stays with the program that words it.
 #pragma once
 #include "../host/vcf_input.h"
+
+// --device-inflate 0|1 of the three programs: how a record file's bytes are read.  0: read_whole, zlib on one host thread.  1: the
+// file as it lies on the disk, its BGZF members inflated on `device` by the reader of vcfgl_hip (inflate_on_device, host/vcf_input.h:
+// 512 members a batch, two batches in flight); zlib stays the specification -- a file that is not a clean series of BGZF members, or
+// of which a member came back VGL_INFLATE_HOST, is read whole by zlib as with 0, so a damaged file gives what it gives today.
+// Without a device the run ends with the library's message.  One reader serves every file of a run (gtdiscordance_hip reads two).
+#define DEVICE_INFLATE_HELP "1: the file's BGZF members are inflated on the GPU (any other file: zlib, as with 0); the one thing that opens the GPU under --on-device 0"
+struct FileReader {
+    int device_inflate = 0, device = 0, verbose = 0;
+    vgl_inflate_host* h = nullptr;
+    FileReader() = default;
+    FileReader(const FileReader&) = delete;
+    FileReader& operator=(const FileReader&) = delete;
+    ~FileReader() { if (h) vgl_inflate_host_destroy(h); }
+
+    // the [input] line of --verbose 1
+    static void report(const std::string& fn, const long members, const int64_t up, const int64_t down, const double t_inflate, const char* fallback) {
+        fprintf(stderr, "[input] %s: device-inflate 1, members inflated on the device %ld, bytes sent up %lld, received %lld, inflate %.3f s, read by the host: %s%s%s\n",
+                fn.c_str(), members, (long long)up, (long long)down, t_inflate, fallback ? "yes (" : "no", fallback ? fallback : "", fallback ? ")" : "");
+    }
+    std::vector<uint8_t> read(const std::string& fn) {
+        if (!device_inflate) return read_whole(fn);
+        InputOpt opt; opt.device_inflate = 1; opt.device = device;
+        opt.inflater = [this]() -> vgl_inflate_host* {
+            if (!h && vgl_inflate_host_create(device, INFLATE_BATCH, &h) != VGL_OK) die("--device-inflate 1: %s", vgl_last_error());
+            return h;
+        };
+        InputStats st;
+        std::vector<uint8_t> raw;
+        const bool done = inflate_on_device(fn, opt, raw, st);
+        if (!done) raw = read_whole(fn);
+        if (verbose) report(fn, done ? st.members_dev : 0, st.inflate_up, done ? st.inflate_down : 0, st.t_inflate, st.fallback);
+        return raw;
+    }
+};
 
 // VCF text: the ## lines, the sample names of the #CHROM line and [begin, end) of every record line; empty lines are skipped
 struct TextLines {

@@ -1,6 +1,7 @@
 // setal_main.cpp -- setalleles_hip: the reference's misc/setAlleles (a record file gets a new REF/ALT list per record from a TSV; INFO/QS
 // and FORMAT GL / PL / GP follow the new allele order and are renormalised) for this platform, on a file that exists on disk.
 //   setalleles_hip -i file -a alleles.tsv [-O b|u|z|v] [-o prefix] [--on-device 0|1] [--device INT] [--batch-records INT] [--threads INT] [--verbose 0|1]
+//                  [--device-inflate 0|1]
 // Both files are read whole (the record file through zlib: plain, gzip or bgzip text, or BCF inside either).  The TSV is checked first, then one pass reads the
 // first nine columns of every record, matches its TSV line, builds oldgt2newgt and the new fixed columns (REF, ALT, INFO with QS
 // permuted) and keeps a note per record; every stop of these two passes comes before the output file is opened.
@@ -21,7 +22,7 @@ namespace {
 struct Opt {
     std::string in, alleles, prefix, out_fn;
     char mode = 'b';
-    int on_device = 1, device = 0, batch = 4096, threads = 1, verbose = 0;
+    int on_device = 1, device = 0, batch = 4096, threads = 1, verbose = 0, device_inflate = 0;
 };
 
 const char SAL_VERSION[] = "0.0.1";
@@ -40,7 +41,8 @@ const char SAL_USAGE[] =
     "    --device INT [0]           the GPU\n"
     "    --batch-records INT [4096] records per device batch (and no more than 64 MiB staged either way in one)\n"
     "    --threads INT [1]          BGZF compression threads of -O z / -O b\n"
-    "    --verbose 0|1 [0]          record counts, bytes sent up and received, stage times\n\n";
+    "    --verbose 0|1 [0]          record counts, bytes sent up and received, stage times\n"
+    "    --device-inflate 0|1 [0]   " DEVICE_INFLATE_HELP "\n\n";
 
 Opt parse_opt(int argc, char** argv) {
     Opt o;
@@ -63,6 +65,7 @@ Opt parse_opt(int argc, char** argv) {
         else if (!strcmp(a, "--batch-records")) o.batch = option_int(a, v, 1, 1 << 24);
         else if (!strcmp(a, "--threads")) o.threads = option_int(a, v, 1, 1024);
         else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--device-inflate")) o.device_inflate = option_int(a, v, 0, 1);
         else die("Unknown arg:%s", a);
     }
     if (o.in.empty()) die("Input file is required. Please provide a record file using the -i flag (e.g. -i input.vcf)");
@@ -601,7 +604,10 @@ int main(int argc, char** argv) {
     const Opt& o = R.o;
     double t0 = now_s();
     R.tsv = load_alleles(o.alleles);
-    R.raw = read_whole(o.in);
+    {
+        FileReader reader; reader.device_inflate = o.device_inflate; reader.device = o.device; reader.verbose = o.verbose;
+        R.raw = reader.read(o.in);
+    }
     R.t_read = now_s() - t0; t0 = now_s();
     R.bcf = R.raw.size() >= 3 && !memcmp(R.raw.data(), "BCF", 3);
     // text is written as text and BCF as BCF: converting between the two would need every INFO / FORMAT field's type, not this program's work

@@ -101,12 +101,13 @@ SETALLELES_PROGRAM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "b
 
 
 def set_file(path, alleles, out_prefix, mode="v", on_device=True, device=None, batch_records=None, threads=None, verbose=False, timeout=3600,
-             env=None):
+             env=None, device_inflate=None):
     """Runs setalleles_hip -i `path` -a `alleles` -O `mode` -o `out_prefix` as a fresh child process under `timeout` seconds
     (subprocess.TimeoutExpired when it runs out) and returns (returncode, stdout, stderr) as text.  The records are in `out_prefix`.vcf
     (mode v) or .vcf.gz (mode z) for VCF text input, in `out_prefix`.bcf (modes u, b) for BCF input.  on_device=True works BCF input on
     the GPU, fails without one and is refused for text input (returncode 1): there is no fallback; on_device=False works on the host
-    and touches no GPU.  A missing program is an error (build the package first)."""
+    and touches no GPU -- unless device_inflate=True, which inflates a BGZF input's members on the GPU (--device-inflate 1; any other
+    file is read by zlib as without it).  A missing program is an error (build the package first)."""
     if not os.path.exists(SETALLELES_PROGRAM):
         raise FileNotFoundError("%s is not built (make -C vcfgl_amd/csrc all)" % SETALLELES_PROGRAM)
     cmd = [SETALLELES_PROGRAM, "-i", str(path), "-a", str(alleles), "-O", str(mode), "-o", str(out_prefix), "--on-device", "1" if on_device else "0"]
@@ -116,6 +117,8 @@ def set_file(path, alleles, out_prefix, mode="v", on_device=True, device=None, b
         cmd += ["--batch-records", str(int(batch_records))]
     if threads is not None:
         cmd += ["--threads", str(int(threads))]
+    if device_inflate is not None:
+        cmd += ["--device-inflate", "1" if device_inflate else "0"]
     if verbose:
         cmd += ["--verbose", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
