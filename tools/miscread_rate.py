@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """End-to-end time of the three misc programs with their input read by zlib (--device-inflate 0), with its BGZF members inflated on the
-device (--device-inflate 1) and, for fetchgl_hip on VCF text, with the inflated text left on the device (--device-inflate 1
---resident 1), on files vcfgl_hip writes: SITES x SAMPLES, C3 flags (depth 20, -e 0.01, --error-qs 2, --beta-variance 1e-5, -GL 2).
+device (--device-inflate 1) and, for fetchgl_hip, with the inflated file left on the device (--device-inflate 1 --resident 1 on VCF
+text, and --resident-bcf 1 beside it on BCF), on files vcfgl_hip writes: SITES x SAMPLES, C3 flags (depth 20, -e 0.01, --error-qs 2, --beta-variance 1e-5, -GL 2).
   fetchgl_hip        -O z and -O b files, --on-device 1, -gt AC, -o FILE
   setalleles_hip     the -O b file of a run with -doUnobserved 4 -addPL 1 -addGP 1 -addQS 1, -O b out, --threads 16, --on-device 1; the
                      TSV cuts every record to REF + 2 ALTs
@@ -9,7 +9,8 @@ device (--device-inflate 1) and, for fetchgl_hip on VCF text, with the inflated 
 MISCREAD_PARENT=dir adds the programs of the parent commit (dir/fetchgl_hip ...; they take no new flag) as a setting of their own.
 Everything is inside the measured wall time, process start included.  The settings alternate, MISCREAD_REPS times each (default 3),
 and are reported as min / median / max with the programs' [input] and stage lines of every run; all settings of a row must write the
-same bytes.  MISCREAD_ONLY=fetchgl,setal,gtdisc picks programs, MISCREAD_MODES=z,b the files of fetchgl_hip.
+same bytes.  MISCREAD_ONLY=fetchgl,setal,gtdisc picks programs, MISCREAD_MODES=z,b the files of fetchgl_hip; the mode `short` is a
+-O b file of many short records: one sample, MISCREAD_SHORT records (default 2^20).
 usage (GPU box): python tools/miscread_rate.py [sites] [samples]"""
 import gzip, hashlib, os, shutil, struct, subprocess, sys, tempfile, time, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +25,8 @@ only = os.environ.get("MISCREAD_ONLY", "fetchgl,setal,gtdisc").split(",")
 d = tempfile.mkdtemp(prefix="miscreadrate")
 C3 = "--seed 42 --depth 20 -e 0.01 --error-qs 2 --beta-variance 1e-5 -GL 2"
 NEW, RES = ["--device-inflate", "1"], ["--device-inflate", "1", "--resident", "1"]
+RES_BCF = RES + ["--resident-bcf", "1"]
+SHORT = int(os.environ.get("MISCREAD_SHORT", str(1 << 20)))
 
 
 def digest(path, inflate):
@@ -61,7 +64,7 @@ def row(title, settings, out_of, tags, inflate=False):
         print("  --device-inflate 0 against the parent commit: " + ("ranges overlap" if max(min(a), min(b)) <= min(max(a), max(b)) else "below" if max(b) < min(a) else "above"), flush=True)
 
 
-def simulate(tag, mode, extra=""):
+def simulate(tag, mode, extra="", S=S, N=N):
     src = os.path.join(d, "in.vcf")
     rng = np.random.default_rng(42)
     tok = np.array(["0|0", "1|0", "0|1", "1|1"])
@@ -87,12 +90,14 @@ def with_parent(program, settings, build):
 
 if "fetchgl" in only:
     for mode in os.environ.get("MISCREAD_MODES", "z,b").split(","):
-        path = simulate("fgl_" + mode, mode)
+        path = simulate("fgl_" + mode, "b", S=SHORT, N=1) if mode == "short" else simulate("fgl_" + mode, mode)
         build = lambda exe, out, extra, path=path: [exe, "-i", path, "-gt", "AC", "-o", out, "--on-device", "1", "--verbose", "1"] + extra
         exe = os.path.join(BINDIR, "fetchgl_hip")
         settings = {"--device-inflate 0": lambda out: build(exe, out, []), "--device-inflate 1": lambda out: build(exe, out, NEW)}
         if mode == "z":
             settings["--device-inflate 1 --resident 1"] = lambda out: build(exe, out, RES)
+        else:
+            settings["--device-inflate 1 --resident 1 --resident-bcf 1"] = lambda out: build(exe, out, RES_BCF)
         row(f"fetchgl_hip, -O {mode} file, --on-device 1:", with_parent("fetchgl_hip", settings, build), lambda out: out, ("[input]", "[fetchgl]"))
         os.remove(path)
 

@@ -8,7 +8,8 @@
 //                 colons, counts the field's values, finds value g and parses it into float bits (END for a count <= g), stored in the
 //                 [record][sample] uint32 plane.  The workgroup then reduces the largest count to n_gls and lane 0 stores the status:
 //                 OK, HOST (a picked token outside the device grammar) or RANGE (g >= n_gls, or a column count other than N).  No atomics.
-//   k_fgl_pick    BCF: a workgroup per record, a lane per sample: value g of the sample's vector into the same plane
+//   k_fgl_pick    BCF: a workgroup per record, a lane per sample: value g of the sample's vector into the same plane (<false>: from the
+//                 staging, on 4-byte addresses; <true>: from a resident file, at any byte)
 //   k_fgl_plan    a workgroup per record: the byte count of its line, "POS," included (0 for a record that is not OK)
 //   k_offsets_scan (wg_scan.hip.h) one workgroup: the exclusive prefix sums of the counts over the batch's records
 //   k_fgl_write   a workgroup per record, a lane per value: the values' lengths are scanned across the workgroup, chunk by chunk, and
@@ -21,6 +22,7 @@
 
 #include "../../../include/vcfgl_hip.h"
 #include "fgl_dev.h"
+#include "rb_core.h"
 #include "column_walk.hip.h"
 #include "batch_dev.hip.h"
 
@@ -72,20 +74,28 @@ __global__ void __launch_bounds__(NT) k_fgl_parse(const ParseArgs A) {
     }
 }
 
-// BCF: text holds the records' GL vector blocks, N vectors of r.len floats from byte r.off (a multiple of 4)
+// BCF: text holds the records' GL vector blocks, N vectors of r.len floats from byte r.off.  ANY = false: the slot's staging, where
+// r.off is a multiple of 4.  ANY = true: a resident file (resident_file.h), where a block begins at any byte: a float is read from
+// the aligned words around it (rb::load_u32_any), never from a word that reaches past text_bytes
+template <bool ANY>
 __global__ void __launch_bounds__(NT) k_fgl_pick(const ParseArgs A) {
     const int rec = blockIdx.x, t = threadIdx.x;
     if (rec >= A.n_recs) return;
     const fgl::Rec r = A.recs[rec];
     const int64_t n = r.len, N = A.N;
-    const bool fits = r.off >= 0 && (r.off & 3) == 0 && n >= 1 && r.off + N * n * 4 <= A.text_bytes;
+    const bool fits = r.off >= 0 && (ANY || (r.off & 3) == 0) && n >= 1 && r.off + N * n * 4 <= A.text_bytes;
     if (!fits || r.g < 0 || r.g >= n) {
         if (t == 0) A.status[rec] = fits ? fgl::ST_RANGE : fgl::ST_HOST;
         return;
     }
-    const uint32_t* __restrict__ v = reinterpret_cast<const uint32_t*>(A.text + r.off);
     uint32_t* __restrict__ plane = A.plane + (size_t)rec * (size_t)N;
-    for (int64_t s = t; s < N; s += NT) plane[s] = v[s * n + r.g];
+    if (ANY) {
+        const uint8_t* __restrict__ text = A.text;
+        for (int64_t s = t; s < N; s += NT) plane[s] = rb::load_u32_any(text, r.off + (s * n + r.g) * 4, A.text_bytes);
+    } else {
+        const uint32_t* __restrict__ v = reinterpret_cast<const uint32_t*>(A.text + r.off);
+        for (int64_t s = t; s < N; s += NT) plane[s] = v[s * n + r.g];
+    }
     if (t == 0) A.status[rec] = fgl::ST_OK;
 }
 
@@ -199,7 +209,8 @@ static int submit_on(FglDev* d, int slot, int32_t n_recs, const uint8_t* staged,
     if (staged && text_bytes > 0) BATCH_HIP(d, hipMemcpyAsync(s.d_text, staged, (size_t)text_bytes, hipMemcpyHostToDevice, st));
     BATCH_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(fgl::Rec), hipMemcpyHostToDevice, st));
     const ParseArgs P{text, text_bytes, s.d_recs, n_recs, d->N, s.d_plane, s.d_status};
-    if (bcf) hipLaunchKernelGGL(k_fgl_pick, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
+    if (bcf && !staged) hipLaunchKernelGGL(k_fgl_pick<true>, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
+    else if (bcf) hipLaunchKernelGGL(k_fgl_pick<false>, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
     else hipLaunchKernelGGL(k_fgl_parse, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
     BATCH_HIP(d, hipGetLastError());
     const LineArgs L{d->N, n_recs, s.d_recs, s.d_plane, s.d_status, s.d_len, s.d_off, s.d_csv, d->cap};
@@ -220,9 +231,9 @@ int fgl_dev_submit(FglDev* d, int slot, int32_t n_recs, int64_t text_bytes, int 
     return submit_on(d, slot, n_recs, s.h_text, s.d_text, text_bytes, bcf);
 }
 
-int fgl_dev_submit_resident(FglDev* d, int slot, int32_t n_recs, const uint8_t* d_text, int64_t text_bytes) {
+int fgl_dev_submit_resident(FglDev* d, int slot, int32_t n_recs, const uint8_t* d_text, int64_t text_bytes, int bcf) {
     if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && d_text && text_bytes >= 0) != 0) return -1;
-    return submit_on(d, slot, n_recs, nullptr, d_text, text_bytes, 0);
+    return submit_on(d, slot, n_recs, nullptr, d_text, text_bytes, bcf);
 }
 
 int fgl_dev_wait(FglDev* d, int slot, FglBatchOut* out) {

@@ -1,12 +1,16 @@
 // fetchgl_main.cpp -- fetchgl_hip: the reference's misc/fetchGl (one genotype's FORMAT/GL of every sample, as CSV) for this platform.
 //   fetchgl_hip -i file -gt XY [-o out.csv] [--on-device 0|1] [--device INT] [--batch-records INT] [--messages 0|1] [--verbose 0|1]
-//               [--device-inflate 0|1] [--resident 0|1] [--resident-max-bytes INT]
+//               [--device-inflate 0|1] [--resident 0|1] [--resident-max-bytes INT] [--resident-bcf 0|1]
 // The file is read whole (plain, gzip or bgzip text through zlib, or BCF inside either; --device-inflate 1: BGZF members on the GPU,
 // record_file.h).  --resident 1 (with --device-inflate 1 and --on-device 1): a BGZF file of VCF text is inflated into device memory
 // and stays there (resident_file.h) -- the device finds the lines, only their heads (the first nine columns) come down for the notes
 // below, and the batches' descriptors point into the resident text; a record the device hands back has its sample columns copied
 // down for the strtod reader.  Whatever keeps the file from being resident (not BGZF, a member left to the host, BCF, too large, a
 // line whose ninth tab is too far, too many lines) is named in the [input] line, and the run goes on as with --resident 0.
+// --resident-bcf 1 (with --resident 1) does the same for a BGZF file of BCF: the device follows the records' lengths and walks their
+// FORMAT fields (rb_core.h), the head of each record (its lengths, its shared block, the fields' keys and descriptors) comes down for
+// the notes, and the batches' descriptors point at the GL vectors where the inflater wrote them.  A record the walk is not sure of
+// hands the whole file back to the host reader, and the [input] line says which record and why.
 // The host finds the records, reads the first nine columns of each (for BCF: the shared block and the FORMAT field headers), finds GL
 // and the genotype's index g, and keeps a small note per record.  The records that get a CSV line are then read by the rules of fgl_core.h -- on the device in batches
 // (--on-device 1: fetchgl.hip) or by the same routines on the host (--on-device 0) -- and a record those rules hand back (a token
@@ -23,7 +27,7 @@ namespace {
 struct Opt {
     std::string in, gt, out;
     int on_device = 1, device = 0, batch = 4096, messages = 1, verbose = 0;
-    int device_inflate = 0, resident = 0;
+    int device_inflate = 0, resident = 0, resident_bcf = 0;
     int64_t resident_max = -1;         // --resident-max-bytes (-1: the device's free memory less 1 GiB)
 };
 
@@ -44,6 +48,9 @@ const char FGL_USAGE[] =
     "                            columns alone come down, the sample columns are parsed where they lie (needs --device-inflate 1 and\n"
     "                            --on-device 1; any other file is read as with 0, the reason is in the [input] line of --verbose 1)\n"
     "  --resident-max-bytes INT  the most bytes, inflated and compressed together, a resident file may take [the GPU's free memory less 1 GiB]\n"
+    "  --resident-bcf 0|1 [0]    1: a BGZF file of BCF stays in GPU memory too: the GPU follows the records and walks their FORMAT fields, the\n"
+    "                            shared blocks and field headers alone come down, the GL vectors are read where they lie (needs --resident 1;\n"
+    "                            a file the walk is not sure of is read as with 0, the record and the reason are in the [input] line)\n"
     "  -h, --help                print help\n\n";
 
 Opt parse_opt(int argc, char** argv) {
@@ -64,6 +71,7 @@ Opt parse_opt(int argc, char** argv) {
         else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
         else if (!strcmp(a, "--device-inflate")) o.device_inflate = option_int(a, v, 0, 1);
         else if (!strcmp(a, "--resident")) o.resident = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--resident-bcf")) o.resident_bcf = option_int(a, v, 0, 1);
         else if (!strcmp(a, "--resident-max-bytes")) {
             char* e; const long long x = strtoll(v, &e, 10);
             if (e == v || *e || x < 0) die("%s takes an integer of at least 0, not '%s'", a, v);
@@ -75,12 +83,13 @@ Opt parse_opt(int argc, char** argv) {
     if (o.gt.empty()) die("Genotype to fetch not specified. Exiting...");
     if (o.gt.size() != 2) die("A genotype is exactly two characters, not '%s'.", o.gt.c_str());
     if (o.resident && !(o.device_inflate && o.on_device)) die("--resident 1 needs --device-inflate 1 and --on-device 1.");
+    if (o.resident_bcf && !o.resident) die("--resident-bcf 1 needs --resident 1 (and with it --device-inflate 1 and --on-device 1).");
     return o;
 }
 
 // what the host keeps of a record: where its sample columns (BCF: its GL vectors) lie, GL's place, the two alleles
 struct Note {
-    int64_t pos = 0, off = 0;
+    int64_t pos = 0, off = 0;             // off: into raw, or (a resident file) into the file
     int32_t len = 0;                   // text: bytes of the sample columns; BCF: the vector length
     int32_t k = 0;
     int16_t a0 = -1, a1 = -1;
@@ -103,6 +112,8 @@ struct Run {
     FglDev* dev = nullptr;
     RfFile* rf = nullptr;              // --resident 1: the file's text in device memory (raw is then the head stream)
     rf::Split split;
+    std::vector<uint8_t> bcf_head;     // --resident-bcf 1: the header of a resident BCF file (raw is then the records' head stream)
+    RbSplit bsplit;
     long n_lines = 0, n_host = 0; int64_t up = 0, down = 0;
     double t_read = 0, t_nine = 0, t_dev = 0, t_host = 0;
 
@@ -135,11 +146,22 @@ struct Run {
     // a record for the strtod reader: its sample columns where the host holds them, or copied down from the resident text
     void record_redo(const Note& n, std::vector<uint32_t>& plane) {
         if (!rf) { record_strtod(n, (const char*)raw.data() + n.off, plane); return; }
+        if (bcf) {                                                     // a resident BCF record the device handed back: its GL block, by the host's rule
+            std::vector<uint8_t> block((size_t)N * (size_t)n.len * 4);
+            if (rf_fetch(rf, n.off, (int64_t)block.size(), block.data()) != 0) stop_run("--resident-bcf 1: %s", rf_error(rf));
+            pick_bcf(n, block.data(), plane);
+            return;
+        }
         std::vector<uint8_t> cols((size_t)n.len + 1);
         if (rf_fetch(rf, n.off, n.len, cols.data()) != 0) stop_run("--resident 1: %s", rf_error(rf));
         record_strtod(n, (const char*)cols.data(), plane);
     }
+    void pick_bcf(const Note& n, const uint8_t* v, std::vector<uint32_t>& plane) {
+        for (int64_t s = 0; s < N; s++) memcpy(&plane[s], v + ((size_t)s * n.len + n.g()) * 4, 4);
+        put_line(n, plane.data());
+    }
     bool load_resident(FileReader& reader);
+    const char* load_resident_bcf(std::string& why);
     void record_host(const Note& n, std::vector<uint32_t>& plane);
     void notes_text();
     void notes_bcf();
@@ -191,12 +213,7 @@ void Run::record_strtod(const Note& n, const char* const t, std::vector<uint32_t
 
 // --on-device 0: the routines the kernels run, a column at a time; the strtod reader for what they hand back
 void Run::record_host(const Note& n, std::vector<uint32_t>& plane) {
-    if (bcf) {
-        const uint8_t* v = raw.data() + n.off;
-        for (int64_t s = 0; s < N; s++) memcpy(&plane[s], v + ((size_t)s * n.len + n.g()) * 4, 4);
-        put_line(n, plane.data());
-        return;
-    }
+    if (bcf) { pick_bcf(n, raw.data() + n.off, plane); return; }
     fgl::Rec r; memset(&r, 0, sizeof r);
     r.off = n.off; r.len = n.len; r.k = n.k; r.g = n.g(); r.pos = n.pos;
     const int st = fgl::record_plain(raw.data(), r, N, plane.data(), nullptr);
@@ -270,6 +287,7 @@ bool Run::load_resident(FileReader& reader) {
     if (rf_load(rf, o.in.c_str(), most, &why) != 0) failed();
     const char* reason = nullptr;
     bool have = false;                                                 // raw was copied down from the device
+    bool is_bcf = false; std::string bcf_why;
     if (why == RF_NOT_BGZF) reason = "the file is not a series of BGZF members";
     else if (why == RF_MEMBER_HOST) reason = "a member was left to the host (VGL_INFLATE_HOST)";
     else if (why == RF_TOO_LARGE) reason = "the inflated and the compressed bytes exceed --resident-max-bytes";
@@ -278,7 +296,8 @@ bool Run::load_resident(FileReader& reader) {
         uint8_t first[3] = {0, 0, 0};
         if (rf_fetch(rf, 0, std::min<int64_t>(3, total), first) != 0) failed();
         bool more_lines = false;
-        if (total >= 3 && !memcmp(first, "BCF", 3)) reason = "the file is BCF";
+        if (total >= 3 && !memcmp(first, "BCF", 3) && o.resident_bcf) { is_bcf = true; reason = load_resident_bcf(bcf_why); }
+        else if (total >= 3 && !memcmp(first, "BCF", 3)) reason = "the file is BCF";
         else {
             if (rf_split(rf, rf::RF_HEAD_MOST, &split, &more_lines) != 0) failed();
             if (more_lines) reason = "the file has more lines than the offsets scan takes (INT32_MAX - 1024)";
@@ -291,38 +310,74 @@ bool Run::load_resident(FileReader& reader) {
         }
     }
     const RfStats st = *rf_stats(rf);
-    if (o.verbose) {
+    if (o.resident_bcf && reason && !have) {                           // nothing was inflated: zlib reads the first three bytes, so that the
+        uint8_t first[3] = {0, 0, 0};                                  // [input] lines come in the order of --resident 1
+        gzFile fp = gzopen(o.in.c_str(), "r");
+        if (fp) { is_bcf = gzread(fp, first, 3) == 3 && !memcmp(first, "BCF", 3); gzclose(fp); }
+    }
+    if (o.verbose && is_bcf)                                           // --resident-bcf 1: a BCF file has a line of its own
+        fprintf(stderr, "[input] %s: resident-bcf %d%s%s%s, members %lld, records %lld, head bytes received %lld, compressed bytes sent up %lld; upload %.3f s, inflate %.3f s, chain %.3f s, heads %.3f s\n",
+                o.in.c_str(), reason ? 0 : 1, reason ? " (" : "", reason ? reason : "", reason ? ")" : "", (long long)st.members, (long long)st.records,
+                (long long)st.head_bytes, (long long)st.compressed_up, st.t_upload, st.t_inflate, st.t_chain, st.t_heads);
+    else if (o.verbose)
         fprintf(stderr, "[input] %s: resident %d%s%s%s, RF_CHUNK %lld, members %lld, lines %lld, head bytes received %lld, compressed bytes sent up %lld; upload %.3f s, inflate %.3f s, split %.3f s\n",
                 o.in.c_str(), reason ? 0 : 1, reason ? " (" : "", reason ? reason : "", reason ? ")" : "", (long long)rf::RF_CHUNK, (long long)st.members, (long long)st.lines,
                 (long long)st.head_bytes, (long long)st.compressed_up, st.t_upload, st.t_inflate, st.t_split);
-        if (have) FileReader::report(o.in, (long)st.members, st.compressed_up, st.total, st.t_inflate, nullptr);
-    }
-    if (!reason) { raw = std::move(split.heads); return true; }
-    rf_destroy(rf); rf = nullptr; split = rf::Split();
+    if (o.verbose && have) FileReader::report(o.in, (long)st.members, st.compressed_up, st.total, st.t_inflate, nullptr);
+    if (!reason) { raw = std::move(is_bcf ? bsplit.heads : split.heads); bcf = is_bcf; return true; }
+    rf_destroy(rf); rf = nullptr; split = rf::Split(); bsplit = RbSplit(); bcf_head.clear();
     if (!have) raw = reader.read(o.in);
     return false;
 }
 
+// --resident-bcf 1, a resident file that begins as BCF: its header and the split of its records (resident_file.h).  nullptr: bcf_head
+// and bsplit hold them; else why the bytes come down whole
+const char* Run::load_resident_bcf(std::string& why) {
+    auto failed = [&]() { die("--resident-bcf 1: %s", rf_error(rf)); };
+    bool fits = false;
+    if (rf_bcf_header(rf, &bcf_head, &fits) != 0) failed();
+    if (!fits) { why = "the header does not fit the file"; return why.c_str(); }
+    int64_t n_samples = -1;
+    try { BcfDict d; Vcf v; BcfIn c; c.buf = bcf_head.data(); c.size = bcf_head.size(); c.soft = true; bcf_header(c, d, v); n_samples = (int64_t)v.samples.size(); }
+    catch (const BcfSoftFail&) { why = "the header could not be read"; return why.c_str(); }
+    if (rf_bcf_split(rf, (int64_t)bcf_head.size(), n_samples, rb::RB_HOPS_MOST, rf::RF_HEAD_MOST, &bsplit) != 0) failed();
+    if (bsplit.more_records) why = "the file has more records than the offsets scan takes (INT32_MAX - 1024)";
+    else if (bsplit.why != rb::OK) { char b[256]; snprintf(b, sizeof b, "record %lld: %s", (long long)bsplit.ordinal + 1, rb::why_text(bsplit.why)); why = b; }
+    else return nullptr;
+    return why.c_str();
+}
+
 // BCF: the shared block -> POS and the alleles; the FORMAT field headers -> where GL's vectors lie
+// One body for both sources.  The file's bytes in raw: the cursor walks them.  A resident file (--resident-bcf 1): the header is
+// bcf_head, raw is the head stream -- per record the two lengths, the shared block and the fields' keys and descriptors, bytes
+// identical to the file's -- and a field's data offset is worked out from the record's place in the file (bcf_format_fields).
 void Run::notes_bcf() {
-    BcfDict d; BcfIn c; c.buf = raw.data(); c.size = raw.size();
+    BcfDict d; BcfIn c; c.buf = rf ? bcf_head.data() : raw.data(); c.size = rf ? bcf_head.size() : raw.size();
     Vcf v;
     bcf_header(c, d, v);
+    if (rf) { c.buf = raw.data(); c.size = raw.size(); c.off = 0; }
     header = v.header; samples = v.samples;
     N = (int64_t)samples.size();
     std::string type;
     const bool defined = header_defines_gl(header, &type) && type == "Float";
     char msg[256];
-    while (c.off < c.size) {
+    for (size_t i = 0; c.off < c.size; i++) {
         BcfRecAt at; int n_fmt;
-        bcf_scan_record(c, at);
+        const size_t head_at = c.off;
+        if (!rf) bcf_scan_record(c, at);
+        else {                                                         // (the device has made the checks of bcf_scan_record)
+            if (i >= (size_t)bsplit.records || (int64_t)head_at != bsplit.hoff[i]) stop_run("--resident-bcf 1: the head stream does not follow its records.");
+            const uint32_t l_shared = c.u32(); (void)c.u32();
+            at.shared = c.off; at.shared_end = c.off + l_shared; at.rec_end = (size_t)bsplit.hoff[i + 1];
+        }
         Rec r;
         bcf_shared(c, d, at, (size_t)N, r, n_fmt);
         Note n; n.pos = r.pos0 + 1; n.k = -1;
         bool is_float = false;
         bcf_format_fields(c, d, n_fmt, (size_t)N, [&](int k, const std::string& key, int ty, int nv, size_t data_off) {
             if (key == "GL" && n.k < 0) { n.k = k; is_float = ty == 5 && nv >= 1; n.off = (int64_t)data_off; n.len = nv; }
-        });
+        }, rf ? bsplit.rec_off[i] + (int64_t)(c.off - head_at) : (int64_t)-1);
+        if (rf && c.off != at.rec_end) stop_run("--resident-bcf 1: a record's head is not as long as the device made it.");
         c.off = at.rec_end;
         if (!defined || n.k < 0 || !is_float) { snprintf(msg, sizeof msg, "Could not read GL tag at position %lld. Exiting...", (long long)n.pos); stop = msg; return; }
         for (size_t j = 0; j < r.alleles.size() && j < (size_t)INT16_MAX; j++) match_alleles(o, r.alleles[j].empty() ? '\0' : r.alleles[j][0], (int)j, n);
@@ -365,7 +420,7 @@ void run_device(Run& R, std::vector<uint32_t>& plane) {
             if (!R.rf) { memcpy(text + at, R.raw.data() + nt.off, (size_t)bytes_of(nt)); at += bytes_of(nt); }
             recs[n] = r;
         }
-        const int rc = R.rf ? fgl_dev_submit_resident(R.dev, slot, n, rf_device_text(R.rf), rf_total(R.rf)) : fgl_dev_submit(R.dev, slot, n, at, R.bcf ? 1 : 0);
+        const int rc = R.rf ? fgl_dev_submit_resident(R.dev, slot, n, rf_device_text(R.rf), rf_total(R.rf), R.bcf ? 1 : 0) : fgl_dev_submit(R.dev, slot, n, at, R.bcf ? 1 : 0);
         if (rc != 0) R.stop_run("--on-device 1: %s", fgl_dev_error(R.dev));
         R.up += at + (int64_t)n * (int64_t)sizeof(fgl::Rec); R.t_dev += now_s() - t0;
     };
@@ -408,7 +463,7 @@ int main(int argc, char** argv) {
     R.out_fp = o.out.empty() ? stdout : fopen(o.out.c_str(), "w");
     if (!R.out_fp) die("Could not open output file %s for writing", o.out.c_str());
     R.t_read = now_s() - t0; t0 = now_s();
-    R.bcf = R.raw.size() >= 3 && !memcmp(R.raw.data(), "BCF", 3);
+    if (!R.rf) R.bcf = R.raw.size() >= 3 && !memcmp(R.raw.data(), "BCF", 3);
     if (R.bcf) R.notes_bcf(); else R.notes_text();
     if (R.N <= 0) die("The file %s names no sample.", o.in.c_str());
     if (R.N > (int64_t)(INT32_MAX / fgl::VALUE_BOUND)) die("Too many samples.");

@@ -20,8 +20,9 @@ fgl::Rec* fgl_dev_recs(FglDev* d, int slot);
 // bcf 0: the staging holds sample-column text (k_fgl_parse); 1: GL vector blocks of floats (k_fgl_pick)
 int fgl_dev_submit(FglDev* d, int slot, int32_t n_recs, int64_t text_bytes, int bcf);
 // the records' sample columns lie in device memory of the handle's device already (resident_file.h): the descriptors' offsets are into
-// d_text [text_bytes], k_fgl_parse reads them there, and nothing of the slot's staging is copied
-int fgl_dev_submit_resident(FglDev* d, int slot, int32_t n_recs, const uint8_t* d_text, int64_t text_bytes);
+// d_text [text_bytes], k_fgl_parse reads them there, and nothing of the slot's staging is copied.  bcf 1: the file is BCF, a descriptor's
+// offset is where the record's GL vectors begin (any byte), and k_fgl_pick<true> reads them there
+int fgl_dev_submit_resident(FglDev* d, int slot, int32_t n_recs, const uint8_t* d_text, int64_t text_bytes, int bcf);
 int fgl_dev_wait(FglDev* d, int slot, FglBatchOut* out);
 void fgl_dev_quiesce(FglDev* d);                               // waits for whatever is in flight (before the process leaves on an error)
 void fgl_dev_destroy(FglDev* d);

@@ -93,15 +93,19 @@ static inline int bcf_type_width(const int ty) { return ty == 1 ? 1 : ty == 2 ? 
 
 // the n_fmt FORMAT fields of the BCF record at the cursor, N samples: f(k, key, type, n, data_off) for field k, whose N vectors of n
 // values of `type` lie from byte data_off of the file; the cursor is left behind the last field.  A key outside the dictionary and a
-// field that runs past the file's end stop the program.
-template <typename F> static void bcf_format_fields(BcfIn& c, const BcfDict& d, const int n_fmt, const size_t N, F f) {
+// field that runs past the file's end stop the program.  file_at < 0: the cursor is over the file.  file_at >= 0: the cursor is over
+// the fields' keys and descriptors alone, back to back (the head of a resident record, resident_file.h), the first of which lies at
+// byte file_at of the file: data_off is then file_at + the header bytes so far + the data bytes of the fields before
+template <typename F> static void bcf_format_fields(BcfIn& c, const BcfDict& d, const int n_fmt, const size_t N, F f, const int64_t file_at = -1) {
     std::vector<int32_t> iv; int ty, n;
+    const size_t first = c.off; size_t data_before = 0;
     for (int k = 0; k < n_fmt; k++) {
         c.typed(ty, n); c.ints(ty, n, iv);
         const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
         if (key == d.dict.end()) c.fail("BCF: undefined FORMAT key");
         c.typed(ty, n);
         const size_t bytes = (size_t)bcf_type_width(ty) * n * N;
+        if (file_at >= 0) { f(k, key->second, ty, n, (size_t)file_at + (c.off - first) + data_before); data_before += bytes; continue; }
         if (c.off + bytes > c.size) c.fail("truncated BCF record");
         f(k, key->second, ty, n, c.off);
         c.off += bytes;

@@ -11,6 +11,7 @@
 //   k_offsets_scan  the head lengths + 1 -> where every head begins in the stream
 //   k_rf_head_copy  a wavefront per line: the head's bytes and a '\n' behind them
 // No kernel reads outside [0, total) or stores outside the arrays it is given (every index is compared with the array's length).
+// A BCF file (--resident-bcf 1) is walked by the kernels further down: k_rb_chain, k_rb_head_len, k_rb_head_copy (rb_core.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -19,6 +20,7 @@
 
 #include "../../../include/vcfgl_hip.h"
 #include "resident_file.h"
+#include "rb_core.h"
 #include "wg_scan.hip.h"
 #include "batch_dev.hip.h"
 
@@ -113,6 +115,92 @@ __global__ void __launch_bounds__(RF_NT) k_rf_head_copy(const CopyArgs A) {
         if (b < 0 || n < 0 || b + n > A.total || at < 0 || at + n + 1 > A.head_bytes) continue;     // (uniform over the wavefront)
         for (int64_t j = lane; j < n; j += 64) A.heads[at + j] = A.text[b + j];
         if (lane == 0) A.heads[at + n] = (uint8_t)'\n';
+    }
+}
+
+// ---- a resident BCF file (rb_core.h) ----------------------------------------------------------------------------------------------
+//   k_rb_chain      the serial part, one wavefront: the lanes load a window of RB_WINDOW bytes into LDS (a piece of 16 a lane, as
+//                   k_rf_count loads it), the lengths of the records inside the window are followed from LDS, and the window is loaded
+//                   again only when the next record's lengths lie outside it.  At most hops_most records a launch: their offsets go
+//                   into a buffer of that many entries, and where the launch stopped goes back to the host, which launches again.
+//                   Every hop moves on by RB_REC_LEAST bytes at least.
+//   k_rb_head_len   a lane per record: rb::format_walk (a loop of n_fmt <= 255 fields, and of the shared block's n_allele + n_info
+//                   <= 2^17 items) -> the head's length; a record the walk hands back raises the file's flag, the lowest ordinal wins
+//   k_offsets_scan  the head lengths -> where every head begins in the stream
+//   k_rb_head_copy  a wavefront per record: the lengths and the shared block lane by lane, then the fields' headers by walking the
+//                   fields again (rb::fields_walk; the shared block was walked by k_rb_head_len and is not walked twice)
+// No kernel waits for another; every store is compared with its array's length.
+struct ChainArgs {
+    const uint8_t* bytes; int64_t total, o0, hops_most;
+    int64_t* offs; int64_t offs_cap;
+    rb::ChainEnd* end;
+};
+
+__global__ void __launch_bounds__(rb::RB_WIN_LANES) k_rb_chain(const ChainArgs A) {
+    __shared__ uint32_t s_win[rb::RB_WINDOW / 4];
+    const int lane = threadIdx.x;
+    // (every value below is the same in all lanes: the loop and its barriers are uniform)
+    int64_t o = A.o0, wb = -1, taken = 0;
+    int32_t why = rb::OK, done = 0;
+    while (taken < A.hops_most && taken < A.offs_cap) {
+        if (o == A.total) { done = 1; break; }
+        if (o < 0 || o + 8 > A.total) { why = rb::W_LENGTHS; break; }
+        if (wb < 0 || o < wb || o + 8 > wb + rb::RB_WINDOW) {
+            wb = o & ~(int64_t)(RF_LANE - 1);
+            uint32_t w[4];
+            rf::load_piece(A.bytes, wb + (int64_t)lane * RF_LANE, A.total, w);
+            __syncthreads();
+            s_win[lane * 4 + 0] = w[0]; s_win[lane * 4 + 1] = w[1]; s_win[lane * 4 + 2] = w[2]; s_win[lane * 4 + 3] = w[3];
+            __syncthreads();
+        }
+        uint32_t l_shared, l_indiv; int64_t rec_end;
+        rb::win_lengths(s_win, o - wb, l_shared, l_indiv);
+        why = rb::step_rule(o, A.total, l_shared, l_indiv, rec_end);
+        if (why != rb::OK) break;
+        if (lane == 0) A.offs[taken] = o;
+        taken++;
+        o = rec_end;
+    }
+    if (lane == 0) { A.end->next = o; A.end->taken = taken; A.end->done = done; A.end->why = why; }
+}
+
+struct RbHeadArgs {
+    const uint8_t* bytes; int64_t total;
+    const int64_t* rec_off; int64_t n_recs, N, head_most;
+    int64_t* hl;
+    unsigned long long* flag;
+};
+
+__global__ void __launch_bounds__(RF_NT) k_rb_head_len(const RbHeadArgs A) {
+    for (int64_t i = (int64_t)blockIdx.x * RF_NT + threadIdx.x; i < A.n_recs; i += (int64_t)gridDim.x * RF_NT) {
+        int64_t len = 0;
+        const int st = rb::format_walk(A.bytes, A.total, A.rec_off[i], A.N, A.head_most, len, [](int, int64_t, int64_t, int32_t, int32_t, int64_t, int64_t) {});
+        A.hl[i] = st == rb::OK ? len : 0;
+        if (st != rb::OK) atomicMin(A.flag, rb::flag_word(i, st));
+    }
+}
+
+struct RbCopyArgs {
+    const uint8_t* bytes; int64_t total;
+    const int64_t* rec_off; const int64_t* hoff; int64_t n_recs, N, head_most;
+    uint8_t* heads; int64_t head_bytes;
+};
+
+__global__ void __launch_bounds__(RF_NT) k_rb_head_copy(const RbCopyArgs A) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t i = (int64_t)blockIdx.x * (RF_NT / 64) + wave; i < A.n_recs; i += (int64_t)gridDim.x * (RF_NT / 64)) {
+        const int64_t o = A.rec_off[i], at = A.hoff[i], n = A.hoff[i + 1] - at;
+        rb::Lead L;
+        if (rb::record_lead(A.bytes, A.total, o, A.N, A.head_most, L) != rb::OK) continue;       // (uniform over the wavefront)
+        const int64_t lead = 8 + (int64_t)L.l_shared, hi = at + n < A.head_bytes ? at + n : A.head_bytes;
+        if (at < 0 || n < lead) continue;
+        for (int64_t j = lane; j < lead; j += 64) if (at + j < hi) A.heads[at + j] = A.bytes[o + j];
+        // the fields alone: k_rb_head_len has taken the record, its shared block is not walked again
+        int64_t w = at + lead, hdr;
+        rb::fields_walk(A.bytes, L.se, L.rec_end, L.n_fmt, A.N, hdr, [&](int, int64_t hdr_at, int64_t hdr_len, int32_t, int32_t, int64_t, int64_t) {
+            for (int64_t j = lane; j < hdr_len; j += 64) if (w + j < hi) A.heads[w + j] = A.bytes[hdr_at + j];
+            w += hdr_len;
+        });
     }
 }
 
@@ -310,5 +398,88 @@ int rf_split(RfFile* f, int64_t head_most, rf::Split* out, bool* more_lines) {
     BATCH_HIP(f, hipMemcpyAsync(out->s_len.data(), d_slen, (size_t)L * 8, hipMemcpyDeviceToHost, st));
     BATCH_HIP(f, hipStreamSynchronize(st));
     f->st.head_bytes = head_bytes; f->st.down += head_bytes + (3 * L + 1) * 8; f->st.t_split = now() - t0;
+    return 0;
+}
+
+// ---- a resident BCF file ----------------------------------------------------------------------------------------------------------
+int rf_bcf_header(RfFile* f, std::vector<uint8_t>* hdr, bool* fits) {
+    hdr->clear(); *fits = false;
+    if (f->total < 9) return 0;
+    uint8_t lead[9];
+    if (rf_fetch(f, 0, 9, lead) != 0) return -1;
+    if (memcmp(lead, "BCF\2", 4) != 0) return 0;
+    const int64_t l_text = (int64_t)rb::rd_u32(lead, 5);
+    if (9 + l_text > f->total) return 0;
+    hdr->resize((size_t)(9 + l_text));
+    if (rf_fetch(f, 0, 9 + l_text, hdr->data()) != 0) return -1;
+    *fits = true;
+    return 0;
+}
+
+int rf_bcf_split(RfFile* f, int64_t start, int64_t n_samples, int64_t hops_most, int64_t head_most, RbSplit* out) {
+    *out = RbSplit();
+    const int64_t total = f->total;
+    if (start < 0 || start > total || n_samples < 0 || hops_most < 1 || head_most < 24) return f->refuse("a resident BCF split outside its bounds");
+    BATCH_HIP(f, hipSetDevice(f->device));
+    double t0 = now();
+    hipStream_t st = f->stream;
+    const uint8_t* bytes = f->d_text;
+    const int64_t SCAN_MOST = (int64_t)INT32_MAX - wgscan::SCAN_NT;
+    // the chain: hops_most records a launch
+    const int64_t room = (total - start) / rb::RB_REC_LEAST + 1, cap = hops_most < room ? hops_most : room;
+    batchdev::DevMem<int64_t> d_hop; batchdev::DevMem<rb::ChainEnd> d_end;
+    BATCH_HIP(f, d_hop.alloc((size_t)cap * 8)); BATCH_HIP(f, d_end.alloc(sizeof(rb::ChainEnd)));
+    std::vector<int64_t>& rec_off = out->rec_off;
+    for (int64_t o = start;;) {
+        const ChainArgs A{bytes, total, o, hops_most, d_hop, cap, d_end};
+        hipLaunchKernelGGL(k_rb_chain, dim3(1), dim3(rb::RB_WIN_LANES), 0, st, A);
+        BATCH_HIP(f, hipGetLastError());
+        rb::ChainEnd e;
+        BATCH_HIP(f, hipMemcpyAsync(&e, d_end, sizeof e, hipMemcpyDeviceToHost, st));
+        BATCH_HIP(f, hipStreamSynchronize(st));
+        f->st.chain_launches++;
+        if (e.taken < 0 || e.taken > cap || e.next < o || e.next > total) return f->refuse("a chain launch ended outside the file");
+        if (e.taken > 0) {
+            const size_t at = rec_off.size();
+            rec_off.resize(at + (size_t)e.taken);
+            BATCH_HIP(f, hipMemcpyAsync(rec_off.data() + at, d_hop, (size_t)e.taken * 8, hipMemcpyDeviceToHost, st));
+            BATCH_HIP(f, hipStreamSynchronize(st));
+            f->st.down += e.taken * 8;
+        }
+        if ((int64_t)rec_off.size() > SCAN_MOST) { out->more_records = true; rec_off.clear(); f->st.t_chain = now() - t0; return 0; }
+        if (e.why != rb::OK) { out->why = e.why; out->ordinal = (int64_t)rec_off.size(); break; }
+        if (e.done) break;
+        if (e.taken == 0) return f->refuse("a chain launch took no record");
+        o = e.next;
+    }
+    const int64_t R = (int64_t)rec_off.size();
+    out->records = R; f->st.records = R; f->st.t_chain = now() - t0; t0 = now();
+    out->hoff.assign(1, 0);
+    if (out->why != rb::OK || R == 0) return 0;
+    // the heads
+    batchdev::DevMem<int64_t> d_rec, d_hl, d_hoff; batchdev::DevMem<unsigned long long> d_flag; batchdev::DevMem<uint8_t> d_heads;
+    BATCH_HIP(f, d_rec.alloc((size_t)R * 8)); BATCH_HIP(f, d_hl.alloc((size_t)R * 8)); BATCH_HIP(f, d_hoff.alloc(((size_t)R + 1) * 8)); BATCH_HIP(f, d_flag.alloc(8));
+    BATCH_HIP(f, hipMemcpyAsync(d_rec, rec_off.data(), (size_t)R * 8, hipMemcpyHostToDevice, st));
+    BATCH_HIP(f, hipMemsetAsync(d_flag, 0xFF, 8, st));
+    const RbHeadArgs H{bytes, total, d_rec, R, n_samples, head_most, d_hl, d_flag};
+    hipLaunchKernelGGL(k_rb_head_len, dim3(grid_for((R + RF_NT - 1) / RF_NT)), dim3(RF_NT), 0, st, H);
+    BATCH_HIP(f, hipGetLastError());
+    hipLaunchKernelGGL(wgscan::k_offsets_scan, dim3(1), dim3(wgscan::SCAN_NT), 0, st, (const int64_t*)d_hl, (int64_t*)d_hoff, (int32_t)R);
+    BATCH_HIP(f, hipGetLastError());
+    int64_t head_bytes = 0; unsigned long long flag = rb::FLAG_NONE;
+    BATCH_HIP(f, hipMemcpyAsync(&head_bytes, d_hoff + R, 8, hipMemcpyDeviceToHost, st));
+    BATCH_HIP(f, hipMemcpyAsync(&flag, d_flag, 8, hipMemcpyDeviceToHost, st));
+    BATCH_HIP(f, hipStreamSynchronize(st));
+    if (flag != rb::FLAG_NONE) { out->why = (int)(flag & 0xFF); out->ordinal = (int64_t)(flag >> 8); f->st.t_heads = now() - t0; return 0; }
+    if (head_bytes < R * rb::RB_REC_LEAST || head_bytes > total) return f->refuse("the head stream is longer than the file");
+    BATCH_HIP(f, d_heads.alloc((size_t)head_bytes));
+    const RbCopyArgs C{bytes, total, d_rec, d_hoff, R, n_samples, head_most, d_heads, head_bytes};
+    hipLaunchKernelGGL(k_rb_head_copy, dim3(grid_for((R + RF_NT / 64 - 1) / (RF_NT / 64))), dim3(RF_NT), 0, st, C);
+    BATCH_HIP(f, hipGetLastError());
+    out->heads.resize((size_t)head_bytes); out->hoff.resize((size_t)R + 1);
+    BATCH_HIP(f, hipMemcpyAsync(out->heads.data(), d_heads, (size_t)head_bytes, hipMemcpyDeviceToHost, st));
+    BATCH_HIP(f, hipMemcpyAsync(out->hoff.data(), d_hoff, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost, st));
+    BATCH_HIP(f, hipStreamSynchronize(st));
+    f->st.head_bytes = head_bytes; f->st.down += head_bytes + (R + 1) * 8; f->st.t_heads = now() - t0;
     return 0;
 }

@@ -67,13 +67,14 @@ FETCHGL_PROGRAM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin"
 
 
 def fetch_file(path, gt, out=None, on_device=True, device=None, batch_records=None, messages=True, verbose=False, timeout=None, env=None,
-               device_inflate=None, resident=None, resident_max_bytes=None):
+               device_inflate=None, resident=None, resident_max_bytes=None, resident_bcf=None):
     """Runs fetchgl_hip -i `path` -gt `gt` [-o `out`] as a fresh child process and returns (returncode, stdout, stderr) as text;
     the CSV is in stdout, or in `out` when that is given.  on_device=False reads on the host and touches no GPU; on_device=True
     without a GPU fails (returncode 1): there is no fallback.  device_inflate=True inflates a BGZF file's members on the GPU
     (--device-inflate 1, also under on_device=False; any other file is read by zlib as without it); resident=True (with device_inflate
     and on_device) leaves the inflated text of a BGZF VCF in GPU memory and parses it there (--resident 1), resident_max_bytes bounds
-    what it may take.  A missing program is an error (build the package first)."""
+    what it may take; resident_bcf=True (with resident) does the same for a BGZF BCF file, whose records are walked on the GPU
+    (--resident-bcf 1).  A missing program is an error (build the package first)."""
     if not os.path.exists(FETCHGL_PROGRAM):
         raise FileNotFoundError("%s is not built (make -C vcfgl_amd/csrc all)" % FETCHGL_PROGRAM)
     cmd = [FETCHGL_PROGRAM, "-i", str(path), "-gt", str(gt), "--on-device", "1" if on_device else "0", "--messages", "1" if messages else "0"]
@@ -89,6 +90,8 @@ def fetch_file(path, gt, out=None, on_device=True, device=None, batch_records=No
         cmd += ["--resident", "1" if resident else "0"]
     if resident_max_bytes is not None:
         cmd += ["--resident-max-bytes", str(int(resident_max_bytes))]
+    if resident_bcf is not None:
+        cmd += ["--resident-bcf", "1" if resident_bcf else "0"]
     if verbose:
         cmd += ["--verbose", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
