@@ -3,6 +3,8 @@
 # vgl_sample_seg.hip alone (the k_sample_seg kernels; Makefile: SEGFLAGS); A/B timing with tools/ab_time.sh
 # The options REPLACE the Makefile's SEGFLAGS, so name its scheduler strategy again where it is to stay, e.g. the pool loop of two attempts per iteration:
 #   tools/ab_build_seg.sh attempts -mllvm -amdgpu-sched-strategy=iterative-minreg -DVGL_POOL_HALVES=0
+# or the two half-steps without carried lanes:
+#   tools/ab_build_seg.sh nocarry -mllvm -amdgpu-sched-strategy=iterative-minreg -DVGL_POOL_CARRY=0
 set -eu
 name=$1; shift || true
 tmp=$(mktemp -d)

@@ -24,7 +24,7 @@ sim.lib.vgl_dbg_stamps.argtypes = [C.c_void_p, C.c_void_p]
 assert sim.lib.vgl_dbg_stamps(sim.ctx, out) == 0
 w = out[0]
 names = ["waves", "cycles/wave", "streams+poisson", "owner(bases)", "pool(beta)", "flush", "pool iterations", "pool items",
-         "normal log-test blocks", "gamma log-test blocks", "finish blocks", "lanes with an item", "lanes finishing", "lanes holding"]
+         "normal log-test blocks", "gamma log-test blocks", "finish blocks", "lanes with an item", "lanes finishing", "lanes holding", "lanes carried"]
 res = {}
 for n, v in zip(names, out):
     res[n] = v if n == "waves" else v / w
@@ -32,7 +32,7 @@ for n, v in zip(names, out):
 if mode == "2" and res["pool iterations"] > 0:
     it = res["pool iterations"]
     res["per_iteration"] = {"normal_test": res["normal log-test blocks"] / it, "gamma_test": res["gamma log-test blocks"] / it, "finish": res["finish blocks"] / it,
-                            "lanes_with_item": res["lanes with an item"] / it, "lanes_finishing": res["lanes finishing"] / it, "lanes_holding": res["lanes holding"] / it,
+                            "lanes_with_item": res["lanes with an item"] / it, "lanes_finishing": res["lanes finishing"] / it, "lanes_holding": res["lanes holding"] / it, "lanes_carried": res["lanes carried"] / it,
                             "iterations_per_item_at_64_lanes": 64.0 * it / max(res["pool items"], 1)}
     print("per iteration:", json.dumps(res["per_iteration"]))
     print(f"ideal iterations (items x lane-iterations per item / 64) vs actual: lane efficiency of the loop = "

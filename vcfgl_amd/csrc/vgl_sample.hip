@@ -140,6 +140,13 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
 #ifndef VGL_POOL_HALVES
 #define VGL_POOL_HALVES 3
 #endif
+    // VGL_POOL_CARRY: which of the builds with two half-steps let a lane whose item half-step 1 ended run half-step 2 on the item it claimed ahead
+    // ("carried lanes" below) -- the bits of VGL_POOL_HALVES (bit 0: LEAN 2, C3 6.96 -> 6.80 ms; bit 1: LEAN 4, qsi16 8.27 -> 8.12), effective only where that
+    // build runs the two half-steps.
+    // -DVGL_POOL_CARRY=0: half-step 2 idles behind a finish, as before (A/B timing: tools/ab_build_seg.sh)
+#ifndef VGL_POOL_CARRY
+#define VGL_POOL_CARRY 3
+#endif
 #ifdef VGL_POOL_F64
     constexpr bool F32 = false;
 #else
@@ -158,6 +165,8 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
     constexpr bool P16 = F32;                                         // (LEAN 2 and LEAN 3 without --precise-gl 1)
     constexpr int ISZ = P16 ? 2 : 4;                                  // bytes of an item's slot
     constexpr bool HALVES = F32 && !PREC && ((VGL_POOL_HALVES >> (LEAN == 2 ? 0 : (LEAN == 4 ? 1 : 2))) & 1) != 0;
+    // (not with mixed mean depths, DM 0: k_sample_seg<0, 1, 2> and <0, 2, 4>, which carry the general depth sampler, paid two more spilled registers each)
+    constexpr bool CARRY = HALVES && DM != 0 && (LEAN == 2 || LEAN == 4) && ((VGL_POOL_CARRY >> (LEAN == 2 ? 0 : 1)) & 1) != 0;
     constexpr bool SLIM = (LEAN == 1 || LEAN == 2);                  // default tag surface: none of the optional per-read state
     constexpr bool DUMP = (LEAN == 0);                               // a per-read dump (reads_out) may be asked for
 #ifdef VGL_TEST_HOOKS
@@ -184,7 +193,7 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
     uint64_t st_hap = 0, st_base = 0, st_qs = 0;
     // DBG only: per-phase cycle stamps
     unsigned long long c_t0 = 0, c_pois = 0, c_owner = 0, c_pool = 0, c_flush = 0, c_iter = 0, c_items = 0, c_tmp = 0;
-    unsigned long long c_ntest = 0, c_gtest = 0, c_finb = 0, c_lhave = 0, c_lfin = 0, c_lhold = 0;   // float32 pool loop: block executions and lane counts per iteration
+    unsigned long long c_ntest = 0, c_gtest = 0, c_finb = 0, c_lhave = 0, c_lfin = 0, c_lhold = 0, c_lcarry = 0;   // float32 pool loop: block executions and lane counts per iteration
     if (DBG) c_t0 = clock64();
     uint64_t err_thresh = P.err_thresh;
     // LEAN 4 (round 5, second session) = LEAN 3 for the common optional-tag surface -- strand draws AND quality sums, no --adjust-qs (-addQS / -addI16 with
@@ -657,7 +666,7 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                                 redo = und || (n_amb && dbg_redo_every && (l1 >> 8) % (uint32_t)(dbg_redo_every | (dbg_redo_every == 0)) == 0u);
                             }
                             const bool g_try0 = have && !hold && !(q_lo && (q_hi || slow_n));
-                            prefetch();
+                            prefetch();                                                 // (CARRY needs its results between the half-steps; asked for at the top of the iteration instead: no faster, docs/tried.md)
                             // gamma step (rng.h:139-145) on A
                             const float wA = __builtin_fmaf(ga2, xnA, 1.0f);
                             const float xsqA = xnA * xnA;
@@ -682,6 +691,27 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                             s_hi = hold ? s_hi : (g_try0 ? h3 : h2);
                             gxf = (acc1 && !stage1) ? val1 : gxf;
                             stage1 = (stage1 != acc1) && !redo;
+                            // Carried lanes (VGL_POOL_CARRY): a lane whose item half-step 1 ended -- finished, or handed to k_redo -- and that owns an item
+                            // claimed ahead runs half-step 2 on THAT item instead of sitting it out: the item's start state (its read's jump on its owner's
+                            // base, what the finish block set so far) is formed here from this iteration's prefetch, once for every lane, and tab_n and
+                            // base_n die here.  Half-step 1 has left such a lane at the first stage (stage1 false), so half-step 2 picks the first sampler's
+                            // constants; the finish block still sees the ended item in k, sk, fx and fy.
+                            // Results cannot change: an item's stream is addressed by (owner, read); the new item starts from exactly the state the finish
+                            // block would have set; half-step 2 commits only "rejected by q outright" or "accepted by q, in range and sure" and leaves
+                            // everything else to the next iteration's half-step 1.  So every item meets the same attempts with the same decisions -- only
+                            // the iteration in which an attempt is evaluated moves.
+                            // A lane without a next item has formed nx from whatever its prefetch read: `carry` gates every use of it.
+                            bool carry = false;
+                            uint32_t nx_lo = 0, nx_hi = 0;                              // the start state of the item claimed ahead
+                            if constexpr (CARRY) {
+                                aff52_step(tab_n, (uint32_t)base_n, (uint32_t)(base_n >> 32), nx_lo, nx_hi);
+                                // fin1 && have && !hold && kn < segT4; fin1 says the other two: acc1 holds them, and `redo` comes from a bounded test
+                                // (a full iteration: nobody holds; `und` only for a lane that needed the test) or from g_try0 out of range (never g_amb)
+                                carry = fin1 && kn < segT4;
+                                s_lo = fin1 ? nx_lo : s_lo;
+                                s_hi = fin1 ? nx_hi : s_hi;
+                                if (DBG) c_lcarry += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(carry));
+                            }
                             // Half-step 2, for a lane that is not held and whose read goes on: the next attempt and its gamma step from the state and the
                             // stage half-step 1 left (hence that stage's constants), committed only where float32 settles both without a bounded test --
                             // rejected outright by q (past two outputs), or accepted by q alone, in range and surely accepted by the gamma step (past
@@ -699,7 +729,7 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                             const float svB = pool32_sv(lcg52_top32(m2, n2));
                             const float u2B = pool32_u(lcg52_top32(m3, n3));
                             const float qB = pool32_q(ufB, svB);
-                            const bool run2 = have && !hold && !fin1;
+                            const bool run2 = (have && !hold && !fin1) || carry;
                             const bool rej2 = run2 && (qB > VGL_P32_QHI + VGL_P32_QBAND);
                             const float xnB = svB * __builtin_amdgcn_rcpf(ufB);
                             const float wB = __builtin_fmaf(gb2, xnB, 1.0f);
@@ -712,6 +742,8 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                             s_lo = acc2 ? m3 : (rej2 ? m2 : s_lo);
                             s_hi = acc2 ? n3 : (rej2 ? n2 : s_hi);
                             const bool fin2 = acc2 && stage1;
+                            // (CARRY: a lane that finishes its item HERE takes the next item's start state now, so that nx is dead before the finish block)
+                            if constexpr (CARRY) { s_lo = fin2 ? nx_lo : s_lo; s_hi = fin2 ? nx_hi : s_hi; }
                             fin = fin1 || fin2;
                             fx = gxf;                                                   // (the first deviate: this iteration's or an earlier one's)
                             fy = fin2 ? val2 : val1;
@@ -868,7 +900,9 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
                             } else
                             // ... as a float32 in the item's slot; NaN: undecided (k_redo draws the read)
                             *(lds_u32*)(uintptr_t)(576u + (uint32_t)k) = redo ? 0x7FC00000u : __float_as_uint(pf);
-                            aff52_step(tab_n, (uint32_t)base_n, (uint32_t)(base_n >> 32), s_lo, s_hi);     // the next item's stream: its read's jump on its owner's base
+                            // the next item's stream: its read's jump on its owner's base (CARRY: formed between the half-steps and taken there by every
+                            // finishing lane; a carried lane keeps the state, stage and first deviate half-step 2 left for that item)
+                            if constexpr (!CARRY) aff52_step(tab_n, (uint32_t)base_n, (uint32_t)(base_n >> 32), s_lo, s_hi);
                             k = kn;
                             asm volatile("" : "+v"(k));
                             asm volatile("ds_add_rtn_u32 %0, %1, %2" : "+v"(kn) : "v"(ctr_p), "v"(four_v) : "memory");
@@ -1246,7 +1280,7 @@ __device__ __forceinline__ void k_sample_body(const VglDevParams& P, const VglTi
             atomicAdd(&T.dbg[3], c_owner); atomicAdd(&T.dbg[4], c_pool); atomicAdd(&T.dbg[5], c_flush);
             atomicAdd(&T.dbg[6], c_iter); atomicAdd(&T.dbg[7], c_items);
             atomicAdd(&T.dbg[8], c_ntest); atomicAdd(&T.dbg[9], c_gtest); atomicAdd(&T.dbg[10], c_finb); atomicAdd(&T.dbg[11], c_lhave);
-            atomicAdd(&T.dbg[12], c_lfin); atomicAdd(&T.dbg[13], c_lhold);
+            atomicAdd(&T.dbg[12], c_lfin); atomicAdd(&T.dbg[13], c_lhold); atomicAdd(&T.dbg[14], c_lcarry);
         }
     }
 }
