@@ -18,12 +18,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "vcfgl_amd", "bin", "vcfgl_hip")
 
 
-def random_vcf(rng, path, binary):
-    N = int(rng.choice([1, 2, 5, 70]))
-    S = int(rng.integers(1, 25))
+def random_vcf(rng, path, binary, N=None, S=None, miss=None):
+    """(N samples, S records, the share of missing genotypes: drawn here unless the caller fixes them)"""
+    N = int(rng.choice([1, 2, 5, 70])) if N is None else N
+    S = int(rng.integers(1, 25)) if S is None else S
     length = S * 3 + 5
     pos = np.sort(rng.choice(np.arange(1, length), size=S, replace=False))
-    miss = float(rng.choice([0.0, 0.0, 0.1]))
+    miss = float(rng.choice([0.0, 0.0, 0.1])) if miss is None else miss
     with open(path, "w") as fh:
         fh.write("##fileformat=VCFv4.2\n##FILTER=<ID=PASS,Description=\"All filters passed\">\n")
         fh.write(f"##contig=<ID=chr7,length={length}>\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n")
@@ -196,10 +197,11 @@ def gvcf_expected(args, sites, tile, block_dps):
     return out
 
 
-def random_vcf_gvcf(rng, path, binary):
-    """few samples, runs of invariant sites: most records (and every site -explode adds) are homozygous for the reference allele"""
-    N = int(rng.choice([1, 2, 3, 6]))
-    S = int(rng.integers(2, 14))
+def random_vcf_gvcf(rng, path, binary, N=None, S=None):
+    """few samples, runs of invariant sites: most records (and every site -explode adds) are homozygous for the reference allele
+    (N samples, S records on the first contig: drawn here unless the caller fixes them)"""
+    N = int(rng.choice([1, 2, 3, 6])) if N is None else N
+    S = int(rng.integers(2, 14)) if S is None else S
     length = S * 4 + 10
     pos = np.sort(rng.choice(np.arange(1, length), size=S, replace=False))
     with open(path, "w") as fh:
