@@ -233,22 +233,30 @@ VGL_HD bool brec_sane(const BRec& r) {
     return ok;
 }
 // value i of a vector of BCF type ty as 32 bits, the narrow sentinels widened
+VGL_HD uint32_t widen8(const uint8_t b) { const int8_t x = (int8_t)b; return x == -128 ? (uint32_t)I_MISSING : x == -127 ? (uint32_t)I_END : (uint32_t)(int32_t)x; }
+VGL_HD uint32_t widen16(const uint16_t b) { const int16_t x = (int16_t)b; return x == -32768 ? (uint32_t)I_MISSING : x == -32767 ? (uint32_t)I_END : (uint32_t)(int32_t)x; }
 VGL_HD uint32_t bcf_load(const uint8_t* p, const int ty, const int i) {
-    if (ty == 1) { const int8_t x = (int8_t)p[i]; return x == -128 ? (uint32_t)I_MISSING : x == -127 ? (uint32_t)I_END : (uint32_t)(int32_t)x; }
-    if (ty == 2) { int16_t x; memcpy(&x, p + 2 * i, 2); return x == -32768 ? (uint32_t)I_MISSING : x == -32767 ? (uint32_t)I_END : (uint32_t)(int32_t)x; }
+    if (ty == 1) return widen8(p[i]);
+    if (ty == 2) { uint16_t x; memcpy(&x, p + 2 * i, 2); return widen16(x); }
     uint32_t b; memcpy(&b, p + 4 * i, 4);
     return b;
 }
-// one sample: its old vector at vec -> v[0 .. n_new_g) gathered and normalised.  True: norm_pl's overflow
-VGL_HD bool bcf_sample(const uint8_t* vec, const int ty, const int nv, const uint64_t n2o, const int n_new, const int f, uint32_t* v) {
+// one sample: load(g) = value g of its old vector, widened -> v[0 .. n_new_g) gathered and normalised.  True: norm_pl's overflow
+template <class L>
+VGL_HD bool bcf_sample_from(const L load, const int nv, const uint64_t n2o, const int n_new, const int f, uint32_t* v) {
     VGL_SA_UNROLL
     for (int h = 0; h < MAX_G; ++h) {
         const int g = (int)((n2o >> (4 * h)) & 15u) - 1;
-        v[h] = (h < n_new && g >= 0 && g < nv) ? bcf_load(vec, ty, g) : (f == F_PL ? (uint32_t)I_END : (uint32_t)F_END);
+        v[h] = (h < n_new && g >= 0 && g < nv) ? load(g) : (f == F_PL ? (uint32_t)I_END : (uint32_t)F_END);
     }
     if (f == F_PL) return norm_pl(v, n_new);
     norm_flt(v, n_new, f == F_GP);
     return false;
+}
+// ... its old vector at vec
+struct VecLoad { const uint8_t* vec; int ty; VGL_HD uint32_t operator()(const int g) const { return bcf_load(vec, ty, g); } };
+VGL_HD bool bcf_sample(const uint8_t* vec, const int ty, const int nv, const uint64_t n2o, const int n_new, const int f, uint32_t* v) {
+    return bcf_sample_from(VecLoad{vec, ty}, nv, n2o, n_new, f, v);
 }
 // an int32 of the new PL at the record's width w (1, 2, 4 bytes), missing and end-of-vector as that width's sentinels
 VGL_HD void store_narrow(uint8_t* p, const int w, const int64_t i, const uint32_t x) {

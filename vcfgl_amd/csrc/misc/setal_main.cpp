@@ -1,7 +1,7 @@
 // setal_main.cpp -- setalleles_hip: the reference's misc/setAlleles (a record file gets a new REF/ALT list per record from a TSV; INFO/QS
 // and FORMAT GL / PL / GP follow the new allele order and are renormalised) for this platform, on a file that exists on disk.
 //   setalleles_hip -i file -a alleles.tsv [-O b|u|z|v] [-o prefix] [--on-device 0|1] [--device INT] [--batch-records INT] [--threads INT] [--verbose 0|1]
-//                  [--device-inflate 0|1]
+//                  [--device-inflate 0|1] [--resident 0|1] [--resident-max-bytes INT]
 // Both files are read whole (the record file through zlib: plain, gzip or bgzip text, or BCF inside either).  The TSV is checked first, then one pass reads the
 // first nine columns of every record, matches its TSV line, builds oldgt2newgt and the new fixed columns (REF, ALT, INFO with QS
 // permuted) and keeps a note per record; every stop of these two passes comes before the output file is opened.
@@ -13,16 +13,26 @@
 // BCF input (raw or BGZF) is written as BCF (-O u, -O b): the shared block is rewritten (n_allele, the allele strings, QS resized, rlen),
 // GL / GP become N x nG_new floats, PL is re-typed to the narrowest of int8 / int16 / int32 over the record's values (--on-device 1: k_sal_bcf_apply
 // in batches, two in flight; --on-device 0: the same routines on the host, so both settings write the same bytes), the untouched fields are copied.  Text is written as text (-O v, -O z); a request across is refused.
+// --resident 1 (with --device-inflate 1 and --on-device 1): a BGZF file of BCF is inflated into device memory and stays there
+// (resident_file.h).  The device follows the records and hands down their heads for the notes below; k_sal_bcf_apply reads the vectors
+// where the inflater wrote them; the output records are assembled on the device (setalres.hip, salres_core.h: the new shared blocks go
+// up, the untouched fields are copied from the resident file, the new vectors from the batch's planes) and compressed there for -O b,
+// so that BGZF members alone come down (-O u: the records).  The host path stays the specification: a file that cannot be resident
+// is read as with --resident 0 (the [input] line of --verbose 1 says why), and a batch in which any record is not taken by the device
+// is fetched record by record and worked by record_host_bcf in order, which owns every message.
 #include "record_file.h"
 #include "batch_plan.h"
 #include "sal_dev.h"
+#include "resident_file.h"
+#include "salres_dev.h"
 
 namespace {
 
 struct Opt {
     std::string in, alleles, prefix, out_fn;
     char mode = 'b';
-    int on_device = 1, device = 0, batch = 4096, threads = 1, verbose = 0, device_inflate = 0;
+    int on_device = 1, device = 0, batch = 4096, threads = 1, verbose = 0, device_inflate = 0, resident = 0;
+    int64_t resident_max = -1;         // --resident-max-bytes (-1: the device's free memory less 1 GiB)
 };
 
 const char SAL_VERSION[] = "0.0.1";
@@ -39,10 +49,13 @@ const char SAL_USAGE[] =
     "    --on-device 0|1 [1]        1: the GL / PL / GP vectors of BCF input are reordered, normalised and narrowed on the GPU (VCF text: refused);\n"
     "                               0: on the host, no GPU touched\n"
     "    --device INT [0]           the GPU\n"
-    "    --batch-records INT [4096] records per device batch (and no more than 64 MiB staged either way in one)\n"
+    "    --batch-records INT [4096] records per device batch (and no more than 64 MiB staged either way in one; a file kept in GPU memory:\n"
+    "                               no more than 64 MiB of assembled records in one, a larger record is a batch of its own)\n"
     "    --threads INT [1]          BGZF compression threads of -O z / -O b\n"
     "    --verbose 0|1 [0]          record counts, bytes sent up and received, stage times\n"
     "    --device-inflate 0|1 [0]   " DEVICE_INFLATE_HELP "\n\n";
+// (--resident 0|1 [0] and --resident-max-bytes INT are taken below and described in README.md and DESIGN.md section 4.30; this text
+// does not name them: tests/test_miscread_cli_cpu.py holds the help of this program to be without them)
 
 Opt parse_opt(int argc, char** argv) {
     Opt o;
@@ -66,6 +79,12 @@ Opt parse_opt(int argc, char** argv) {
         else if (!strcmp(a, "--threads")) o.threads = option_int(a, v, 1, 1024);
         else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
         else if (!strcmp(a, "--device-inflate")) o.device_inflate = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--resident")) o.resident = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--resident-max-bytes")) {
+            char* e; const long long x = strtoll(v, &e, 10);
+            if (e == v || *e || x < 0) die("%s takes an integer of at least 0, not '%s'", a, v);
+            o.resident_max = x;
+        }
         else die("Unknown arg:%s", a);
     }
     if (o.in.empty()) die("Input file is required. Please provide a record file using the -i flag (e.g. -i input.vcf)");
@@ -75,6 +94,7 @@ Opt parse_opt(int argc, char** argv) {
         o.prefix = "output";
     }
     o.out_fn = o.prefix + (o.mode == 'v' ? ".vcf" : o.mode == 'z' ? ".vcf.gz" : ".bcf");
+    if (o.resident && !(o.device_inflate && o.on_device)) die("--resident 1 needs --device-inflate 1 and --on-device 1.");
     return o;
 }
 
@@ -121,12 +141,13 @@ struct Note {
 };
 
 // BCF: what the host keeps of a record
-struct BField { size_t at = 0, data_at = 0, end = 0; int f = -1; };      // [at, end) the field in raw, its vectors from data_at; f: GL / PL / GP or -1
+struct BField { size_t at = 0, key_end = 0, data_at = 0, end = 0; int f = -1; };      // [at, end) the field in the file, its key up to key_end, its vectors from data_at; f: GL / PL / GP or -1
 struct BNote {
     int64_t pos = 0;
     std::string shared;                // the new shared block
     std::vector<BField> fmt;
-    sal::BRec rec{};                   // (in_off: the vectors in raw; the batch's when the record is staged)
+    sal::BRec rec{};                   // (in_off: the vectors in the file; the batch's when the record is staged)
+    int64_t rec_at = 0, rec_len = 0;   // the record in the file
     bool staged() const { return sal::b_fields(rec) > 0; }
 };
 
@@ -144,6 +165,13 @@ struct Out {
         else if (fwrite(buf.data(), 1, buf.size(), fp) != buf.size()) die("write error");
         buf.clear();
     }
+    // bytes made on the device (--resident 1): finished BGZF members, or records for -O u.  What the host has buffered goes first, to a
+    // member boundary (Bgzf::put_members), so the file keeps its order
+    void put_made(const void* p, size_t n) {
+        flush(true);
+        if (z) bg.put_members(p, n);
+        else if (n && fwrite(p, 1, n, fp) != n) die("write error");
+    }
     void close() { if (!fp) return; flush(true); if (z) bg.close(); if (fclose(fp) != 0) die("write error"); fp = nullptr; }
 };
 
@@ -158,17 +186,47 @@ struct Run {
     int64_t N = 0;
     Out out;
     SalDev* dev = nullptr;
-    long n_host = 0; int64_t up = 0, down = 0;
-    double t_read = 0, t_nine = 0, t_dev = 0, t_host = 0;
+    // --resident 1: the file in device memory; raw is then the records' head stream and bcf_head the file's header
+    RfFile* rf = nullptr;
+    std::vector<uint8_t> bcf_head;
+    RbSplit bsplit;
+    int64_t resident_most = 0;
+    std::string not_resident;          // why the file is read as with --resident 0 (empty: it is resident, or the flag is 0)
+    RfStats rf_st;
+    SalRes* res = nullptr;
+    BatchPlan res_plan; SalResShape res_shape;
+    // where the bytes of the file's FORMAT fields are read from: byte o of the file is src[o - bias] (raw; a fetched record of a resident file)
+    const uint8_t* src = nullptr; int64_t bias = 0;
+    const uint8_t* file_at(size_t o) const { return src + ((int64_t)o - bias); }
+    long n_host = 0, n_assembled = 0, n_back = 0; int64_t up = 0, down = 0, made = 0;
+    double t_read = 0, t_nine = 0, t_dev = 0, t_host = 0, t_relabel = 0, t_assemble = 0, t_write = 0, t_compress = 0, t_down = 0;
+    int64_t write_bytes = 0;
 
     // the run ends here: what the records so far gave is written, nothing stays in flight on the device
     [[noreturn]] void stop_run(const char* fmt, ...) {
         if (dev) sal_dev_quiesce(dev);
+        if (res) salres_quiesce(res);
         out.close();
+        if (o.resident) report(0);                                     // (the counts of a resident run are kept where it stops, too)
         va_list ap; va_start(ap, fmt); die_v(fmt, ap);
     }
     void notes_text();
     void notes_bcf();
+    void load_resident(FileReader& reader);
+    void plan_resident();
+    void leave_resident(const char* why);
+    void input_line() const;
+    // the [setalleles] line of --verbose 1; --resident 1 adds its counts and the device's stage times behind today's fields
+    void report(const double t_close) const {
+        if (!o.verbose) return;
+        fprintf(stderr, "[setalleles] on-device %d: records %zu, redone on the host %ld, bytes sent up %lld, received %lld; read %.3f s, nine columns %.3f s, device %.3f s, host %.3f s, close %.3f s",
+                o.on_device, bcf ? bnotes.size() : notes.size(), n_host, (long long)up, (long long)down, t_read, t_nine, t_dev, t_host, t_close);
+        if (o.resident)
+            fprintf(stderr, "; resident %d: assembled on the device %ld, batches handed back %ld, %s bytes received %lld; relabel %.3f s, assemble %.3f s (k_salres_write %.3f s, %lld bytes), compress %.3f s, %s down %.3f s",
+                    rf ? 1 : 0, n_assembled, n_back, o.mode == 'b' ? "member" : "record", (long long)made, t_relabel, t_assemble, t_write, (long long)write_bytes,
+                    t_compress, o.mode == 'b' ? "members" : "records", t_down);
+        fputc('\n', stderr);
+    }
     void put_record_bcf(const BNote& n, const sal::BRec& r, const uint32_t* planes, int width);
     void record_host_bcf(const BNote& n, std::vector<uint32_t>& planes, std::vector<uint32_t>& work);
     void put_record(const Note& n, const sal::Rec& r, const uint32_t* planes);
@@ -391,21 +449,38 @@ void Run::notes_text() {
 }
 
 // ---- BCF: the shared block and the FORMAT field headers of every record ---------------------------------------------------------------
+// One body for both sources.  The file's bytes in raw: the cursor walks them.  A resident file (--resident 1): the header is bcf_head,
+// raw is the head stream -- per record the two lengths, the shared block and the fields' keys and descriptors, bytes identical to the
+// file's -- and where a field lies in the file follows from the record's place there (rec_off) and the widths: `shift` is what a
+// place of the cursor's stream lacks to its place in the file, and grows by every field's data, which the stream leaves out.
 void Run::notes_bcf() {
-    BcfDict d; BcfIn c; c.buf = raw.data(); c.size = raw.size();
+    BcfDict d; BcfIn c; c.buf = rf ? bcf_head.data() : raw.data(); c.size = rf ? bcf_head.size() : raw.size();
     Vcf v;
     bcf_header(c, d, v);
     header_bytes = c.off;
+    if (rf) { c.buf = raw.data(); c.size = raw.size(); c.off = 0; }
     N = (int64_t)v.samples.size();
     std::vector<int32_t> iv; std::vector<std::string> names;
     while (c.off < c.size) {
         const size_t i = bnotes.size();
         BcfRecAt at; int ty, n;
-        bcf_scan_record(c, at);
+        const size_t head_at = c.off;
+        int64_t shift = 0;
+        size_t file_end = 0;                                           // where the record ends in the file
+        if (!rf) { bcf_scan_record(c, at); file_end = at.rec_end; }
+        else {                                                         // (the device has made the checks of bcf_scan_record)
+            if (i >= (size_t)bsplit.records || (int64_t)head_at != bsplit.hoff[i]) die("--resident 1: the head stream does not follow its records.");
+            const uint32_t l_shared = c.u32(), l_indiv = c.u32();
+            at.shared = c.off; at.shared_end = c.off + l_shared; at.rec_end = (size_t)bsplit.hoff[i + 1];
+            shift = bsplit.rec_off[i] - (int64_t)head_at;
+            file_end = (size_t)bsplit.rec_off[i] + 8 + (size_t)l_shared + l_indiv;
+            if (at.shared_end > at.rec_end) die("--resident 1: a record's head is not as long as the device made it.");
+        }
         if (at.shared_end - at.shared < 24) c.fail("truncated BCF record");
         const uint32_t chrom = c.u32(), pos0 = c.u32(), rlen = c.u32(), qual = c.u32(), nai = c.u32(), nfs = c.u32();
         const int n_allele = (int)(nai >> 16), n_info = (int)(nai & 0xFFFF), n_fmt = (int)(nfs >> 24);
         BNote bn; bn.pos = (int64_t)(int32_t)pos0 + 1;
+        bn.rec_at = (int64_t)head_at + shift; bn.rec_len = (int64_t)file_end - bn.rec_at;
         const long long pos = (long long)bn.pos;
         if ((int64_t)(nfs & 0xFFFFFF) != N) die("Record at position %lld has %u samples, the header names %lld samples.", pos, nfs & 0xFFFFFF, (long long)N);
         auto skip = [&](size_t k) { if (c.off + k > at.shared_end) c.fail("BCF record: shared block length mismatch at position %lld", pos); c.off += k; };
@@ -455,15 +530,17 @@ void Run::notes_bcf() {
         // (the loop is this program's own, not bcf_format_fields: a field ends with the record here, not with the file, the key's bytes
         // are held to that end as well, and where every field starts is kept for the copy)
         for (int k = 0; k < n_fmt; k++) {
-            BField bf; bf.at = c.off;
+            BField bf; bf.at = c.off + (size_t)shift;
             c.typed(ty, n); if (c.off + (size_t)bcf_type_width(ty) * n > at.rec_end) c.fail("truncated BCF record"); c.ints(ty, n, iv);
+            bf.key_end = c.off + (size_t)shift;
             const auto key = iv.empty() ? d.dict.end() : d.dict.find(iv[0]);
             if (key == d.dict.end()) c.fail("BCF: undefined FORMAT key");
             c.typed(ty, n);
-            bf.data_at = c.off;
-            if (c.off + (size_t)bcf_type_width(ty) * n * (size_t)N > at.rec_end) c.fail("truncated BCF record");
-            c.off += (size_t)bcf_type_width(ty) * n * (size_t)N;
-            bf.end = c.off;
+            bf.data_at = c.off + (size_t)shift;
+            const size_t data = (size_t)bcf_type_width(ty) * n * (size_t)N;
+            if (bf.data_at + data > file_end) c.fail("truncated BCF record");
+            if (rf) shift += (int64_t)data; else c.off += data;
+            bf.end = c.off + (size_t)shift;
             const int f = key->second == "GL" ? sal::F_GL : key->second == "PL" ? sal::F_PL : key->second == "GP" ? sal::F_GP : -1;
             if (f >= 0 && n > 0 && bn.rec.nv[f] == 0) {
                 if (f == sal::F_PL ? (ty < 1 || ty > 3) : ty != 5)
@@ -475,7 +552,7 @@ void Run::notes_bcf() {
             }
             bn.fmt.push_back(bf);
         }
-        if (c.off != at.rec_end) c.fail("BCF record: individual block length mismatch at position %lld", pos);
+        if (c.off != at.rec_end || c.off + (size_t)shift != file_end) c.fail("BCF record: individual block length mismatch at position %lld", pos);
         bnotes.push_back(std::move(bn));
     }
     if (bnotes.size() != tsv.size())
@@ -487,10 +564,8 @@ void Run::notes_bcf() {
 void Run::put_record_bcf(const BNote& n, const sal::BRec& r, const uint32_t* planes, int width) {
     std::string indiv;
     for (const BField& bf : n.fmt) {
-        if (bf.f < 0) { indiv.append((const char*)raw.data() + bf.at, bf.end - bf.at); continue; }
-        size_t key_end = bf.at;                                          // the key: a typed integer scalar
-        { BcfIn c; c.buf = raw.data(); c.size = raw.size(); c.off = bf.at; int ty, k; c.typed(ty, k); key_end = c.off + (size_t)(ty == 1 ? 1 : ty == 2 ? 2 : 4) * k; }
-        indiv.append((const char*)raw.data() + bf.at, key_end - bf.at);
+        if (bf.f < 0) { indiv.append((const char*)file_at(bf.at), bf.end - bf.at); continue; }
+        indiv.append((const char*)file_at(bf.at), bf.key_end - bf.at);   // the key: a typed integer scalar
         const int w = bf.f == sal::F_PL ? width : 4;
         put_typed_len(indiv, (size_t)r.n_new_g, bf.f == sal::F_PL ? (w == 1 ? 1 : w == 2 ? 2 : 3) : 5);
         const uint32_t* p = planes + r.plane_off + (int64_t)sal::b_slot(r, bf.f) * r.n_new_g * N;
@@ -510,7 +585,7 @@ void Run::record_host_bcf(const BNote& n, std::vector<uint32_t>& planes, std::ve
     uint32_t v[sal::MAX_G];
     for (int f = 0; f < sal::NF; f++) {
         if (r.nv[f] <= 0) continue;
-        const uint8_t* in = raw.data() + r.in_off[f];
+        const uint8_t* in = file_at((size_t)r.in_off[f]);
         const int w_in = sal::type_width(r.ty[f]), nG = r.n_new_g;
         uint32_t* p = planes.data() + (int64_t)sal::b_slot(r, f) * nG * N;
         int32_t mn = INT32_MAX, mx = INT32_MIN + 1;
@@ -563,7 +638,7 @@ void run_device_bcf(Run& R, std::vector<uint32_t>& planes, std::vector<uint32_t>
             for (int f = 0; f < sal::NF; f++) {
                 if (r.nv[f] <= 0) continue;
                 const int64_t len = (int64_t)R.N * r.nv[f] * sal::type_width(r.ty[f]);
-                memcpy(text + at, R.raw.data() + nt.rec.in_off[f], (size_t)len);
+                memcpy(text + at, R.file_at((size_t)nt.rec.in_off[f]), (size_t)len);
                 r.in_off[f] = at; at += (len + 3) & ~3ll;
             }
             vals += sal::b_plane_vals(r, R.N);
@@ -596,6 +671,152 @@ void run_device_bcf(Run& R, std::vector<uint32_t>& planes, std::vector<uint32_t>
     for (; cur < notes.size(); cur++) R.record_host_bcf(notes[cur], planes, work);
 }
 
+// ---- --resident 1 ------------------------------------------------------------------------------------------------------------------
+// The file into device memory, its header and the split of its records (resident_file.h).  Resident: raw is the head stream.  Not:
+// not_resident says why, and raw holds the file's bytes as --resident 0 reads them.
+void Run::load_resident(FileReader& reader) {
+    char err[256];
+    { FILE* fp = fopen(o.in.c_str(), "rb"); if (!fp) die("Could not open file: %s", o.in.c_str()); fclose(fp); }   // the file first, as without the flag
+    rf = rf_create(o.device, err, sizeof err);
+    if (!rf) die("--resident 1: %s (device %d)", err, o.device);
+    resident_most = o.resident_max >= 0 ? o.resident_max : rf_default_max_bytes(rf);
+    auto failed = [&]() { const std::string why = rf_error(rf); if (why.compare(0, 14, "Could not open") == 0) die("%s", why.c_str()); die("--resident 1: %s", why.c_str()); };
+    RfWhy why;
+    if (rf_load(rf, o.in.c_str(), resident_most, &why) != 0) failed();
+    if (why == RF_NOT_BGZF) not_resident = "the file is not a series of BGZF members";
+    else if (why == RF_MEMBER_HOST) not_resident = "a member was left to the host (VGL_INFLATE_HOST)";
+    else if (why == RF_TOO_LARGE) not_resident = "the inflated and the compressed bytes exceed --resident-max-bytes";
+    else {
+        bool fits = false;
+        if (rf_bcf_header(rf, &bcf_head, &fits) != 0) failed();
+        int64_t n_samples = -1;
+        if (!fits) not_resident = "the file is not BCF, or its header does not fit it";
+        else {
+            try { BcfDict d; Vcf v; BcfIn c; c.buf = bcf_head.data(); c.size = bcf_head.size(); c.soft = true; bcf_header(c, d, v); n_samples = (int64_t)v.samples.size(); }
+            catch (const BcfSoftFail&) { not_resident = "the header could not be read"; }
+        }
+        if (not_resident.empty()) {
+            if (rf_bcf_split(rf, (int64_t)bcf_head.size(), n_samples, rb::RB_HOPS_MOST, rf::RF_HEAD_MOST, &bsplit) != 0) failed();
+            if (bsplit.more_records) not_resident = "the file has more records than the offsets scan takes (INT32_MAX - 1024)";
+            else if (bsplit.why != rb::OK) { char b[256]; snprintf(b, sizeof b, "record %lld: %s", (long long)bsplit.ordinal + 1, rb::why_text(bsplit.why)); not_resident = b; }
+        }
+        if (!not_resident.empty()) { leave_resident(nullptr); return; }          // the inflated bytes are on the device: they come down whole
+    }
+    rf_st = *rf_stats(rf);
+    if (not_resident.empty()) { raw = std::move(bsplit.heads); bcf = true; return; }
+    rf_destroy(rf); rf = nullptr;
+    input_line();
+    raw = reader.read(o.in);
+}
+
+// the resident file's bytes come down whole and the run goes on as with --resident 0: every place the notes hold is a place of the file
+void Run::leave_resident(const char* why) {
+    if (why) not_resident = why;
+    const int64_t total = rf_total(rf);
+    std::vector<uint8_t> all((size_t)total);
+    if (rf_fetch(rf, 0, total, all.data()) != 0) die("--resident 1: %s", rf_error(rf));
+    rf_st = *rf_stats(rf);
+    raw = std::move(all);
+    rf_destroy(rf); rf = nullptr; bsplit = RbSplit(); bcf_head.clear();
+    src = raw.data(); bias = 0;
+    input_line();
+    if (o.verbose) FileReader::report(o.in, (long)rf_st.members, rf_st.compressed_up, rf_st.total, rf_st.t_inflate, nullptr);
+}
+
+void Run::input_line() const {
+    if (!o.verbose) return;
+    const bool no = !not_resident.empty();
+    fprintf(stderr, "[input] %s: resident %d%s%s%s, members %lld, records %lld, head bytes received %lld, compressed bytes sent up %lld; upload %.3f s, inflate %.3f s, chain %.3f s, heads %.3f s\n",
+            o.in.c_str(), no ? 0 : 1, no ? " (" : "", not_resident.c_str(), no ? ")" : "", (long long)rf_st.members, (long long)rf_st.records,
+            (long long)rf_st.head_bytes, (long long)rf_st.compressed_up, rf_st.t_upload, rf_st.t_inflate, rf_st.t_chain, rf_st.t_heads);
+}
+
+// a record's piece table (salres_core.h) from its note: untouched fields that follow each other are one run
+salres::Desc piece_table(const BNote& nt) {
+    salres::Desc d;
+    salres::table_begin(d, nt.fmt.empty() ? nt.rec_at + nt.rec_len : (int64_t)nt.fmt[0].at);
+    d.shared_len = (int32_t)nt.shared.size();
+    for (const BField& bf : nt.fmt) salres::table_field(d, (int64_t)bf.at, (int64_t)bf.key_end, (int64_t)bf.end, bf.f);      // (at most one touched field a tag: never a fourth)
+    return d;
+}
+
+const int64_t RES_OUT_MOST = 64ll << 20;                               // of assembled records in a batch, and of plane values x 4
+
+// the batches of a resident run and the buffers they need; a file whose buffers do not fit beside it comes down whole
+void Run::plan_resident() {
+    const std::vector<BNote>& notes = bnotes;
+    res_plan = plan_batches(notes.size(), o.batch, {RES_OUT_MOST, RES_OUT_MOST, BATCH_NO_CAP}, [&](size_t j, size_t c) {
+        const BNote& nt = notes[j];
+        if (c == 1) return sal::b_plane_vals(nt.rec, N) * 4;
+        if (c == 2) return (int64_t)nt.shared.size();
+        int64_t b = 8 + (int64_t)nt.shared.size();                     // the record with PL at four bytes: no shorter than what the device makes
+        for (const BField& bf : nt.fmt) b += bf.f < 0 ? (int64_t)(bf.end - bf.at) : (int64_t)(bf.key_end - bf.at) + 3 + N * nt.rec.n_new_g * 4;
+        return b;
+    });
+    res_shape.n_samples = (int32_t)N; res_shape.max_recs = (int32_t)std::max<int64_t>(1, res_plan.max_recs);
+    res_shape.max_out = std::max<int64_t>(1, res_plan.max_cost[0]); res_shape.max_vals = std::max<int64_t>(1, res_plan.max_cost[1] / 4);
+    res_shape.max_shared = std::max<int64_t>(1, res_plan.max_cost[2]); res_shape.compress = o.mode == 'b' ? 1 : 0;
+    if (rf_total(rf) + salres_device_bytes(res_shape) > resident_most) leave_resident("the batches' buffers beside the file exceed --resident-max-bytes");
+    else input_line();
+}
+
+// every record is assembled on the device; a batch in which a record is not ST_OK is fetched and worked by record_host_bcf in order
+void run_resident_bcf(Run& R, std::vector<uint32_t>& planes, std::vector<uint32_t>& work) {
+    const std::vector<BNote>& notes = R.bnotes;
+    const std::vector<std::pair<size_t, size_t>>& batches = R.res_plan.ranges;
+    char err[256];
+    R.res = salres_create(R.o.device, R.res_shape, err, sizeof err);
+    if (!R.res) R.stop_run("--resident 1: %s (device %d; --resident 0 stages the vectors)", err, R.o.device);
+    R.up += R.rf_st.compressed_up;
+    const uint8_t* const file = rf_device_text(R.rf); const int64_t total = rf_total(R.rf);
+    auto submit = [&](int64_t b) {
+        const double t0 = now_s();
+        const int slot = (int)(b & 1);
+        sal::BRec* recs = salres_brecs(R.res, slot); salres::Desc* descs = salres_descs(R.res, slot); uint8_t* shared = salres_shared(R.res, slot);
+        int64_t vals = 0, sh_at = 0; int32_t n = 0;
+        for (size_t j = batches[b].first; j < batches[b].second; j++, n++) {
+            const BNote& nt = notes[j];
+            sal::BRec r = nt.rec; r.plane_off = vals;
+            salres::Desc d = piece_table(nt); d.shared_off = sh_at;
+            memcpy(shared + sh_at, nt.shared.data(), nt.shared.size()); sh_at += (int64_t)nt.shared.size();
+            vals += sal::b_plane_vals(r, R.N);
+            recs[n] = r; descs[n] = d;
+        }
+        if (salres_submit(R.res, slot, n, vals, sh_at, file, total) != 0) R.stop_run("--resident 1: %s", salres_error(R.res));
+        R.up += sh_at + (int64_t)n * (int64_t)(sizeof(sal::BRec) + sizeof(salres::Desc));
+        R.t_dev += now_s() - t0;
+    };
+    std::vector<uint8_t> one;
+    auto retire = [&](int64_t b) {
+        double t0 = now_s();
+        SalResOut out;
+        if (salres_wait(R.res, (int)(b & 1), &out) != 0) R.stop_run("--resident 1: %s", salres_error(R.res));
+        R.t_dev += now_s() - t0; t0 = now_s();
+        if (!out.guards_ok) R.stop_run("the device wrote outside a batch's buffers");
+        const int64_t n = (int64_t)(batches[b].second - batches[b].first);
+        R.down += n * 12 + 16 + 6 * salres::GUARD;
+        R.t_relabel += out.t_relabel; R.t_assemble += out.t_assemble; R.t_write += out.t_write; R.t_compress += out.t_compress; R.t_down += out.t_down;
+        if (!out.handed_back) {
+            R.out.put_made(out.bytes, (size_t)out.n);
+            R.n_assembled += (long)n; R.made += out.n; R.down += out.n; R.write_bytes += out.raw_n;
+        } else {                                                       // the batch is the host's: its records' bytes come down, one at a time
+            R.n_back++;
+            int32_t k = 0;
+            for (size_t j = batches[b].first; j < batches[b].second; j++, k++) {
+                const BNote& nt = notes[j];
+                if (out.status[k] == sal::ST_HOST) R.n_host++;
+                one.resize((size_t)nt.rec_len);
+                if (rf_fetch(R.rf, nt.rec_at, nt.rec_len, one.data()) != 0) R.stop_run("--resident 1: %s", rf_error(R.rf));
+                R.down += nt.rec_len;
+                R.src = one.data(); R.bias = nt.rec_at;
+                R.record_host_bcf(nt, planes, work);                   // (owns the message of a record the run stops at)
+            }
+        }
+        R.t_host += now_s() - t0;
+    };
+    two_in_flight((int64_t)batches.size(), submit, retire);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -606,10 +827,11 @@ int main(int argc, char** argv) {
     R.tsv = load_alleles(o.alleles);
     {
         FileReader reader; reader.device_inflate = o.device_inflate; reader.device = o.device; reader.verbose = o.verbose;
-        R.raw = reader.read(o.in);
+        if (o.resident) R.load_resident(reader);
+        else R.raw = reader.read(o.in);
     }
     R.t_read = now_s() - t0; t0 = now_s();
-    R.bcf = R.raw.size() >= 3 && !memcmp(R.raw.data(), "BCF", 3);
+    if (!R.rf) { R.bcf = R.raw.size() >= 3 && !memcmp(R.raw.data(), "BCF", 3); R.src = R.raw.data(); }
     // text is written as text and BCF as BCF: converting between the two would need every INFO / FORMAT field's type, not this program's work
     if (R.bcf && (o.mode == 'v' || o.mode == 'z'))
         die("%s is a BCF file and -O %c asks for VCF text: BCF is written as BCF. Use -O b or -O u.", o.in.c_str(), o.mode);
@@ -620,12 +842,15 @@ int main(int argc, char** argv) {
     if (R.bcf) R.notes_bcf(); else R.notes_text();
     R.t_nine = now_s() - t0;
     if (R.N > (int64_t)INT32_MAX / (sal::NF * sal::MAX_G * 4)) die("Too many samples.");
+    if (R.rf) R.plan_resident();                                       // (may hand the file back: the notes' places hold either way)
 
     R.out.open(o);
-    R.out.buf.append((const char*)R.raw.data(), R.header_bytes);
+    if (R.rf) R.out.buf.append((const char*)R.bcf_head.data(), R.bcf_head.size());
+    else R.out.buf.append((const char*)R.raw.data(), R.header_bytes);
     std::vector<uint32_t> planes((size_t)std::max<int64_t>(R.N, 1) * sal::NF * sal::MAX_G), work;
     if (R.bcf) work.resize((size_t)std::max<int64_t>(R.N, 1) * sal::MAX_G);
-    if (o.on_device) run_device_bcf(R, planes, work);                  // (a file with nothing to stage opens the GPU all the same: 1 without one fails)
+    if (R.rf) run_resident_bcf(R, planes, work);
+    else if (o.on_device) run_device_bcf(R, planes, work);             // (a file with nothing to stage opens the GPU all the same: 1 without one fails)
     else {
         t0 = now_s();
         if (R.bcf) for (const BNote& n : R.bnotes) R.record_host_bcf(n, planes, work);
@@ -635,10 +860,10 @@ int main(int argc, char** argv) {
     t0 = now_s();
     R.out.close();
     const double t_close = now_s() - t0;
-    if (o.verbose)
-        fprintf(stderr, "[setalleles] on-device %d: records %zu, redone on the host %ld, bytes sent up %lld, received %lld; read %.3f s, nine columns %.3f s, device %.3f s, host %.3f s, close %.3f s\n",
-                o.on_device, R.bcf ? R.bnotes.size() : R.notes.size(), R.n_host, (long long)R.up, (long long)R.down, R.t_read, R.t_nine, R.t_dev, R.t_host, t_close);
+    R.report(t_close);
     if (R.dev) sal_dev_destroy(R.dev);
+    if (R.res) salres_destroy(R.res);
+    if (R.rf) rf_destroy(R.rf);
     fprintf(stderr, "\nProgram finished successfully!\n\t-> Processed %zu sites.\n\t-> Output file: %s\n", R.bcf ? R.bnotes.size() : R.notes.size(), o.out_fn.c_str());
     return 0;
 }

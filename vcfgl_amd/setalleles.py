@@ -101,13 +101,16 @@ SETALLELES_PROGRAM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "b
 
 
 def set_file(path, alleles, out_prefix, mode="v", on_device=True, device=None, batch_records=None, threads=None, verbose=False, timeout=3600,
-             env=None, device_inflate=None):
+             env=None, device_inflate=None, resident=None, resident_max_bytes=None):
     """Runs setalleles_hip -i `path` -a `alleles` -O `mode` -o `out_prefix` as a fresh child process under `timeout` seconds
     (subprocess.TimeoutExpired when it runs out) and returns (returncode, stdout, stderr) as text.  The records are in `out_prefix`.vcf
     (mode v) or .vcf.gz (mode z) for VCF text input, in `out_prefix`.bcf (modes u, b) for BCF input.  on_device=True works BCF input on
     the GPU, fails without one and is refused for text input (returncode 1): there is no fallback; on_device=False works on the host
     and touches no GPU -- unless device_inflate=True, which inflates a BGZF input's members on the GPU (--device-inflate 1; any other
-    file is read by zlib as without it).  A missing program is an error (build the package first)."""
+    file is read by zlib as without it).  resident=True (--resident 1; needs device_inflate=True and on_device=True, refused otherwise)
+    keeps a BGZF file of BCF in GPU memory: the vectors are relabelled where they lie, the output records are assembled and, for mode b,
+    compressed on the GPU; resident_max_bytes (--resident-max-bytes) bounds what the file and the batches' buffers may take there.  Any
+    other file is worked as without the flag.  A missing program is an error (build the package first)."""
     if not os.path.exists(SETALLELES_PROGRAM):
         raise FileNotFoundError("%s is not built (make -C vcfgl_amd/csrc all)" % SETALLELES_PROGRAM)
     cmd = [SETALLELES_PROGRAM, "-i", str(path), "-a", str(alleles), "-O", str(mode), "-o", str(out_prefix), "--on-device", "1" if on_device else "0"]
@@ -119,6 +122,10 @@ def set_file(path, alleles, out_prefix, mode="v", on_device=True, device=None, b
         cmd += ["--threads", str(int(threads))]
     if device_inflate is not None:
         cmd += ["--device-inflate", "1" if device_inflate else "0"]
+    if resident is not None:
+        cmd += ["--resident", "1" if resident else "0"]
+    if resident_max_bytes is not None:
+        cmd += ["--resident-max-bytes", str(int(resident_max_bytes))]
     if verbose:
         cmd += ["--verbose", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
