@@ -8,6 +8,8 @@
 //                     (gtd::sample_true / gtd::sample_call, bounded by the region's end) and stores one byte per plane: true bases,
 //                     called bases (0xFF missing), GQ.  The status (an OR over the columns, and the column count against n_samples) is
 //                     stored by lane 0.  No atomics.
+//   k_gtd_bcf_decode  --bcf-direct 1, in k_gtd_parse's place: the same planes and status from the typed GT / GQ / PL vectors of a BCF
+//                     side (gtdbcf_core.h), 16 bytes a lane where GT is int8 pairs; a text side of a mixed pair is walked as above
 //   k_gtd_tally       k_disc_tally's shape: a workgroup of 16 wavefronts owns 64 consecutive samples over a run of records, a wavefront
 //                     takes a record (ST_OK ones only), its lanes the samples; counts go to an LDS histogram [cell][GQ][sample] of 16-bit
 //                     counters -- a counter belongs to one sample and a run has at most 32768 records, so none can wrap -- and once per
@@ -76,6 +78,120 @@ __global__ void __launch_bounds__(NT) k_gtd_parse(const ParseArgs A) {
         if (col >= N) return;
         uint32_t b, g;
         if (!gtd::sample_call(text, q, ce, r, b, g)) bad = 1; else { cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
+    });
+    bad = __any(bad) ? 1 : 0;
+    if (lane == 0) s_bad[wave] = bad;
+    __syncthreads();
+    if (t == 0) {
+        int B = 0;
+        for (int k = 0; k < NT / 64; k++) B |= s_bad[k];
+        if (cols_t != N || cols_c != N) B = 1;
+        A.status[rec] = B ? gtd::ST_HOST : gtd::ST_OK;
+    }
+}
+
+// ---- --bcf-direct 1: the planes from typed vectors ---------------------------------------------------------------------------------
+struct DecodeArgs {
+    const uint8_t* bytes; int64_t n_bytes;                             // the batch's staging: vectors of the BCF sides, text of the others
+    const gtd::Rec* recs; const gtd::BSide* sides;                     // [n_recs], [2 * n_recs] (truth, call)
+    int32_t n_recs, N;
+    uint8_t* tb; uint8_t* cb; uint8_t* gq; int32_t* status;
+};
+
+constexpr int WS = 8;                    // samples a lane takes at once in the wide form: 16 bytes of int8 GT pairs
+
+__device__ __forceinline__ void store8(uint8_t* __restrict__ p, const uint64_t v) {
+    if (((uintptr_t)p & 7u) == 0) { *reinterpret_cast<uint64_t*>(p) = v; return; }
+#pragma unroll
+    for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (8 * i));
+}
+__device__ __forceinline__ int32_t widen8(const uint32_t byte) {
+    const int8_t x = (int8_t)byte;
+    return x == -128 ? gtd::BCF_MISSING : x == -127 ? gtd::BCF_EOV : (int32_t)x;
+}
+
+// one BCF side of a record: the samples' bytes into `plane` (true or called bases) and, for a call, `gqp`.  Returns 1 when a sample
+// is not plain.  The common shape -- int8 GT, two values a sample, the vectors on a 16-byte boundary -- is read 16 bytes a lane, so
+// that a wavefront takes 1 KiB of consecutive bytes with one load and stores its 8 bytes a plane at once; everything else, and the
+// last samples of such a vector, goes a sample a lane through the per-value routines of gtdbcf_core.h (consecutive lanes still read
+// consecutive vectors).  The caller has checked the descriptor against the staged bytes (gtd::side_fits).
+template <bool CALL>
+__device__ __forceinline__ int decode_side(const uint8_t* __restrict__ bytes, const gtd::BSide& b, const gtd::Rec& r, const int32_t N,
+                                           uint8_t* __restrict__ plane, uint8_t* __restrict__ gqp) {
+    const int t = threadIdx.x;
+    int bad = 0;
+    auto one = [&](const int64_t s) {
+        uint32_t x = 0, g = 0;
+        if (CALL) { if (!gtd::bcf_sample_call(bytes, b, s, r.gq_mode, r.nG, x, g)) bad = 1; plane[s] = (uint8_t)x; gqp[s] = (uint8_t)g; }
+        else { if (!gtd::bcf_sample_true(bytes, b, s, x)) bad = 1; plane[s] = (uint8_t)x; }
+    };
+    const uint8_t* __restrict__ gt = bytes + b.gt_off;
+    if (b.gt_type == 1 && b.gt_n == 2 && ((uintptr_t)gt & 15u) == 0) {
+        for (int64_t s0 = (int64_t)t * WS; s0 < N; s0 += (int64_t)NT * WS) {
+            if (s0 + WS > N) { for (int64_t s = s0; s < N; s++) one(s); continue; }
+            const uint4 v = *reinterpret_cast<const uint4*>(gt + 2 * s0);          // [gt + 2 s0, + 16) lies inside the N pairs
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            uint64_t o0 = 0, o1 = 0;
+#pragma unroll
+            for (int i = 0; i < WS; i++) {
+                const uint32_t h = w[i >> 1] >> (16 * (i & 1));
+                const int32_t x0 = widen8(h & 0xFFu), x1 = widen8((h >> 8) & 0xFFu);
+                int a0 = 0, a1 = 0; uint32_t x = 0, g = 0;
+                bool ok = x0 != gtd::BCF_EOV && x1 != gtd::BCF_EOV && gtd::gt_pair(x0, x1, a0, a1);
+                if (ok) ok = CALL ? gtd::call_of(bytes, b, s0 + i, r.gq_mode, r.nG, a0, a1, x, g) : gtd::true_of(b, a0, a1, x);
+                if (!ok) bad = 1;
+                o0 |= (uint64_t)(x & 0xFFu) << (8 * i); o1 |= (uint64_t)(g & 0xFFu) << (8 * i);
+            }
+            store8(plane + s0, o0);
+            if (CALL) store8(gqp + s0, o1);
+        }
+    } else {
+        for (int64_t s = t; s < N; s += NT) one(s);
+    }
+    return bad;
+}
+
+// One workgroup of 256 lanes per record, the truth side and then the call side.  A BCF side (BSide::have) is decoded from its vectors,
+// a text side is walked as k_gtd_parse walks it; the status is the OR of both.  Every descriptor is checked against the staged byte
+// count before a byte is read; a record that fails the check is ST_HOST.  No atomics.
+__global__ void __launch_bounds__(NT) k_gtd_bcf_decode(const DecodeArgs A) {
+    __shared__ int32_t s_tot[2][NT / 64];
+    __shared__ int32_t s_bad[NT / 64];
+    const int rec = blockIdx.x;
+    if (rec >= A.n_recs) return;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const gtd::Rec r = A.recs[rec];
+    const gtd::BSide T = A.sides[2 * (size_t)rec], C = A.sides[2 * (size_t)rec + 1];
+    const int32_t N = A.N;
+    const int64_t tl = r.t_off, te = r.t_off + r.t_len, cl = r.c_off, ce = r.c_off + r.c_len;
+    bool ok = r.t_nal >= 1 && r.c_nal >= 1;
+    if (T.have) ok = ok && T.nal == r.t_nal && gtd::side_fits(T, false, r.gq_mode, r.nG, N, A.n_bytes);
+    else ok = ok && r.t_off >= 0 && r.t_len >= 0 && te <= A.n_bytes && r.t_gti >= 0;
+    if (C.have) ok = ok && C.nal == r.c_nal && gtd::side_fits(C, true, r.gq_mode, r.nG, N, A.n_bytes);
+    else ok = ok && r.c_off >= 0 && r.c_len >= 0 && ce <= A.n_bytes && r.c_gti >= 0 && (r.gq_mode != gtd::GQ_TAG || r.c_gqi >= 0) &&
+              (r.gq_mode != gtd::GQ_PL || r.c_nal == 1 || (r.c_pli >= 0 && r.c_nal <= 5 && r.nG == gtd::n_genotypes(r.c_nal)));
+    if (!ok) {                                                         // (the host sends no such record; never read outside the bytes)
+        if (t == 0) A.status[rec] = gtd::ST_HOST;
+        return;
+    }
+    const uint8_t* __restrict__ bytes = A.bytes;
+    uint8_t* __restrict__ tb = A.tb + (size_t)rec * (size_t)N;
+    uint8_t* __restrict__ cb = A.cb + (size_t)rec * (size_t)N;
+    uint8_t* __restrict__ gq = A.gq + (size_t)rec * (size_t)N;
+    int bad = 0;
+    int32_t cols_t = N, cols_c = N;
+    if (T.have) bad |= decode_side<false>(bytes, T, r, N, tb, nullptr);
+    else cols_t = scan_columns(bytes, tl, te, s_tot, [&](const int32_t col, const int64_t q) {
+        if (col >= N) return;
+        uint32_t b;
+        if (!gtd::sample_true(bytes, q, te, r, b)) bad = 1; else tb[col] = (uint8_t)b;
+    });
+    __syncthreads();                                                   // (s_tot is used again)
+    if (C.have) bad |= decode_side<true>(bytes, C, r, N, cb, gq);
+    else cols_c = scan_columns(bytes, cl, ce, s_tot, [&](const int32_t col, const int64_t q) {
+        if (col >= N) return;
+        uint32_t b, g;
+        if (!gtd::sample_call(bytes, q, ce, r, b, g)) bad = 1; else { cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
     });
     bad = __any(bad) ? 1 : 0;
     if (lane == 0) s_bad[wave] = bad;
@@ -228,7 +344,10 @@ struct GtdDev : batchdev::BatchDev {
     int32_t N = 0, max_recs = 0; int64_t max_text = 0; int list = 0, per_site = 0;
     int64_t list_cap = 0, site_cap = 0;
     batchdev::DevMem<unsigned long long> d_table; int64_t table_len = 0;
+    int bcf = 0; double ms_stage = 0, ms_decode = 0;                   // --bcf-direct 1: the retired batches' device time
     struct Slot {
+        batchdev::PinMem<gtd::BSide> h_sides; batchdev::DevMem<gtd::BSide> d_sides;
+        batchdev::Event t0, k0, k1, t1;                                // (timing events: the batch's first copy, around the decode, its last kernel)
         batchdev::PinMem<uint8_t> h_text; batchdev::PinMem<gtd::Rec> h_recs;
         batchdev::PinMem<int32_t> h_status; batchdev::PinMem<int64_t> h_off; batchdev::PinMem<uint8_t> h_list, h_site;
         batchdev::DevMem<uint8_t> d_text; batchdev::DevMem<gtd::Rec> d_recs;
@@ -239,10 +358,10 @@ struct GtdDev : batchdev::BatchDev {
 
 const char* gtd_dev_error(GtdDev* d) { return d->err; }
 
-GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, char* err, size_t err_len) {
+GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, int bcf, char* err, size_t err_len) {
     if (n_samples <= 0 || max_recs <= 0 || max_text < 0) { snprintf(err, err_len, "bad batch shape"); return nullptr; }
     return batchdev::create<GtdDev>(device, err, err_len, [&](GtdDev* d) {
-        d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->list = list; d->per_site = per_site;
+        d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->list = list; d->per_site = per_site; d->bcf = bcf;
         d->list_cap = list ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
         d->site_cap = per_site ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
         d->table_len = vgl_disc_table_len(d->N);
@@ -256,6 +375,11 @@ GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t 
             if (!ok) return d->no_pinned();
             BATCH_HIP(d, s.d_text.alloc((size_t)d->max_text + LB));
             BATCH_HIP(d, s.d_recs.alloc(R * sizeof(gtd::Rec)));
+            if (d->bcf) {
+                if (!s.h_sides.alloc(d->device, 2 * R * sizeof(gtd::BSide))) return d->no_pinned();
+                BATCH_HIP(d, s.d_sides.alloc(2 * R * sizeof(gtd::BSide)));
+                for (batchdev::Event* e : {&s.t0, &s.k0, &s.k1, &s.t1}) BATCH_HIP(d, hipEventCreate(&e->h));
+            }
             BATCH_HIP(d, s.d_planes.alloc(3 * R * N));
             BATCH_HIP(d, s.d_status.alloc(R * 4));
             BATCH_HIP(d, s.d_len.alloc(2 * R * 8));
@@ -269,6 +393,8 @@ GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t 
 
 uint8_t* gtd_dev_text(GtdDev* d, int slot) { return d->slot[slot & 1].h_text; }
 gtd::Rec* gtd_dev_recs(GtdDev* d, int slot) { return d->slot[slot & 1].h_recs; }
+gtd::BSide* gtd_dev_sides(GtdDev* d, int slot) { return d->slot[slot & 1].h_sides; }
+void gtd_dev_times(GtdDev* d, double* stage_ms, double* decode_ms) { *stage_ms = d->ms_stage; *decode_ms = d->ms_decode; }
 
 int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
     GtdDev::Slot& s = d->slot[slot & 1];
@@ -276,12 +402,22 @@ int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
     if (n_recs == 0) return 0;
     hipStream_t st = d->stream;
     const size_t R = (size_t)n_recs, N = (size_t)d->N;
+    if (d->bcf) BATCH_HIP(d, hipEventRecord(s.t0, st));
     BATCH_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
     BATCH_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(gtd::Rec), hipMemcpyHostToDevice, st));
     uint8_t* tb = s.d_planes; uint8_t* cb = tb + (size_t)d->max_recs * N; uint8_t* gq = cb + (size_t)d->max_recs * N;
-    const ParseArgs P{s.d_text, text_bytes, s.d_recs, n_recs, d->N, tb, cb, gq, s.d_status};
-    hipLaunchKernelGGL(k_gtd_parse, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
-    BATCH_HIP(d, hipGetLastError());
+    if (d->bcf) {
+        BATCH_HIP(d, hipMemcpyAsync(s.d_sides, s.h_sides, 2 * R * sizeof(gtd::BSide), hipMemcpyHostToDevice, st));
+        BATCH_HIP(d, hipEventRecord(s.k0, st));
+        const DecodeArgs P{s.d_text, text_bytes, s.d_recs, s.d_sides, n_recs, d->N, tb, cb, gq, s.d_status};
+        hipLaunchKernelGGL(k_gtd_bcf_decode, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
+        BATCH_HIP(d, hipGetLastError());
+        BATCH_HIP(d, hipEventRecord(s.k1, st));
+    } else {
+        const ParseArgs P{s.d_text, text_bytes, s.d_recs, n_recs, d->N, tb, cb, gq, s.d_status};
+        hipLaunchKernelGGL(k_gtd_parse, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
+        BATCH_HIP(d, hipGetLastError());
+    }
     // the tally: about two workgroups per CU where the batch has them, runs of at least 16 records, never more than MAX_RUN
     const int groups = (d->N + SG - 1) / SG;
     int runs = 512 / groups;
@@ -305,6 +441,7 @@ int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
         BATCH_HIP(d, hipGetLastError());
         BATCH_HIP(d, hipMemcpyAsync(s.h_off, s.d_off, 2 * (R + 1) * 8, hipMemcpyDeviceToHost, st));
     }
+    if (d->bcf) BATCH_HIP(d, hipEventRecord(s.t1, st));
     BATCH_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, R * 4, hipMemcpyDeviceToHost, st));
     return d->end_submit(slot);
 }
@@ -313,6 +450,11 @@ int gtd_dev_wait(GtdDev* d, int slot, GtdBatchOut* out) {
     GtdDev::Slot& s = d->slot[slot & 1];
     if (d->begin_wait(slot) != 0) return -1;
     const size_t R = (size_t)d->head[slot & 1].n_recs;
+    if (d->bcf && R > 0) {
+        float a = 0, b = 0;
+        BATCH_HIP(d, hipEventElapsedTime(&a, s.t0, s.t1)); BATCH_HIP(d, hipEventElapsedTime(&b, s.k0, s.k1));
+        d->ms_stage += a; d->ms_decode += b;
+    }
     if (!(d->list || d->per_site) || R == 0) for (size_t i = 0; i < 2 * (R + 1); i++) s.h_off[i] = 0;
     const int64_t n_list = s.h_off[R], n_site = s.h_off[2 * R + 1];
     if (n_list < 0 || n_list > d->list_cap || n_site < 0 || n_site > d->site_cap) return d->refuse("a batch's listing is longer than its bound");

@@ -212,25 +212,26 @@ VGL_HD uint32_t site_len(const int64_t pos, const uint32_t i, const uint32_t cel
 // One record by the plain grammar, a column at a time: what k_gtd_parse does with a lane per column.  tb / cb / gq: N bytes each;
 // t_text / c_text: what Rec::t_off and Rec::c_off count from (the device has both regions in one text).
 // Returns ST_OK, or ST_HOST (the planes are then unspecified).
-inline int record_plain(const uint8_t* t_text, const uint8_t* c_text, const Rec& r, const int64_t N, uint8_t* tb, uint8_t* cb, uint8_t* gq) {
-    for (int side = 0; side < 2; side++) {
-        const uint8_t* text = side ? c_text : t_text;
-        const int64_t lb = side ? r.c_off : r.t_off, le = lb + (side ? r.c_len : r.t_len);
-        int64_t col = 0, q = lb;
-        for (;;) {
-            if (col < N) {
-                uint32_t b, g;
-                if (side == 0) { if (!sample_true(text, q, le, r, b)) return ST_HOST; tb[col] = (uint8_t)b; }
-                else { if (!sample_call(text, q, le, r, b, g)) return ST_HOST; cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
-            }
-            col++;
-            while (q < le && text[q] != '\t') q++;
-            if (q >= le) break;
-            q++;
+// side_plain: one of its two regions (side 0 the truth's into tb, side 1 the call's into cb / gq).
+inline int side_plain(const uint8_t* text, const int side, const Rec& r, const int64_t N, uint8_t* tb, uint8_t* cb, uint8_t* gq) {
+    const int64_t lb = side ? r.c_off : r.t_off, le = lb + (side ? r.c_len : r.t_len);
+    int64_t col = 0, q = lb;
+    for (;;) {
+        if (col < N) {
+            uint32_t b, g;
+            if (side == 0) { if (!sample_true(text, q, le, r, b)) return ST_HOST; tb[col] = (uint8_t)b; }
+            else { if (!sample_call(text, q, le, r, b, g)) return ST_HOST; cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
         }
-        if (col != N) return ST_HOST;
+        col++;
+        while (q < le && text[q] != '\t') q++;
+        if (q >= le) break;
+        q++;
     }
-    return ST_OK;
+    return col == N ? ST_OK : ST_HOST;
+}
+inline int record_plain(const uint8_t* t_text, const uint8_t* c_text, const Rec& r, const int64_t N, uint8_t* tb, uint8_t* cb, uint8_t* gq) {
+    if (side_plain(t_text, 0, r, N, tb, cb, gq) != ST_OK) return ST_HOST;
+    return side_plain(c_text, 1, r, N, tb, cb, gq);
 }
 
 }  // namespace gtd

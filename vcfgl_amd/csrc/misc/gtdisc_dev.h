@@ -3,6 +3,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "gtdisc_core.h"
+#include "gtdbcf_core.h"
 
 struct GtdDev;
 
@@ -15,8 +16,13 @@ struct GtdBatchOut {
     const uint8_t* site_text;
 };
 
-// n_samples, the most records and text bytes of a batch, the listing (gtd::LIST_*) and -perSite.  nullptr with the reason in err
-GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, char* err, size_t err_len);
+// n_samples, the most records and text bytes of a batch, the listing (gtd::LIST_*) and -perSite.  nullptr with the reason in err.
+// bcf 1 (--bcf-direct 1 with a BCF file in the pair): a batch also carries two gtd::BSide per record (truth, call), its bytes hold the
+// typed vectors of the BCF sides beside the text of the others, k_gtd_bcf_decode fills the planes in k_gtd_parse's place, and the
+// batches are timed by hipEvent pairs
+GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, int bcf, char* err, size_t err_len);
+gtd::BSide* gtd_dev_sides(GtdDev* d, int slot);                // bcf 1: the slot's 2 * max_recs side descriptors
+void gtd_dev_times(GtdDev* d, double* stage_ms, double* decode_ms);   // bcf 1: the retired batches' device time (copies up to the last kernel), and k_gtd_bcf_decode's share
 uint8_t* gtd_dev_text(GtdDev* d, int slot);                    // the slot's staging: max_text bytes, max_recs descriptors
 gtd::Rec* gtd_dev_recs(GtdDev* d, int slot);
 int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes);

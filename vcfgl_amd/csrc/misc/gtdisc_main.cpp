@@ -1,6 +1,7 @@
 // gtdisc_main.cpp -- gtdiscordance_hip: the reference's misc/gtDiscordance (a call file against -printTruth's file) for this platform.
-//   gtdiscordance_hip -t truth -i call -o out [-doGQ 0..8] [-perSite 0|1] [--on-device 0|1] [--device INT] [--batch-records INT] [--verbose 0|1] [--device-inflate 0|1]
-// Both files are read whole (plain, gzip or bgzip text through zlib; BCF records are decoded into the same text lines on the host), their
+//   gtdiscordance_hip -t truth -i call -o out [-doGQ 0..8] [-perSite 0|1] [--on-device 0|1] [--device INT] [--batch-records INT] [--verbose 0|1] [--device-inflate 0|1] [--bcf-direct 0|1]
+// Both files are read whole (plain, gzip or bgzip text through zlib; BCF records are decoded into the same text lines on the host, or
+// under --bcf-direct 1 left as they are and judged from their typed vectors by the rules of gtdbcf_core.h), their
 // first nine columns are parsed on the host and the records matched by the tool's sequential merge on POS.  Every matched pair is then
 // judged by the PLAIN grammar of gtdisc_core.h -- on the device in batches (--on-device 1: gtdisc.hip) or by the same routines on the
 // host (--on-device 0) -- and a record outside that grammar is redone whole by the permissive reader below, which owns every message.
@@ -15,7 +16,7 @@ namespace {
 
 struct Opt {
     std::string truth, call, out;
-    int do_gq = 0, per_site = 0, on_device = 1, device = 0, batch = 4096, verbose = 0, device_inflate = 0;
+    int do_gq = 0, per_site = 0, on_device = 1, device = 0, batch = 4096, verbose = 0, device_inflate = 0, bcf_direct = 0;
 };
 
 const char GTD_USAGE[] =
@@ -38,6 +39,7 @@ const char GTD_USAGE[] =
     "  --batch-records INT [4096] call records per device batch\n"
     "  --verbose 0|1 [0]         record counts, bytes sent up and stage times\n"
     "  --device-inflate 0|1 [0]  " DEVICE_INFLATE_HELP "\n"
+    "  --bcf-direct 0|1 [0]      1: a BCF file is not turned into text: its typed GT / GQ / PL vectors are judged as they lie in the file\n"
     "  -h, --help                print help\n\n";
 
 Opt parse_opt(int argc, char** argv) {
@@ -58,6 +60,7 @@ Opt parse_opt(int argc, char** argv) {
         else if (!strcmp(a, "--batch-records")) o.batch = option_int(a, v, 1, 1 << 24);
         else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
         else if (!strcmp(a, "--device-inflate")) o.device_inflate = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--bcf-direct")) o.bcf_direct = option_int(a, v, 0, 1);
         else die("Unknown arg:%s", a);
     }
     if (o.call.empty()) die("Input file not specified. Please use -i/--input <file>.");
@@ -67,73 +70,120 @@ Opt parse_opt(int argc, char** argv) {
 }
 
 // ---- the two files ---------------------------------------------------------------------------------------------------------------
+// where the integer GT / GQ / PL vectors of a record lie in the file's bytes (the last field of a key counts; a field of another type
+// counts as absent)
+struct BcfFields {
+    size_t at = 0, rec_end = 0;        // the record's first byte (its two lengths) and the byte behind it
+    int64_t off[3] = {0, 0, 0}; int type[3] = {0, 0, 0}, n[3] = {0, 0, 0}; bool have[3] = {false, false, false};      // GT, GQ, PL
+    bool as_text = false;              // --bcf-direct 1: the record's whole line stands in Input::text after all
+};
+enum { F_GT = 0, F_GQ = 1, F_PL = 2 };
+
 struct Input {
     std::vector<uint8_t> text;                                   // the file's text, or the lines made from its BCF records
     std::vector<std::string> header, samples;
     std::vector<std::pair<int64_t, int64_t>> lines;              // [begin, end) of every record line
+    // --bcf-direct 1, a BCF file: its bytes as read, its dictionaries and where every record's vectors lie
+    bool direct = false;
+    std::vector<uint8_t> bcf; BcfDict dict; std::vector<BcfFields> brecs;
     bool has_format(const char* id) const {
         const std::string k = std::string("##FORMAT=<ID=") + id + ",";
         for (const std::string& h : header) if (h.compare(0, k.size(), k) == 0) return true;
         return false;
     }
+    bool vectors(const size_t i) const { return direct && !brecs[i].as_text; }     // record i is judged from its typed vectors
 };
 
-// BCF records -> the lines a VCF writer would give GT, GQ and PL (the other columns are '.': nothing reads them)
-void bcf_lines(std::vector<uint8_t>& raw, Input& in) {
-    BcfDict d; BcfIn c; c.buf = raw.data(); c.size = raw.size();
-    Vcf v;
-    bcf_header(c, d, v);
-    in.header = v.header; in.samples = v.samples;
-    const size_t N = v.samples.size();
-    std::string out; std::vector<int32_t> gt, gq, pl; char num[16];
-    while (c.off < c.size) {
-        BcfRecAt at; int n_fmt;
-        bcf_scan_record(c, at);
-        Rec r;
-        bcf_shared(c, d, at, N, r, n_fmt);
-        int n_gt = 0, n_gq = 0, n_pl = 0; bool have_gt = false, have_gq = false, have_pl = false;
-        bcf_format_fields(c, d, n_fmt, N, [&](int, const std::string& key, int type, int n, size_t data_off) {
-            if (type < 1 || type > 3) return;
-            BcfIn v = c; v.off = data_off;                              // (the walker has checked that the vectors lie inside the file)
-            if (key == "GT") { v.ints(type, (int)(n * N), gt); n_gt = n; have_gt = true; }
-            else if (key == "GQ") { v.ints(type, (int)(n * N), gq); n_gq = n; have_gq = true; }
-            else if (key == "PL") { v.ints(type, (int)(n * N), pl); n_pl = n; have_pl = true; }
-        });
-        if (!have_gt) die("Could not find GT tag at position %ld.", r.pos0 + 1);
-        c.off = at.rec_end;
-        const int64_t begin = (int64_t)out.size();
-        out += r.chrom; out += '\t'; out += std::to_string(r.pos0 + 1); out += "\t.\t"; out += r.alleles[0]; out += '\t';
-        if (r.alleles.size() == 1) out += '.';
-        for (size_t a = 1; a < r.alleles.size(); a++) { if (a > 1) out += ','; out += r.alleles[a]; }
-        out += "\t.\t.\t.\tGT"; if (have_gq) out += ":GQ"; if (have_pl) out += ":PL";
-        auto put = [&](int32_t x) { if (x == INT32_MIN) out += '.'; else { snprintf(num, sizeof num, "%d", x); out += num; } };
-        for (size_t s = 0; s < N; s++) {
-            out += '\t';
-            int j = 0;
-            for (; j < n_gt && gt[s * n_gt + j] != INT32_MIN + 1; j++) {
-                const int32_t x = gt[s * n_gt + j];
-                if (j) out += (x & 1) ? '|' : '/';
-                if ((x >> 1) - 1 < 0) out += '.'; else put((x >> 1) - 1);
-            }
-            if (j == 0) out += '.';
-            if (have_gq) { out += ':'; if (n_gq < 1 || gq[s * n_gq] == INT32_MIN + 1) out += '.'; else put(gq[s * n_gq]); }
-            if (have_pl) {
-                out += ':';
-                int g = 0;
-                for (; g < n_pl && pl[s * n_pl + g] != INT32_MIN + 1; g++) { if (g) out += ','; put(pl[s * n_pl + g]); }
-                if (g == 0) out += '.';
-            }
+// the record at the cursor: its shared block -> r, its FORMAT field headers -> f; the cursor is left behind the record
+void bcf_walk(BcfIn& c, const BcfDict& d, const size_t N, Rec& r, BcfFields& f) {
+    BcfRecAt at; int n_fmt;
+    f.at = c.off;
+    bcf_scan_record(c, at);
+    bcf_shared(c, d, at, N, r, n_fmt);
+    bcf_format_fields(c, d, n_fmt, N, [&](int, const std::string& key, int type, int n, size_t data_off) {
+        if (type < 1 || type > 3) return;                               // (the walker has checked that the vectors lie inside the file)
+        const int k = key == "GT" ? F_GT : key == "GQ" ? F_GQ : key == "PL" ? F_PL : -1;
+        if (k < 0) return;
+        f.off[k] = (int64_t)data_off; f.type[k] = type; f.n[k] = n; f.have[k] = true;
+    });
+    if (!f.have[F_GT]) die("Could not find GT tag at position %ld.", r.pos0 + 1);
+    c.off = f.rec_end = at.rec_end;
+}
+// the first nine columns a VCF writer would give the record (the columns nothing reads are '.')
+void bcf_nine(const Rec& r, const BcfFields& f, std::string& out) {
+    out += r.chrom; out += '\t'; out += std::to_string(r.pos0 + 1); out += "\t.\t"; out += r.alleles[0]; out += '\t';
+    if (r.alleles.size() == 1) out += '.';
+    for (size_t a = 1; a < r.alleles.size(); a++) { if (a > 1) out += ','; out += r.alleles[a]; }
+    out += "\t.\t.\t.\tGT"; if (f.have[F_GQ]) out += ":GQ"; if (f.have[F_PL]) out += ":PL";
+}
+// its sample columns, each behind a tab
+void bcf_columns(const BcfIn& c, const BcfFields& f, const size_t N, std::string& out) {
+    std::vector<int32_t> vec[3]; char num[16];
+    for (int k = 0; k < 3; k++) if (f.have[k]) { BcfIn v = c; v.off = (size_t)f.off[k]; v.ints(f.type[k], (int)(f.n[k] * N), vec[k]); }
+    const std::vector<int32_t>& gt = vec[F_GT]; const std::vector<int32_t>& gq = vec[F_GQ]; const std::vector<int32_t>& pl = vec[F_PL];
+    const int n_gt = f.n[F_GT], n_gq = f.n[F_GQ], n_pl = f.n[F_PL];
+    auto put = [&](int32_t x) { if (x == INT32_MIN) out += '.'; else { snprintf(num, sizeof num, "%d", x); out += num; } };
+    for (size_t s = 0; s < N; s++) {
+        out += '\t';
+        int j = 0;
+        for (; j < n_gt && gt[s * n_gt + j] != INT32_MIN + 1; j++) {
+            const int32_t x = gt[s * n_gt + j];
+            if (j) out += (x & 1) ? '|' : '/';
+            if ((x >> 1) - 1 < 0) out += '.'; else put((x >> 1) - 1);
         }
-        in.lines.emplace_back(begin, (int64_t)out.size());
-        out += '\n';
+        if (j == 0) out += '.';
+        if (f.have[F_GQ]) { out += ':'; if (n_gq < 1 || gq[s * n_gq] == INT32_MIN + 1) out += '.'; else put(gq[s * n_gq]); }
+        if (f.have[F_PL]) {
+            out += ':';
+            int g = 0;
+            for (; g < n_pl && pl[s * n_pl + g] != INT32_MIN + 1; g++) { if (g) out += ','; put(pl[s * n_pl + g]); }
+            if (g == 0) out += '.';
+        }
     }
-    in.text.assign(out.begin(), out.end());
+}
+// the record at byte `at` of the file -> the line a VCF writer would give GT, GQ and PL (no newline)
+void bcf_one_line(const std::vector<uint8_t>& raw, const BcfDict& d, const size_t N, const size_t at, std::string& out) {
+    BcfIn c; c.buf = raw.data(); c.size = raw.size(); c.off = at;
+    Rec r; BcfFields f;
+    bcf_walk(c, d, N, r, f);
+    bcf_nine(r, f, out); bcf_columns(c, f, N, out);
 }
 
-Input read_input_file(FileReader& reader, const std::string& fn) {
+// BCF records -> text.  direct false: the lines of every record.  direct true (--bcf-direct 1): the file's bytes stay as read; the
+// text holds a record's first nine columns and a tab -- what parse_nine reads -- and its sample columns are written only on demand
+// (Input::line_of).  A record whose first nine columns would not stand where a reader of the line looks for them (a tab inside a
+// name), or whose line could pass 2 GiB, gets its whole line here as without the flag.
+void bcf_lines(std::vector<uint8_t>& raw, Input& in, const bool direct) {
+    BcfIn c; c.buf = raw.data(); c.size = raw.size();
+    Vcf v;
+    bcf_header(c, in.dict, v);
+    in.header = v.header; in.samples = v.samples;
+    const size_t N = v.samples.size();
+    std::string out;
+    while (c.off < c.size) {
+        Rec r; BcfFields f;
+        bcf_walk(c, in.dict, N, r, f);
+        const int64_t begin = (int64_t)out.size();
+        bcf_nine(r, f, out);
+        if (direct) {
+            int tabs = 0;
+            for (size_t q = (size_t)begin; q < out.size(); q++) tabs += out[q] == '\t';
+            const double bound = (double)N * (12.0 * ((double)f.n[F_GT] + 1.0 + (double)f.n[F_PL]) + 4.0);
+            f.as_text = tabs != 8 || bound > (double)(INT32_MAX / 2);
+        }
+        if (!direct || f.as_text) bcf_columns(c, f, N, out); else out += '\t';
+        in.lines.emplace_back(begin, (int64_t)out.size());
+        out += '\n';
+        if (direct) in.brecs.push_back(f);
+    }
+    in.text.assign(out.begin(), out.end());
+    if (direct) { in.direct = true; in.bcf = std::move(raw); }
+}
+
+Input read_input_file(FileReader& reader, const std::string& fn, const bool bcf_direct) {
     Input in;
     std::vector<uint8_t> raw = reader.read(fn);
-    if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) { bcf_lines(raw, in); return in; }
+    if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) { bcf_lines(raw, in, bcf_direct); return in; }
     in.text = std::move(raw);
     TextLines tl = scan_text(in.text);
     in.header = std::move(tl.header); in.samples = std::move(tl.samples); in.lines = std::move(tl.lines);
@@ -173,7 +223,7 @@ Fixed parse_nine(const Input& in, const size_t i, const char* which) {
 }
 
 // a call record and the truth record it is compared with
-struct Pair { size_t ci, ti; int32_t nsites1; gtd::Rec rec; };
+struct Pair { size_t ci, ti; int32_t nsites1; gtd::Rec rec; gtd::BSide tside, cside; };    // (a side with have == 0 is text; offsets of a BCF side count from the file's first byte)
 
 // ---- the run's state -------------------------------------------------------------------------------------------------------------
 struct Run {
@@ -189,6 +239,7 @@ struct Run {
     std::string list_buf, site_buf;
     GtdDev* dev = nullptr;
     long n_host = 0; int64_t text_up = 0;
+    long n_direct[2] = {0, 0}; int64_t vec_up = 0; double ms_stage = 0, ms_decode = 0; long n_batches = 0;      // --bcf-direct 1
     double t_read = 0, t_nine = 0, t_dev = 0, t_host = 0;
 
     void flush(bool all) {
@@ -242,13 +293,24 @@ bool host_gt(Span f, long& a0, long& a1) {
     return one(f.first, s, a0) && one(s + 1, f.second, a1);
 }
 
+// the sample columns of record i: where they stand in the text, or the line bcf_lines would have made of the record's vectors
+Span sample_columns(const Input& in, const size_t i, const Fixed& F, std::string& line) {
+    const char* t0 = (const char*)in.text.data();
+    if (!in.vectors(i)) return Span(t0 + F.s_off, t0 + F.s_off + F.s_len);
+    bcf_one_line(in.bcf, in.dict, in.samples.size(), in.brecs[i].at, line);
+    const char* col_at[10]; int nc;
+    nine_columns(line.data(), line.data() + line.size(), col_at, nc);
+    return nc < 9 ? Span(line.data() + line.size(), line.data() + line.size()) : Span(col_at[9], line.data() + line.size());
+}
+
 void Run::record_permissive(const Pair& p) {
     const Fixed& T = tf[p.ti]; const Fixed& C = cf[p.ci];
     const gtd::Rec& r = p.rec;
     const long long pos = (long long)r.pos;
     std::vector<Span> tc, cc;
-    const char* tt = (const char*)truth.text.data() + T.s_off; const char* ct = (const char*)call.text.data() + C.s_off;
-    split_cols(tt, tt + T.s_len, tc); split_cols(ct, ct + C.s_len, cc);
+    std::string t_line, c_line;                                    // (the line of a record that was judged from its vectors is written now)
+    const Span ts = sample_columns(truth, p.ti, T, t_line), cs = sample_columns(call, p.ci, C, c_line);
+    split_cols(ts.first, ts.second, tc); split_cols(cs.first, cs.second, cc);
     if (tc.size() != (size_t)N) stop_run("The truth record at position %lld has %zu sample columns, the header names %d samples.", pos, tc.size(), N);
     if (cc.size() != (size_t)N) stop_run("The call record at position %lld has %zu sample columns, the header names %d samples.", pos, cc.size(), N);
     std::vector<int> pl_gq;
@@ -305,13 +367,35 @@ void Run::record_permissive(const Pair& p) {
 // --on-device 0: the plain grammar by the routines the kernels run, a column at a time; the permissive reader for the rest
 void Run::record_host(const Pair& p, std::vector<uint8_t>& planes) {
     uint8_t* tb = planes.data(); uint8_t* cb = tb + N; uint8_t* gq = cb + N;
-    if (gtd::record_plain(truth.text.data(), call.text.data(), p.rec, N, tb, cb, gq) != gtd::ST_OK) { n_host++; record_permissive(p); return; }
+    int st;
+    if (!p.tside.have && !p.cside.have) st = gtd::record_plain(truth.text.data(), call.text.data(), p.rec, N, tb, cb, gq);
+    else {                                                           // a side at a time: the column walk for text, the typed vectors for BCF
+        st = p.tside.have ? gtd::bcf_side_plain(truth.bcf.data(), (int64_t)truth.bcf.size(), p.tside, false, p.rec.gq_mode, p.rec.nG, N, tb, cb, gq)
+                          : gtd::side_plain(truth.text.data(), 0, p.rec, N, tb, cb, gq);
+        if (st == gtd::ST_OK)
+            st = p.cside.have ? gtd::bcf_side_plain(call.bcf.data(), (int64_t)call.bcf.size(), p.cside, true, p.rec.gq_mode, p.rec.nG, N, tb, cb, gq)
+                              : gtd::side_plain(call.text.data(), 1, p.rec, N, tb, cb, gq);
+    }
+    if (st != gtd::ST_OK) { n_host++; record_permissive(p); return; }
     for (int32_t s = 0; s < N; s++) {
         if (cb[s] == gtd::CALL_MISSING) { call_missing(s); continue; }
         const uint32_t cell = gtd::classify(tb[s], cb[s]);
         count(s, cell, gq[s]);
         if (list || o.per_site) lines(p, s, cell, gq[s]);
     }
+}
+
+// the descriptor of record i of a file: its vectors where they are judged as they lie, have == 0 (text) otherwise
+gtd::BSide bcf_side(const Input& in, const size_t i, const int32_t nal, const uint64_t map) {
+    gtd::BSide b;
+    memset(&b, 0, sizeof b);
+    if (!in.vectors(i)) return b;
+    const BcfFields& f = in.brecs[i];
+    b.gt_off = f.off[F_GT]; b.gt_type = f.type[F_GT]; b.gt_n = f.n[F_GT];
+    if (f.have[F_GQ]) { b.gq_off = f.off[F_GQ]; b.gq_type = f.type[F_GQ]; b.gq_n = f.n[F_GQ]; b.have |= gtd::B_GQ; }
+    if (f.have[F_PL]) { b.pl_off = f.off[F_PL]; b.pl_type = f.type[F_PL]; b.pl_n = f.n[F_PL]; b.have |= gtd::B_PL; }
+    b.have |= gtd::B_GT; b.nal = nal; b.map = map;
+    return b;
 }
 
 // ---- the tables of the tool's lines 629-833 ------------------------------------------------------------------------------------------
@@ -369,27 +453,56 @@ void run_device(Run& R) {
     int64_t B = R.o.batch;
     const int64_t per_rec = (int64_t)N * ((R.list || R.o.per_site) ? gtd::LINE_BOUND : 3);
     B = std::max<int64_t>(1, std::min<int64_t>(B, (64ll << 20) / std::max<int64_t>(per_rec, 1)));
-    const BatchPlan plan = plan_batches(K, B, {BATCH_NO_CAP}, [&](size_t j, size_t) { return R.pairs[j].rec.t_len + (int64_t)R.pairs[j].rec.c_len; });
+    // --bcf-direct 1: a BCF side sends the vectors its record needs -- GT, GQ under GQ_TAG, PL under GQ_PL with more than one allele --
+    // each at a 16-byte boundary of the staging (so at a 4-byte one), where a lane can take several samples with one load
+    const bool direct = R.truth.direct || R.call.direct;
+    auto up16 = [](int64_t x) { return (x + 15) & ~(int64_t)15; };
+    auto vec_bytes = [&](int type, int32_t n) { return (int64_t)gtd::bcf_width(type) * n * N; };
+    auto needs = [](const gtd::BSide& b, const gtd::Rec& r, bool call, bool& gq, bool& pl) {
+        gq = call && r.gq_mode == gtd::GQ_TAG && (b.have & gtd::B_GQ); pl = call && r.gq_mode == gtd::GQ_PL && r.c_nal > 1 && (b.have & gtd::B_PL);
+    };
+    auto side_cost = [&](const Pair& p, bool call) -> int64_t {
+        const gtd::BSide& b = call ? p.cside : p.tside;
+        if (!b.have) return call ? p.rec.c_len : p.rec.t_len;
+        bool gq, pl; needs(b, p.rec, call, gq, pl);
+        return 16 + up16(vec_bytes(b.gt_type, b.gt_n)) + (gq ? 16 + up16(vec_bytes(b.gq_type, b.gq_n)) : 0) + (pl ? 16 + up16(vec_bytes(b.pl_type, b.pl_n)) : 0);
+    };
+    const BatchPlan plan = plan_batches(K, B, {BATCH_NO_CAP}, [&](size_t j, size_t) { return side_cost(R.pairs[j], false) + side_cost(R.pairs[j], true); });
     const std::vector<std::pair<size_t, size_t>>& batches = plan.ranges;     // blocks of B records: the text has no cap of its own
     const int64_t nb = (int64_t)batches.size();
     const int64_t max_text = std::max<int64_t>(1, plan.max_cost[0]);
     char err[256];
-    R.dev = gtd_dev_create(R.o.device, N, (int32_t)std::min<int64_t>(B, std::max<size_t>(K, 1)), max_text, R.list, R.o.per_site, err, sizeof err);
+    R.dev = gtd_dev_create(R.o.device, N, (int32_t)std::min<int64_t>(B, std::max<size_t>(K, 1)), max_text, R.list, R.o.per_site, direct ? 1 : 0, err, sizeof err);
     if (!R.dev) R.stop_run("--on-device 1: %s (device %d; --on-device 0 compares on the host)", err, R.o.device);
     auto submit = [&](int64_t b) {
         const double t0 = now_s();
         const int slot = (int)(b & 1);
         uint8_t* text = gtd_dev_text(R.dev, slot); gtd::Rec* recs = gtd_dev_recs(R.dev, slot);
-        int64_t at = 0; int32_t n = 0;
+        gtd::BSide* sides = direct ? gtd_dev_sides(R.dev, slot) : nullptr;
+        int64_t at = 0, vec = 0, txt = 0; int32_t n = 0;
+        auto vector_up = [&](const Input& in, int64_t& off, int type, int32_t n_val) {
+            const int64_t bytes = vec_bytes(type, n_val);
+            at = up16(at);
+            memcpy(text + at, in.bcf.data() + off, (size_t)bytes); off = at; at += bytes; vec += bytes;
+        };
         for (size_t j = batches[b].first; j < batches[b].second; j++, n++) {
             const Pair& p = R.pairs[j];
             gtd::Rec r = p.rec;
-            memcpy(text + at, R.truth.text.data() + p.rec.t_off, (size_t)r.t_len); r.t_off = at; at += r.t_len;
-            memcpy(text + at, R.call.text.data() + p.rec.c_off, (size_t)r.c_len); r.c_off = at; at += r.c_len;
+            gtd::BSide ts = p.tside, cs = p.cside; bool gq, pl;
+            if (ts.have) vector_up(R.truth, ts.gt_off, ts.gt_type, ts.gt_n);
+            else { memcpy(text + at, R.truth.text.data() + p.rec.t_off, (size_t)r.t_len); r.t_off = at; at += r.t_len; txt += r.t_len; }
+            if (cs.have) {
+                needs(cs, r, true, gq, pl);
+                vector_up(R.call, cs.gt_off, cs.gt_type, cs.gt_n);
+                if (gq) vector_up(R.call, cs.gq_off, cs.gq_type, cs.gq_n); else cs.have &= ~(uint32_t)gtd::B_GQ;      // (not staged: not to be read)
+                if (pl) vector_up(R.call, cs.pl_off, cs.pl_type, cs.pl_n); else cs.have &= ~(uint32_t)gtd::B_PL;
+            } else { memcpy(text + at, R.call.text.data() + p.rec.c_off, (size_t)r.c_len); r.c_off = at; at += r.c_len; txt += r.c_len; }
             recs[n] = r;
+            if (direct) { sides[2 * n] = ts; sides[2 * n + 1] = cs; }
         }
         if (gtd_dev_submit(R.dev, slot, n, at) != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
-        R.text_up += at; R.t_dev += now_s() - t0;
+        R.text_up += txt; R.vec_up += vec;                                    // (the padding in front of a vector is neither)
+         R.n_batches += direct; R.t_dev += now_s() - t0;
     };
     auto retire = [&](int64_t b) {
         double t0 = now_s();
@@ -409,6 +522,7 @@ void run_device(Run& R) {
     std::vector<int64_t> dt(R.table.size());
     if (gtd_dev_table(R.dev, dt.data()) != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
     for (size_t i = 0; i + 2 < dt.size(); i++) R.table[i] += dt[i];
+    if (direct) gtd_dev_times(R.dev, &R.ms_stage, &R.ms_decode);
 }
 
 }  // namespace
@@ -420,8 +534,8 @@ int main(int argc, char** argv) {
     double t0 = now_s();
     {
         FileReader reader; reader.device_inflate = o.device_inflate; reader.device = o.device; reader.verbose = o.verbose;
-        R.truth = read_input_file(reader, o.truth);
-        R.call = read_input_file(reader, o.call);
+        R.truth = read_input_file(reader, o.truth, o.bcf_direct != 0);
+        R.call = read_input_file(reader, o.call, o.bcf_direct != 0);
     }
     R.out_fp = fopen(o.out.c_str(), "w");
     if (!R.out_fp) die("Could not open output file %s for writing", o.out.c_str());
@@ -471,6 +585,8 @@ int main(int argc, char** argv) {
             if (C.pli < 0) { snprintf(msg, sizeof msg, "The call record at position %lld has no PL tag (-doGQ 8 on a call file without GQ reads it).", (long long)C.pos); R.stop = msg; break; }
             if (r.c_nal > 5) { snprintf(msg, sizeof msg, "The call record at position %lld has %d alleles: -doGQ 8 reads PL for at most 5.", (long long)C.pos, r.c_nal); R.stop = msg; break; }
         }
+        p.tside = bcf_side(R.truth, ti, r.t_nal, r.t_map); p.cside = bcf_side(R.call, ci, r.c_nal, r.c_map);
+        R.n_direct[0] += p.tside.have != 0; R.n_direct[1] += p.cside.have != 0;
         R.pairs.push_back(p);
     }
     const long nsites2 = (long)R.pairs.size();
@@ -495,6 +611,10 @@ int main(int argc, char** argv) {
     if (o.verbose)
         fprintf(stderr, "[gtdisc] on-device %d: records %ld, redone on the host %ld, text bytes sent up %lld; read %.3f s, nine columns and merge %.3f s, device %.3f s, host %.3f s\n",
                 o.on_device, nsites2, R.n_host, (long long)R.text_up, R.t_read, R.t_nine, R.t_dev, R.t_host);
+    if (o.verbose && o.bcf_direct)
+        fprintf(stderr, "[bcf] bcf-direct 1: records judged from their vectors: truth %ld, call %ld; redone on the host %ld; vector bytes sent up %lld, text bytes sent up %lld; "
+                        "device stage %.3f ms over %ld batches (hipEvent pairs), of which k_gtd_bcf_decode %.3f ms\n",
+                R.n_direct[0], R.n_direct[1], R.n_host, (long long)R.vec_up, (long long)R.text_up, R.ms_stage, R.n_batches, R.ms_decode);
     fprintf(stderr, "\n\nFinished running gtDiscordance\n\t-> Output file: %s\n", o.out.c_str());
     if (R.dev) gtd_dev_destroy(R.dev);
     fclose(R.out_fp);

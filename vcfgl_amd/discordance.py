@@ -115,12 +115,13 @@ GTDISC_PROGRAM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin",
 
 
 def compare_files(truth, call, out, do_gq=0, per_site=False, on_device=True, device=None, batch_records=None, verbose=False,
-                  timeout=None, env=None, device_inflate=None):
+                  timeout=None, env=None, device_inflate=None, bcf_direct=None):
     """Runs gtdiscordance_hip -t `truth` -i `call` -o `out` -doGQ `do_gq` [-perSite 1] as a fresh child process and returns
     (returncode, stdout, stderr) as text; stdout holds the -perSite lines, `out` the table or the -doGQ 1 / 2 listing.
     on_device=False compares on the host and touches no GPU; on_device=True without a GPU fails (returncode 1): there is no
     fallback.  device_inflate=True inflates the BGZF members of both files on the GPU (--device-inflate 1; any other file is read by
-    zlib as without it), also under on_device=False.  A missing program is an error (build the package first)."""
+    zlib as without it), also under on_device=False.  bcf_direct=True judges a BCF file of the pair from its typed GT / GQ / PL vectors
+    (--bcf-direct 1) and writes the same bytes as without it.  A missing program is an error (build the package first)."""
     if not os.path.exists(GTDISC_PROGRAM):
         raise FileNotFoundError("%s is not built (make -C vcfgl_amd/csrc all)" % GTDISC_PROGRAM)
     cmd = [GTDISC_PROGRAM, "-t", str(truth), "-i", str(call), "-o", str(out), "-doGQ", str(int(do_gq)), "-perSite", "1" if per_site else "0",
@@ -131,6 +132,8 @@ def compare_files(truth, call, out, do_gq=0, per_site=False, on_device=True, dev
         cmd += ["--batch-records", str(int(batch_records))]
     if device_inflate is not None:
         cmd += ["--device-inflate", "1" if device_inflate else "0"]
+    if bcf_direct is not None:
+        cmd += ["--bcf-direct", "1" if bcf_direct else "0"]
     if verbose:
         cmd += ["--verbose", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
