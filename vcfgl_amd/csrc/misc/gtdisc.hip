@@ -19,6 +19,9 @@
 //   k_gtd_list_write  a workgroup per record, a lane per line: the lines' lengths are scanned across the workgroup, chunk by chunk, and
 //                     every lane formats its line at its offset, never past the text's capacity
 // The planes never leave the device; the table is read once, the listing text per batch.
+// Two bases: the truth side and the call side of a record are read from a base pointer and a byte count of their own.  A batch that
+// is staged whole passes its staging twice; under --resident 1 a side whose file lies in device memory (resident_file.h) passes that
+// file, and Rec::t_off / c_off and the BSide offsets of the side count from the file's first byte.  Every bound is the side's own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -26,6 +29,7 @@
 
 #include "../../../include/vcfgl_hip.h"
 #include "gtdisc_dev.h"
+#include "gtdres_core.h"
 #include "column_walk.hip.h"
 #include "batch_dev.hip.h"
 
@@ -42,7 +46,8 @@ constexpr int MAX_RUN = 32768;           // records per tally workgroup: below 2
 constexpr size_t TALLY_LDS = (size_t)HIST * 2 + SG * sizeof(uint32_t);
 
 struct ParseArgs {
-    const uint8_t* text; int64_t text_bytes;
+    const uint8_t* t_text; int64_t t_bytes;                            // the truth side's base and byte count
+    const uint8_t* c_text; int64_t c_bytes;                            // the call side's
     const gtd::Rec* recs; int32_t n_recs, N;
     uint8_t* tb; uint8_t* cb; uint8_t* gq; int32_t* status;
 };
@@ -56,28 +61,29 @@ __global__ void __launch_bounds__(NT) k_gtd_parse(const ParseArgs A) {
     const gtd::Rec r = A.recs[rec];
     const int32_t N = A.N;
     const int64_t tl = r.t_off, te = r.t_off + r.t_len, cl = r.c_off, ce = r.c_off + r.c_len;
-    const bool fits = r.t_off >= 0 && r.t_len >= 0 && te <= A.text_bytes && r.c_off >= 0 && r.c_len >= 0 && ce <= A.text_bytes;
+    const bool fits = r.t_off >= 0 && r.t_len >= 0 && te <= A.t_bytes && r.c_off >= 0 && r.c_len >= 0 && ce <= A.c_bytes;
     const bool known = r.t_gti >= 0 && r.c_gti >= 0 && r.t_nal >= 1 && r.c_nal >= 1 && (r.gq_mode != gtd::GQ_TAG || r.c_gqi >= 0) &&
                        (r.gq_mode != gtd::GQ_PL || r.c_nal == 1 || (r.c_pli >= 0 && r.c_nal <= 5 && r.nG == gtd::n_genotypes(r.c_nal)));
     if (!fits || !known) {                                             // (the host sends no such record; never read outside the text)
         if (t == 0) A.status[rec] = gtd::ST_HOST;
         return;
     }
-    const uint8_t* __restrict__ text = A.text;
+    const uint8_t* __restrict__ t_text = A.t_text;
+    const uint8_t* __restrict__ c_text = A.c_text;
     uint8_t* __restrict__ tb = A.tb + (size_t)rec * (size_t)N;
     uint8_t* __restrict__ cb = A.cb + (size_t)rec * (size_t)N;
     uint8_t* __restrict__ gq = A.gq + (size_t)rec * (size_t)N;
     int bad = 0;
-    const int32_t cols_t = scan_columns(text, tl, te, s_tot, [&](const int32_t col, const int64_t q) {
+    const int32_t cols_t = scan_columns(t_text, tl, te, s_tot, [&](const int32_t col, const int64_t q) {
         if (col >= N) return;
         uint32_t b;
-        if (!gtd::sample_true(text, q, te, r, b)) bad = 1; else tb[col] = (uint8_t)b;
+        if (!gtd::sample_true(t_text, q, te, r, b)) bad = 1; else tb[col] = (uint8_t)b;
     });
     __syncthreads();                                                   // (s_tot is used again)
-    const int32_t cols_c = scan_columns(text, cl, ce, s_tot, [&](const int32_t col, const int64_t q) {
+    const int32_t cols_c = scan_columns(c_text, cl, ce, s_tot, [&](const int32_t col, const int64_t q) {
         if (col >= N) return;
         uint32_t b, g;
-        if (!gtd::sample_call(text, q, ce, r, b, g)) bad = 1; else { cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
+        if (!gtd::sample_call(c_text, q, ce, r, b, g)) bad = 1; else { cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
     });
     bad = __any(bad) ? 1 : 0;
     if (lane == 0) s_bad[wave] = bad;
@@ -92,7 +98,8 @@ __global__ void __launch_bounds__(NT) k_gtd_parse(const ParseArgs A) {
 
 // ---- --bcf-direct 1: the planes from typed vectors ---------------------------------------------------------------------------------
 struct DecodeArgs {
-    const uint8_t* bytes; int64_t n_bytes;                             // the batch's staging: vectors of the BCF sides, text of the others
+    const uint8_t* t_bytes; int64_t t_n;                               // the truth side's base and byte count: the batch's staging (vectors of
+    const uint8_t* c_bytes; int64_t c_n;                               // a BCF side, text of another), or a resident file; the call side's
     const gtd::Rec* recs; const gtd::BSide* sides;                     // [n_recs], [2 * n_recs] (truth, call)
     int32_t n_recs, N;
     uint8_t* tb; uint8_t* cb; uint8_t* gq; int32_t* status;
@@ -111,12 +118,14 @@ __device__ __forceinline__ int32_t widen8(const uint32_t byte) {
 }
 
 // one BCF side of a record: the samples' bytes into `plane` (true or called bases) and, for a call, `gqp`.  Returns 1 when a sample
-// is not plain.  The common shape -- int8 GT, two values a sample, the vectors on a 16-byte boundary -- is read 16 bytes a lane, so
-// that a wavefront takes 1 KiB of consecutive bytes with one load and stores its 8 bytes a plane at once; everything else, and the
-// last samples of such a vector, goes a sample a lane through the per-value routines of gtdbcf_core.h (consecutive lanes still read
-// consecutive vectors).  The caller has checked the descriptor against the staged bytes (gtd::side_fits).
+// is not plain.  The common shape -- int8 GT, two values a sample -- is read 16 bytes a lane, so that a wavefront takes 1 KiB of
+// consecutive bytes and stores its 8 bytes a plane at once: one load where the vector starts on a 16-byte address (the staging puts it
+// there), the two aligned pieces around the lane's bytes joined by a byte shift where it does not (a resident file: gtd::load16_any,
+// which loads a piece only when all of it lies inside [0, n_bytes) of the side).  Everything else, the last samples of such a vector
+// and a lane whose pieces do not lie inside go a sample a lane through the per-value routines of gtdbcf_core.h (consecutive lanes
+// still read consecutive vectors).  The caller has checked the descriptor against the side's byte count (gtd::side_fits).
 template <bool CALL>
-__device__ __forceinline__ int decode_side(const uint8_t* __restrict__ bytes, const gtd::BSide& b, const gtd::Rec& r, const int32_t N,
+__device__ __forceinline__ int decode_side(const uint8_t* __restrict__ bytes, const int64_t n_bytes, const gtd::BSide& b, const gtd::Rec& r, const int32_t N,
                                            uint8_t* __restrict__ plane, uint8_t* __restrict__ gqp) {
     const int t = threadIdx.x;
     int bad = 0;
@@ -125,12 +134,16 @@ __device__ __forceinline__ int decode_side(const uint8_t* __restrict__ bytes, co
         if (CALL) { if (!gtd::bcf_sample_call(bytes, b, s, r.gq_mode, r.nG, x, g)) bad = 1; plane[s] = (uint8_t)x; gqp[s] = (uint8_t)g; }
         else { if (!gtd::bcf_sample_true(bytes, b, s, x)) bad = 1; plane[s] = (uint8_t)x; }
     };
-    const uint8_t* __restrict__ gt = bytes + b.gt_off;
-    if (b.gt_type == 1 && b.gt_n == 2 && ((uintptr_t)gt & 15u) == 0) {
+#ifdef GTD_NO_WIDE_ANY                                                 // (the measurement of DESIGN.md 4.32: an unaligned vector a sample a lane)
+    const bool wide = b.gt_type == 1 && b.gt_n == 2 && ((uintptr_t)(bytes + b.gt_off) & 15u) == 0;
+#else
+    const bool wide = b.gt_type == 1 && b.gt_n == 2;
+#endif
+    if (wide) {
         for (int64_t s0 = (int64_t)t * WS; s0 < N; s0 += (int64_t)NT * WS) {
-            if (s0 + WS > N) { for (int64_t s = s0; s < N; s++) one(s); continue; }
-            const uint4 v = *reinterpret_cast<const uint4*>(gt + 2 * s0);          // [gt + 2 s0, + 16) lies inside the N pairs
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            uint32_t w[4];
+            // [gt_off + 2 s0, + 16) lies inside the N pairs; the pieces around it need not
+            if (s0 + WS > N || !gtd::load16_any(bytes, b.gt_off + 2 * s0, n_bytes, w)) { for (int64_t s = s0; s < N && s < s0 + WS; s++) one(s); continue; }
             uint64_t o0 = 0, o1 = 0;
 #pragma unroll
             for (int i = 0; i < WS; i++) {
@@ -152,8 +165,8 @@ __device__ __forceinline__ int decode_side(const uint8_t* __restrict__ bytes, co
 }
 
 // One workgroup of 256 lanes per record, the truth side and then the call side.  A BCF side (BSide::have) is decoded from its vectors,
-// a text side is walked as k_gtd_parse walks it; the status is the OR of both.  Every descriptor is checked against the staged byte
-// count before a byte is read; a record that fails the check is ST_HOST.  No atomics.
+// a text side is walked as k_gtd_parse walks it; the status is the OR of both.  Every descriptor is checked against the byte count
+// of its own side before a byte is read; a record that fails the check is ST_HOST.  No atomics.
 __global__ void __launch_bounds__(NT) k_gtd_bcf_decode(const DecodeArgs A) {
     __shared__ int32_t s_tot[2][NT / 64];
     __shared__ int32_t s_bad[NT / 64];
@@ -165,33 +178,34 @@ __global__ void __launch_bounds__(NT) k_gtd_bcf_decode(const DecodeArgs A) {
     const int32_t N = A.N;
     const int64_t tl = r.t_off, te = r.t_off + r.t_len, cl = r.c_off, ce = r.c_off + r.c_len;
     bool ok = r.t_nal >= 1 && r.c_nal >= 1;
-    if (T.have) ok = ok && T.nal == r.t_nal && gtd::side_fits(T, false, r.gq_mode, r.nG, N, A.n_bytes);
-    else ok = ok && r.t_off >= 0 && r.t_len >= 0 && te <= A.n_bytes && r.t_gti >= 0;
-    if (C.have) ok = ok && C.nal == r.c_nal && gtd::side_fits(C, true, r.gq_mode, r.nG, N, A.n_bytes);
-    else ok = ok && r.c_off >= 0 && r.c_len >= 0 && ce <= A.n_bytes && r.c_gti >= 0 && (r.gq_mode != gtd::GQ_TAG || r.c_gqi >= 0) &&
+    if (T.have) ok = ok && T.nal == r.t_nal && gtd::side_fits(T, false, r.gq_mode, r.nG, N, A.t_n);
+    else ok = ok && r.t_off >= 0 && r.t_len >= 0 && te <= A.t_n && r.t_gti >= 0;
+    if (C.have) ok = ok && C.nal == r.c_nal && gtd::side_fits(C, true, r.gq_mode, r.nG, N, A.c_n);
+    else ok = ok && r.c_off >= 0 && r.c_len >= 0 && ce <= A.c_n && r.c_gti >= 0 && (r.gq_mode != gtd::GQ_TAG || r.c_gqi >= 0) &&
               (r.gq_mode != gtd::GQ_PL || r.c_nal == 1 || (r.c_pli >= 0 && r.c_nal <= 5 && r.nG == gtd::n_genotypes(r.c_nal)));
     if (!ok) {                                                         // (the host sends no such record; never read outside the bytes)
         if (t == 0) A.status[rec] = gtd::ST_HOST;
         return;
     }
-    const uint8_t* __restrict__ bytes = A.bytes;
+    const uint8_t* __restrict__ t_bytes = A.t_bytes;
+    const uint8_t* __restrict__ c_bytes = A.c_bytes;
     uint8_t* __restrict__ tb = A.tb + (size_t)rec * (size_t)N;
     uint8_t* __restrict__ cb = A.cb + (size_t)rec * (size_t)N;
     uint8_t* __restrict__ gq = A.gq + (size_t)rec * (size_t)N;
     int bad = 0;
     int32_t cols_t = N, cols_c = N;
-    if (T.have) bad |= decode_side<false>(bytes, T, r, N, tb, nullptr);
-    else cols_t = scan_columns(bytes, tl, te, s_tot, [&](const int32_t col, const int64_t q) {
+    if (T.have) bad |= decode_side<false>(t_bytes, A.t_n, T, r, N, tb, nullptr);
+    else cols_t = scan_columns(t_bytes, tl, te, s_tot, [&](const int32_t col, const int64_t q) {
         if (col >= N) return;
         uint32_t b;
-        if (!gtd::sample_true(bytes, q, te, r, b)) bad = 1; else tb[col] = (uint8_t)b;
+        if (!gtd::sample_true(t_bytes, q, te, r, b)) bad = 1; else tb[col] = (uint8_t)b;
     });
     __syncthreads();                                                   // (s_tot is used again)
-    if (C.have) bad |= decode_side<true>(bytes, C, r, N, cb, gq);
-    else cols_c = scan_columns(bytes, cl, ce, s_tot, [&](const int32_t col, const int64_t q) {
+    if (C.have) bad |= decode_side<true>(c_bytes, A.c_n, C, r, N, cb, gq);
+    else cols_c = scan_columns(c_bytes, cl, ce, s_tot, [&](const int32_t col, const int64_t q) {
         if (col >= N) return;
         uint32_t b, g;
-        if (!gtd::sample_call(bytes, q, ce, r, b, g)) bad = 1; else { cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
+        if (!gtd::sample_call(c_bytes, q, ce, r, b, g)) bad = 1; else { cb[col] = (uint8_t)b; gq[col] = (uint8_t)g; }
     });
     bad = __any(bad) ? 1 : 0;
     if (lane == 0) s_bad[wave] = bad;
@@ -344,7 +358,7 @@ struct GtdDev : batchdev::BatchDev {
     int32_t N = 0, max_recs = 0; int64_t max_text = 0; int list = 0, per_site = 0;
     int64_t list_cap = 0, site_cap = 0;
     batchdev::DevMem<unsigned long long> d_table; int64_t table_len = 0;
-    int bcf = 0; double ms_stage = 0, ms_decode = 0;                   // --bcf-direct 1: the retired batches' device time
+    int bcf = 0, timed = 0; double ms_stage = 0, ms_decode = 0;        // --bcf-direct 1 / --resident 1: the retired batches' device time
     struct Slot {
         batchdev::PinMem<gtd::BSide> h_sides; batchdev::DevMem<gtd::BSide> d_sides;
         batchdev::Event t0, k0, k1, t1;                                // (timing events: the batch's first copy, around the decode, its last kernel)
@@ -358,10 +372,10 @@ struct GtdDev : batchdev::BatchDev {
 
 const char* gtd_dev_error(GtdDev* d) { return d->err; }
 
-GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, int bcf, char* err, size_t err_len) {
+GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t max_text, int list, int per_site, int bcf, int timed, char* err, size_t err_len) {
     if (n_samples <= 0 || max_recs <= 0 || max_text < 0) { snprintf(err, err_len, "bad batch shape"); return nullptr; }
     return batchdev::create<GtdDev>(device, err, err_len, [&](GtdDev* d) {
-        d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->list = list; d->per_site = per_site; d->bcf = bcf;
+        d->N = n_samples; d->max_recs = max_recs; d->max_text = max_text; d->list = list; d->per_site = per_site; d->bcf = bcf; d->timed = (bcf || timed) ? 1 : 0;
         d->list_cap = list ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
         d->site_cap = per_site ? (int64_t)max_recs * n_samples * gtd::LINE_BOUND : 0;
         d->table_len = vgl_disc_table_len(d->N);
@@ -378,8 +392,8 @@ GtdDev* gtd_dev_create(int device, int32_t n_samples, int32_t max_recs, int64_t 
             if (d->bcf) {
                 if (!s.h_sides.alloc(d->device, 2 * R * sizeof(gtd::BSide))) return d->no_pinned();
                 BATCH_HIP(d, s.d_sides.alloc(2 * R * sizeof(gtd::BSide)));
-                for (batchdev::Event* e : {&s.t0, &s.k0, &s.k1, &s.t1}) BATCH_HIP(d, hipEventCreate(&e->h));
             }
+            if (d->timed) for (batchdev::Event* e : {&s.t0, &s.k0, &s.k1, &s.t1}) BATCH_HIP(d, hipEventCreate(&e->h));
             BATCH_HIP(d, s.d_planes.alloc(3 * R * N));
             BATCH_HIP(d, s.d_status.alloc(R * 4));
             BATCH_HIP(d, s.d_len.alloc(2 * R * 8));
@@ -396,28 +410,29 @@ gtd::Rec* gtd_dev_recs(GtdDev* d, int slot) { return d->slot[slot & 1].h_recs; }
 gtd::BSide* gtd_dev_sides(GtdDev* d, int slot) { return d->slot[slot & 1].h_sides; }
 void gtd_dev_times(GtdDev* d, double* stage_ms, double* decode_ms) { *stage_ms = d->ms_stage; *decode_ms = d->ms_decode; }
 
-int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
+// the copies of a batch up and its launch sequence; a side's base is the resident file it was given, or the slot's staging
+static int submit_on(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes, const uint8_t* t_base, int64_t t_bytes, const uint8_t* c_base, int64_t c_bytes) {
     GtdDev::Slot& s = d->slot[slot & 1];
-    if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && text_bytes >= 0 && text_bytes <= d->max_text) != 0) return -1;
     if (n_recs == 0) return 0;
     hipStream_t st = d->stream;
     const size_t R = (size_t)n_recs, N = (size_t)d->N;
-    if (d->bcf) BATCH_HIP(d, hipEventRecord(s.t0, st));
-    BATCH_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
+    if (!t_base) { t_base = s.d_text; t_bytes = text_bytes; }
+    if (!c_base) { c_base = s.d_text; c_bytes = text_bytes; }
+    if (d->timed) BATCH_HIP(d, hipEventRecord(s.t0, st));
+    if (text_bytes > 0) BATCH_HIP(d, hipMemcpyAsync(s.d_text, s.h_text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
     BATCH_HIP(d, hipMemcpyAsync(s.d_recs, s.h_recs, R * sizeof(gtd::Rec), hipMemcpyHostToDevice, st));
     uint8_t* tb = s.d_planes; uint8_t* cb = tb + (size_t)d->max_recs * N; uint8_t* gq = cb + (size_t)d->max_recs * N;
+    if (d->bcf) BATCH_HIP(d, hipMemcpyAsync(s.d_sides, s.h_sides, 2 * R * sizeof(gtd::BSide), hipMemcpyHostToDevice, st));
+    if (d->timed) BATCH_HIP(d, hipEventRecord(s.k0, st));
     if (d->bcf) {
-        BATCH_HIP(d, hipMemcpyAsync(s.d_sides, s.h_sides, 2 * R * sizeof(gtd::BSide), hipMemcpyHostToDevice, st));
-        BATCH_HIP(d, hipEventRecord(s.k0, st));
-        const DecodeArgs P{s.d_text, text_bytes, s.d_recs, s.d_sides, n_recs, d->N, tb, cb, gq, s.d_status};
+        const DecodeArgs P{t_base, t_bytes, c_base, c_bytes, s.d_recs, s.d_sides, n_recs, d->N, tb, cb, gq, s.d_status};
         hipLaunchKernelGGL(k_gtd_bcf_decode, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
-        BATCH_HIP(d, hipGetLastError());
-        BATCH_HIP(d, hipEventRecord(s.k1, st));
     } else {
-        const ParseArgs P{s.d_text, text_bytes, s.d_recs, n_recs, d->N, tb, cb, gq, s.d_status};
+        const ParseArgs P{t_base, t_bytes, c_base, c_bytes, s.d_recs, n_recs, d->N, tb, cb, gq, s.d_status};
         hipLaunchKernelGGL(k_gtd_parse, dim3((unsigned)n_recs), dim3(NT), 0, st, P);
-        BATCH_HIP(d, hipGetLastError());
     }
+    BATCH_HIP(d, hipGetLastError());
+    if (d->timed) BATCH_HIP(d, hipEventRecord(s.k1, st));
     // the tally: about two workgroups per CU where the batch has them, runs of at least 16 records, never more than MAX_RUN
     const int groups = (d->N + SG - 1) / SG;
     int runs = 512 / groups;
@@ -441,16 +456,27 @@ int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
         BATCH_HIP(d, hipGetLastError());
         BATCH_HIP(d, hipMemcpyAsync(s.h_off, s.d_off, 2 * (R + 1) * 8, hipMemcpyDeviceToHost, st));
     }
-    if (d->bcf) BATCH_HIP(d, hipEventRecord(s.t1, st));
+    if (d->timed) BATCH_HIP(d, hipEventRecord(s.t1, st));
     BATCH_HIP(d, hipMemcpyAsync(s.h_status, s.d_status, R * 4, hipMemcpyDeviceToHost, st));
     return d->end_submit(slot);
+}
+
+int gtd_dev_submit(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes) {
+    if (d->begin_submit(slot, n_recs, n_recs >= 0 && n_recs <= d->max_recs && text_bytes >= 0 && text_bytes <= d->max_text) != 0) return -1;
+    return submit_on(d, slot, n_recs, text_bytes, nullptr, 0, nullptr, 0);
+}
+
+int gtd_dev_submit_resident(GtdDev* d, int slot, int32_t n_recs, int64_t text_bytes, const uint8_t* t_file, int64_t t_bytes, const uint8_t* c_file, int64_t c_bytes) {
+    const bool ok = n_recs >= 0 && n_recs <= d->max_recs && text_bytes >= 0 && text_bytes <= d->max_text && (!t_file || t_bytes >= 0) && (!c_file || c_bytes >= 0);
+    if (d->begin_submit(slot, n_recs, ok) != 0) return -1;
+    return submit_on(d, slot, n_recs, text_bytes, t_file, t_bytes, c_file, c_bytes);
 }
 
 int gtd_dev_wait(GtdDev* d, int slot, GtdBatchOut* out) {
     GtdDev::Slot& s = d->slot[slot & 1];
     if (d->begin_wait(slot) != 0) return -1;
     const size_t R = (size_t)d->head[slot & 1].n_recs;
-    if (d->bcf && R > 0) {
+    if (d->timed && R > 0) {
         float a = 0, b = 0;
         BATCH_HIP(d, hipEventElapsedTime(&a, s.t0, s.t1)); BATCH_HIP(d, hipEventElapsedTime(&b, s.k0, s.k1));
         d->ms_stage += a; d->ms_decode += b;

@@ -1,5 +1,6 @@
 // gtdisc_main.cpp -- gtdiscordance_hip: the reference's misc/gtDiscordance (a call file against -printTruth's file) for this platform.
 //   gtdiscordance_hip -t truth -i call -o out [-doGQ 0..8] [-perSite 0|1] [--on-device 0|1] [--device INT] [--batch-records INT] [--verbose 0|1] [--device-inflate 0|1] [--bcf-direct 0|1]
+//                     [--resident 0|1] [--resident-max-bytes INT]
 // Both files are read whole (plain, gzip or bgzip text through zlib; BCF records are decoded into the same text lines on the host, or
 // under --bcf-direct 1 left as they are and judged from their typed vectors by the rules of gtdbcf_core.h), their
 // first nine columns are parsed on the host and the records matched by the tool's sequential merge on POS.  Every matched pair is then
@@ -7,18 +8,28 @@
 // host (--on-device 0) -- and a record outside that grammar is redone whole by the permissive reader below, which owns every message.
 // Both paths therefore write the same bytes.  A run that has to stop does so at the record the tool would stop at: what the records
 // before it gave is written first.
+// --resident 1 (with --device-inflate 1 and --on-device 1): each file of the pair that is a clean series of BGZF members is inflated
+// into device memory and stays there (resident_file.h), the truth file first, the call file within what is left of
+// --resident-max-bytes.  Of VCF text the heads alone come down (the # lines, the first nine columns of every other line), of BCF under
+// --bcf-direct 1 the records' heads (lengths, shared block, FORMAT keys and descriptors); the nine columns, the merge and every stop
+// decided from them are the host code below on those bytes, and the batches' descriptors point into the file where the inflater wrote
+// it.  A record the device hands back has its sample columns (BCF: its bytes) copied down for the permissive reader.  A file that
+// cannot be resident is read as with --resident 0 -- the other one may still be -- and its [input] line of --verbose 1 says why.
 #include <strings.h>
 #include "record_file.h"
 #include "batch_plan.h"
 #include "gtdisc_dev.h"
+#include "resident_file.h"
 
 namespace {
 
 struct Opt {
     std::string truth, call, out;
-    int do_gq = 0, per_site = 0, on_device = 1, device = 0, batch = 4096, verbose = 0, device_inflate = 0, bcf_direct = 0;
+    int do_gq = 0, per_site = 0, on_device = 1, device = 0, batch = 4096, verbose = 0, device_inflate = 0, bcf_direct = 0, resident = 0;
+    int64_t resident_max = -1;         // --resident-max-bytes (-1: the device's free memory less 1 GiB)
 };
 
+// (--resident 0|1 [0] and --resident-max-bytes INT are taken and not listed here: README and DESIGN.md 4.32 describe them)
 const char GTD_USAGE[] =
     "Usage: gtdiscordance_hip -t <truth> -i <call> -o <output.tsv>\n"
     "Options:\n"
@@ -61,11 +72,18 @@ Opt parse_opt(int argc, char** argv) {
         else if (!strcmp(a, "--verbose")) o.verbose = option_int(a, v, 0, 1);
         else if (!strcmp(a, "--device-inflate")) o.device_inflate = option_int(a, v, 0, 1);
         else if (!strcmp(a, "--bcf-direct")) o.bcf_direct = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--resident")) o.resident = option_int(a, v, 0, 1);
+        else if (!strcmp(a, "--resident-max-bytes")) {
+            char* e; const long long x = strtoll(v, &e, 10);
+            if (e == v || *e || x < 0) die("%s takes an integer of at least 0, not '%s'", a, v);
+            o.resident_max = x;
+        }
         else die("Unknown arg:%s", a);
     }
     if (o.call.empty()) die("Input file not specified. Please use -i/--input <file>.");
     if (o.truth.empty()) die("Truth file not specified. Please use -t/--truth <file>.");
     if (o.out.empty()) die("Output file not specified. Please use -o/--output <file>.");
+    if (o.resident && !(o.device_inflate && o.on_device)) die("--resident 1 needs --device-inflate 1 and --on-device 1.");
     return o;
 }
 
@@ -86,6 +104,9 @@ struct Input {
     // --bcf-direct 1, a BCF file: its bytes as read, its dictionaries and where every record's vectors lie
     bool direct = false;
     std::vector<uint8_t> bcf; BcfDict dict; std::vector<BcfFields> brecs;
+    // --resident 1, a resident file: its bytes lie in device memory.  VCF text: `text` is the head stream and record i is line
+    // line_of[i] of the file, whose sample columns the split names.  BCF: `bcf` is empty, brecs hold offsets into the file
+    RfFile* rf = nullptr; rf::Split split; std::vector<size_t> line_of;
     bool has_format(const char* id) const {
         const std::string k = std::string("##FORMAT=<ID=") + id + ",";
         for (const std::string& h : header) if (h.compare(0, k.size(), k) == 0) return true;
@@ -94,20 +115,32 @@ struct Input {
     bool vectors(const size_t i) const { return direct && !brecs[i].as_text; }     // record i is judged from its typed vectors
 };
 
-// the record at the cursor: its shared block -> r, its FORMAT field headers -> f; the cursor is left behind the record
-void bcf_walk(BcfIn& c, const BcfDict& d, const size_t N, Rec& r, BcfFields& f) {
+// the record at the cursor: its shared block -> r, its FORMAT field headers -> f; the cursor is left behind the record.
+// One body for both sources.  heads == nullptr: the cursor walks the file's bytes.  Else (a resident BCF file) it walks the head
+// stream -- per record the two lengths, the shared block and the fields' keys and descriptors, bytes identical to the file's -- and
+// record i's place in the file gives f.at and the fields' data offsets (bcf_format_fields)
+void bcf_walk(BcfIn& c, const BcfDict& d, const size_t N, Rec& r, BcfFields& f, const RbSplit* heads = nullptr, const size_t i = 0) {
     BcfRecAt at; int n_fmt;
-    f.at = c.off;
-    bcf_scan_record(c, at);
+    const size_t head_at = c.off;
+    size_t file_end = 0;
+    if (!heads) { f.at = c.off; bcf_scan_record(c, at); }
+    else {                                                             // (the device has made the checks of bcf_scan_record)
+        if (i >= (size_t)heads->records || (int64_t)head_at != heads->hoff[i]) die("--resident 1: the head stream does not follow its records.");
+        f.at = (size_t)heads->rec_off[i];
+        const uint32_t l_shared = c.u32(), l_indiv = c.u32();
+        at.shared = c.off; at.shared_end = c.off + l_shared; at.rec_end = (size_t)heads->hoff[i + 1];
+        file_end = f.at + 8 + (size_t)l_shared + l_indiv;
+    }
     bcf_shared(c, d, at, N, r, n_fmt);
     bcf_format_fields(c, d, n_fmt, N, [&](int, const std::string& key, int type, int n, size_t data_off) {
         if (type < 1 || type > 3) return;                               // (the walker has checked that the vectors lie inside the file)
         const int k = key == "GT" ? F_GT : key == "GQ" ? F_GQ : key == "PL" ? F_PL : -1;
         if (k < 0) return;
         f.off[k] = (int64_t)data_off; f.type[k] = type; f.n[k] = n; f.have[k] = true;
-    });
+    }, heads ? heads->rec_off[i] + (int64_t)(c.off - head_at) : (int64_t)-1);
+    if (heads && c.off != at.rec_end) die("--resident 1: a record's head is not as long as the device made it.");
     if (!f.have[F_GT]) die("Could not find GT tag at position %ld.", r.pos0 + 1);
-    c.off = f.rec_end = at.rec_end;
+    c.off = at.rec_end; f.rec_end = heads ? file_end : at.rec_end;
 }
 // the first nine columns a VCF writer would give the record (the columns nothing reads are '.')
 void bcf_nine(const Rec& r, const BcfFields& f, std::string& out) {
@@ -153,16 +186,20 @@ void bcf_one_line(const std::vector<uint8_t>& raw, const BcfDict& d, const size_
 // text holds a record's first nine columns and a tab -- what parse_nine reads -- and its sample columns are written only on demand
 // (Input::line_of).  A record whose first nine columns would not stand where a reader of the line looks for them (a tab inside a
 // name), or whose line could pass 2 GiB, gets its whole line here as without the flag.
-void bcf_lines(std::vector<uint8_t>& raw, Input& in, const bool direct) {
+// A resident file (heads, always direct): raw is the file's header, the cursor then walks the head stream, and a record that gets its
+// whole line has its bytes copied down for it.
+void bcf_lines(std::vector<uint8_t>& raw, Input& in, const bool direct, const RbSplit* heads = nullptr) {
     BcfIn c; c.buf = raw.data(); c.size = raw.size();
     Vcf v;
     bcf_header(c, in.dict, v);
+    if (heads) { c.buf = heads->heads.data(); c.size = heads->heads.size(); c.off = 0; }
     in.header = v.header; in.samples = v.samples;
     const size_t N = v.samples.size();
     std::string out;
-    while (c.off < c.size) {
+    std::vector<uint8_t> rec_bytes;
+    for (size_t i = 0; c.off < c.size; i++) {
         Rec r; BcfFields f;
-        bcf_walk(c, in.dict, N, r, f);
+        bcf_walk(c, in.dict, N, r, f, heads, i);
         const int64_t begin = (int64_t)out.size();
         bcf_nine(r, f, out);
         if (direct) {
@@ -171,23 +208,113 @@ void bcf_lines(std::vector<uint8_t>& raw, Input& in, const bool direct) {
             const double bound = (double)N * (12.0 * ((double)f.n[F_GT] + 1.0 + (double)f.n[F_PL]) + 4.0);
             f.as_text = tabs != 8 || bound > (double)(INT32_MAX / 2);
         }
-        if (!direct || f.as_text) bcf_columns(c, f, N, out); else out += '\t';
+        if (heads && f.as_text) {
+            rec_bytes.resize(f.rec_end - f.at);
+            if (rf_fetch(in.rf, (int64_t)f.at, (int64_t)rec_bytes.size(), rec_bytes.data()) != 0) die("--resident 1: %s", rf_error(in.rf));
+            out.resize((size_t)begin);
+            bcf_one_line(rec_bytes, in.dict, N, 0, out);
+        }
+        else if (!direct || f.as_text) bcf_columns(c, f, N, out); else out += '\t';
         in.lines.emplace_back(begin, (int64_t)out.size());
         out += '\n';
         if (direct) in.brecs.push_back(f);
     }
     in.text.assign(out.begin(), out.end());
-    if (direct) { in.direct = true; in.bcf = std::move(raw); }
+    if (direct) { in.direct = true; if (!heads) in.bcf = std::move(raw); }
 }
 
-Input read_input_file(FileReader& reader, const std::string& fn, const bool bcf_direct) {
-    Input in;
-    std::vector<uint8_t> raw = reader.read(fn);
-    if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) { bcf_lines(raw, in, bcf_direct); return in; }
+// the file's bytes as the reader gave them -> the Input
+void input_of_bytes(std::vector<uint8_t>& raw, Input& in, const bool bcf_direct) {
+    if (raw.size() >= 3 && !memcmp(raw.data(), "BCF", 3)) { bcf_lines(raw, in, bcf_direct); return; }
     in.text = std::move(raw);
     TextLines tl = scan_text(in.text);
     in.header = std::move(tl.header); in.samples = std::move(tl.samples); in.lines = std::move(tl.lines);
-    return in;
+}
+
+void read_input_file(FileReader& reader, const std::string& fn, const bool bcf_direct, Input& in) {
+    std::vector<uint8_t> raw = reader.read(fn);
+    input_of_bytes(raw, in, bcf_direct);
+}
+
+// --resident 1, a resident file that begins as BCF: its header and the split of its records (resident_file.h).  nullptr: hdr and
+// bsplit hold them; else why the bytes come down whole
+const char* load_resident_bcf(RfFile* rf, std::vector<uint8_t>& hdr, RbSplit& bsplit, std::string& why) {
+    auto failed = [&]() { die("--resident 1: %s", rf_error(rf)); };
+    bool fits = false;
+    if (rf_bcf_header(rf, &hdr, &fits) != 0) failed();
+    if (!fits) { why = "the header does not fit the file"; return why.c_str(); }
+    int64_t n_samples = -1;
+    try { BcfDict d; Vcf v; BcfIn c; c.buf = hdr.data(); c.size = hdr.size(); c.soft = true; bcf_header(c, d, v); n_samples = (int64_t)v.samples.size(); }
+    catch (const BcfSoftFail&) { why = "the header could not be read"; return why.c_str(); }
+    if (rf_bcf_split(rf, (int64_t)hdr.size(), n_samples, rb::RB_HOPS_MOST, rf::RF_HEAD_MOST, &bsplit) != 0) failed();
+    if (bsplit.more_records) why = "the file has more records than the offsets scan takes (INT32_MAX - 1024)";
+    else if (bsplit.why != rb::OK) { char b[256]; snprintf(b, sizeof b, "record %lld: %s", (long long)bsplit.ordinal + 1, rb::why_text(bsplit.why)); why = b; }
+    else return nullptr;
+    return why.c_str();
+}
+
+// --resident 1: one file of the pair into device memory and its split.  `left` is what --resident-max-bytes leaves this file (-1: the
+// device's free memory less 1 GiB, as it is now) and is brought down by what the file takes.  The file is resident (in.rf) or read
+// as --resident 0 reads it; the [input] line says which, and why
+void read_input_resident(FileReader& reader, const Opt& o, const std::string& fn, int64_t& left, Input& in) {
+    char err[256];
+    { FILE* fp = fopen(fn.c_str(), "rb"); if (!fp) die("Could not open file: %s", fn.c_str()); fclose(fp); }   // the file first, as without the flag
+    RfFile* rf = rf_create(o.device, err, sizeof err);
+    if (!rf) die("--resident 1: %s (device %d)", err, o.device);
+    const int64_t most = left >= 0 ? left : rf_default_max_bytes(rf);
+    auto failed = [&]() { const std::string why = rf_error(rf); if (why.compare(0, 14, "Could not open") == 0) die("%s", why.c_str()); die("--resident 1: %s", why.c_str()); };
+    RfWhy why;
+    if (rf_load(rf, fn.c_str(), most, &why) != 0) failed();
+    const char* reason = nullptr;
+    std::vector<uint8_t> raw, hdr; RbSplit bsplit; std::string bcf_why;
+    bool have = false, is_bcf = false;                                 // have: raw was copied down from the device
+    if (why == RF_NOT_BGZF) reason = "the file is not a series of BGZF members";
+    else if (why == RF_MEMBER_HOST) reason = "a member was left to the host (VGL_INFLATE_HOST)";
+    else if (why == RF_TOO_LARGE) reason = "the inflated and the compressed bytes exceed what --resident-max-bytes leaves";
+    else {
+        const int64_t total = rf_total(rf);
+        uint8_t first[3] = {0, 0, 0};
+        if (rf_fetch(rf, 0, std::min<int64_t>(3, total), first) != 0) failed();
+        bool more_lines = false;
+        is_bcf = total >= 3 && !memcmp(first, "BCF", 3);
+        if (is_bcf && !o.bcf_direct) reason = "the file is BCF and --bcf-direct is 0";
+        else if (is_bcf) reason = load_resident_bcf(rf, hdr, bsplit, bcf_why);
+        else {
+            if (rf_split(rf, rf::RF_HEAD_MOST, &in.split, &more_lines) != 0) failed();
+            if (more_lines) reason = "the file has more lines than the offsets scan takes (INT32_MAX - 1024)";
+            else if (in.split.over) reason = "a line's ninth tab is not within RF_HEAD_MOST bytes";
+        }
+        if (reason) {                                                  // the inflated bytes are on the device: they come down whole
+            raw.resize((size_t)total);
+            if (rf_fetch(rf, 0, total, raw.data()) != 0) failed();
+            have = true;
+        }
+    }
+    const RfStats st = *rf_stats(rf);
+    if (o.verbose && is_bcf)
+        fprintf(stderr, "[input] %s: resident %d%s%s%s, members %lld, records %lld, head bytes received %lld, compressed bytes sent up %lld; upload %.3f s, inflate %.3f s, chain %.3f s, heads %.3f s\n",
+                fn.c_str(), reason ? 0 : 1, reason ? " (" : "", reason ? reason : "", reason ? ")" : "", (long long)st.members, (long long)st.records,
+                (long long)st.head_bytes, (long long)st.compressed_up, st.t_upload, st.t_inflate, st.t_chain, st.t_heads);
+    else if (o.verbose)
+        fprintf(stderr, "[input] %s: resident %d%s%s%s, RF_CHUNK %lld, members %lld, lines %lld, head bytes received %lld, compressed bytes sent up %lld; upload %.3f s, inflate %.3f s, split %.3f s\n",
+                fn.c_str(), reason ? 0 : 1, reason ? " (" : "", reason ? reason : "", reason ? ")" : "", (long long)rf::RF_CHUNK, (long long)st.members, (long long)st.lines,
+                (long long)st.head_bytes, (long long)st.compressed_up, st.t_upload, st.t_inflate, st.t_split);
+    if (o.verbose && have) FileReader::report(fn, (long)st.members, st.compressed_up, st.total, st.t_inflate, nullptr);
+    if (reason) {
+        rf_destroy(rf); in.split = rf::Split();
+        if (!have) raw = reader.read(fn);
+        input_of_bytes(raw, in, o.bcf_direct != 0);
+        return;
+    }
+    in.rf = rf;
+    if (left >= 0) left = std::max<int64_t>(0, left - (st.total + st.compressed_up));
+    if (is_bcf) { bcf_lines(hdr, in, true, &bsplit); return; }
+    in.text = std::move(in.split.heads);
+    TextLines tl = scan_text(in.text);
+    in.header = std::move(tl.header); in.samples = std::move(tl.samples); in.lines = std::move(tl.lines);
+    in.line_of.resize(in.lines.size());
+    size_t ln = 0;                                                     // record i is line ln of the file
+    for (size_t i = 0; i < in.lines.size(); i++) { while (in.split.hoff[ln] < in.lines[i].first) ln++; in.line_of[i] = ln; }
 }
 
 // the first nine columns of a record line
@@ -218,6 +345,7 @@ Fixed parse_nine(const Input& in, const size_t i, const char* which) {
     f.gti = format_key_index(col_at[8], fmt_end, "GT"); f.gqi = format_key_index(col_at[8], fmt_end, "GQ"); f.pli = format_key_index(col_at[8], fmt_end, "PL");
     if (f.gti < 0) { snprintf(msg, sizeof msg, "Could not find GT tag at position %lld of the %s file.", (long long)f.pos, which); f.bad = msg; return f; }
     f.s_off = col_at[9] - t0; f.s_len = le - col_at[9];
+    if (in.rf && !in.direct) { f.s_off = in.split.s_off[in.line_of[i]]; f.s_len = in.split.s_len[in.line_of[i]]; }      // (the line's head ends behind its ninth tab)
     if (f.s_len > INT32_MAX) { snprintf(msg, sizeof msg, "The record at position %lld of the %s file is longer than 2 GiB.", (long long)f.pos, which); f.bad = msg; }
     return f;
 }
@@ -238,7 +366,7 @@ struct Run {
     FILE* out_fp = nullptr;
     std::string list_buf, site_buf;
     GtdDev* dev = nullptr;
-    long n_host = 0; int64_t text_up = 0;
+    long n_host = 0, n_timed = 0; int64_t text_up = 0;
     long n_direct[2] = {0, 0}; int64_t vec_up = 0; double ms_stage = 0, ms_decode = 0; long n_batches = 0;      // --bcf-direct 1
     double t_read = 0, t_nine = 0, t_dev = 0, t_host = 0;
 
@@ -259,6 +387,8 @@ struct Run {
         if (list) { gtd::Emit<true> e{b, 0u, (uint32_t)sizeof b}; gtd::list_line(e, list, p.nsites1, (uint32_t)s, cell, gq); list_buf.append((const char*)b, e.n); }
         if (o.per_site) { gtd::Emit<true> e{b, 0u, (uint32_t)sizeof b}; gtd::site_line(e, p.rec.pos, (uint32_t)s, cell); site_buf.append((const char*)b, e.n); }
     }
+    typedef std::pair<const char*, const char*> Span;
+    Span sample_columns(const Input& in, size_t i, const Fixed& F, std::string& line);
     void record_permissive(const Pair& p);
     void record_host(const Pair& p, std::vector<uint8_t>& planes);
 };
@@ -293,11 +423,23 @@ bool host_gt(Span f, long& a0, long& a1) {
     return one(f.first, s, a0) && one(s + 1, f.second, a1);
 }
 
-// the sample columns of record i: where they stand in the text, or the line bcf_lines would have made of the record's vectors
-Span sample_columns(const Input& in, const size_t i, const Fixed& F, std::string& line) {
+// the sample columns of record i: where they stand in the text, or the line bcf_lines would have made of the record's vectors.  Of a
+// resident file they are copied down: the columns of a text line, the bytes of a BCF record
+Span Run::sample_columns(const Input& in, const size_t i, const Fixed& F, std::string& line) {
     const char* t0 = (const char*)in.text.data();
+    if (in.rf && !in.direct) {
+        line.resize((size_t)F.s_len);
+        if (rf_fetch(in.rf, F.s_off, F.s_len, (uint8_t*)&line[0]) != 0) stop_run("--resident 1: %s", rf_error(in.rf));
+        return Span(line.data(), line.data() + line.size());
+    }
     if (!in.vectors(i)) return Span(t0 + F.s_off, t0 + F.s_off + F.s_len);
-    bcf_one_line(in.bcf, in.dict, in.samples.size(), in.brecs[i].at, line);
+    if (in.rf) {
+        const BcfFields& f = in.brecs[i];
+        std::vector<uint8_t> rec(f.rec_end - f.at);
+        if (rf_fetch(in.rf, (int64_t)f.at, (int64_t)rec.size(), rec.data()) != 0) stop_run("--resident 1: %s", rf_error(in.rf));
+        bcf_one_line(rec, in.dict, in.samples.size(), 0, line);
+    }
+    else bcf_one_line(in.bcf, in.dict, in.samples.size(), in.brecs[i].at, line);
     const char* col_at[10]; int nc;
     nine_columns(line.data(), line.data() + line.size(), col_at, nc);
     return nc < 9 ? Span(line.data() + line.size(), line.data() + line.size()) : Span(col_at[9], line.data() + line.size());
@@ -389,7 +531,8 @@ void Run::record_host(const Pair& p, std::vector<uint8_t>& planes) {
 gtd::BSide bcf_side(const Input& in, const size_t i, const int32_t nal, const uint64_t map) {
     gtd::BSide b;
     memset(&b, 0, sizeof b);
-    if (!in.vectors(i)) return b;
+    if (in.rf && in.direct && !in.vectors(i)) { b.have = gtd::B_GT; b.nal = nal; return b; }     // its line stands in the host's text alone: a side that never
+    if (!in.vectors(i)) return b;                                                                // fits (type 0), so the record comes back for the host reader
     const BcfFields& f = in.brecs[i];
     b.gt_off = f.off[F_GT]; b.gt_type = f.type[F_GT]; b.gt_n = f.n[F_GT];
     if (f.have[F_GQ]) { b.gq_off = f.off[F_GQ]; b.gq_type = f.type[F_GQ]; b.gq_n = f.n[F_GQ]; b.have |= gtd::B_GQ; }
@@ -456,6 +599,8 @@ void run_device(Run& R) {
     // --bcf-direct 1: a BCF side sends the vectors its record needs -- GT, GQ under GQ_TAG, PL under GQ_PL with more than one allele --
     // each at a 16-byte boundary of the staging (so at a 4-byte one), where a lane can take several samples with one load
     const bool direct = R.truth.direct || R.call.direct;
+    // --resident 1: a resident side is read where the inflater wrote it, costs a batch nothing and its offsets count from the file
+    const bool resident = R.truth.rf || R.call.rf;
     auto up16 = [](int64_t x) { return (x + 15) & ~(int64_t)15; };
     auto vec_bytes = [&](int type, int32_t n) { return (int64_t)gtd::bcf_width(type) * n * N; };
     auto needs = [](const gtd::BSide& b, const gtd::Rec& r, bool call, bool& gq, bool& pl) {
@@ -463,6 +608,7 @@ void run_device(Run& R) {
     };
     auto side_cost = [&](const Pair& p, bool call) -> int64_t {
         const gtd::BSide& b = call ? p.cside : p.tside;
+        if ((call ? R.call : R.truth).rf) return 0;
         if (!b.have) return call ? p.rec.c_len : p.rec.t_len;
         bool gq, pl; needs(b, p.rec, call, gq, pl);
         return 16 + up16(vec_bytes(b.gt_type, b.gt_n)) + (gq ? 16 + up16(vec_bytes(b.gq_type, b.gq_n)) : 0) + (pl ? 16 + up16(vec_bytes(b.pl_type, b.pl_n)) : 0);
@@ -472,7 +618,7 @@ void run_device(Run& R) {
     const int64_t nb = (int64_t)batches.size();
     const int64_t max_text = std::max<int64_t>(1, plan.max_cost[0]);
     char err[256];
-    R.dev = gtd_dev_create(R.o.device, N, (int32_t)std::min<int64_t>(B, std::max<size_t>(K, 1)), max_text, R.list, R.o.per_site, direct ? 1 : 0, err, sizeof err);
+    R.dev = gtd_dev_create(R.o.device, N, (int32_t)std::min<int64_t>(B, std::max<size_t>(K, 1)), max_text, R.list, R.o.per_site, direct ? 1 : 0, resident ? 1 : 0, err, sizeof err);
     if (!R.dev) R.stop_run("--on-device 1: %s (device %d; --on-device 0 compares on the host)", err, R.o.device);
     auto submit = [&](int64_t b) {
         const double t0 = now_s();
@@ -489,9 +635,12 @@ void run_device(Run& R) {
             const Pair& p = R.pairs[j];
             gtd::Rec r = p.rec;
             gtd::BSide ts = p.tside, cs = p.cside; bool gq, pl;
-            if (ts.have) vector_up(R.truth, ts.gt_off, ts.gt_type, ts.gt_n);
+            if (R.truth.rf) {}
+            else if (ts.have) vector_up(R.truth, ts.gt_off, ts.gt_type, ts.gt_n);
             else { memcpy(text + at, R.truth.text.data() + p.rec.t_off, (size_t)r.t_len); r.t_off = at; at += r.t_len; txt += r.t_len; }
-            if (cs.have) {
+            if (R.call.rf) {
+                if (cs.have) { needs(cs, r, true, gq, pl); if (!gq) cs.have &= ~(uint32_t)gtd::B_GQ; if (!pl) cs.have &= ~(uint32_t)gtd::B_PL; }      // (as a staged side says it)
+            } else if (cs.have) {
                 needs(cs, r, true, gq, pl);
                 vector_up(R.call, cs.gt_off, cs.gt_type, cs.gt_n);
                 if (gq) vector_up(R.call, cs.gq_off, cs.gq_type, cs.gq_n); else cs.have &= ~(uint32_t)gtd::B_GQ;      // (not staged: not to be read)
@@ -500,9 +649,12 @@ void run_device(Run& R) {
             recs[n] = r;
             if (direct) { sides[2 * n] = ts; sides[2 * n + 1] = cs; }
         }
-        if (gtd_dev_submit(R.dev, slot, n, at) != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
+        const int rc = !resident ? gtd_dev_submit(R.dev, slot, n, at)
+                                 : gtd_dev_submit_resident(R.dev, slot, n, at, R.truth.rf ? rf_device_text(R.truth.rf) : nullptr, R.truth.rf ? rf_total(R.truth.rf) : 0,
+                                                           R.call.rf ? rf_device_text(R.call.rf) : nullptr, R.call.rf ? rf_total(R.call.rf) : 0);
+        if (rc != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
         R.text_up += txt; R.vec_up += vec;                                    // (the padding in front of a vector is neither)
-         R.n_batches += direct; R.t_dev += now_s() - t0;
+         R.n_batches += direct; R.n_timed += n > 0; R.t_dev += now_s() - t0;
     };
     auto retire = [&](int64_t b) {
         double t0 = now_s();
@@ -522,7 +674,7 @@ void run_device(Run& R) {
     std::vector<int64_t> dt(R.table.size());
     if (gtd_dev_table(R.dev, dt.data()) != 0) R.stop_run("--on-device 1: %s", gtd_dev_error(R.dev));
     for (size_t i = 0; i + 2 < dt.size(); i++) R.table[i] += dt[i];
-    if (direct) gtd_dev_times(R.dev, &R.ms_stage, &R.ms_decode);
+    if (direct || resident) gtd_dev_times(R.dev, &R.ms_stage, &R.ms_decode);
 }
 
 }  // namespace
@@ -534,8 +686,9 @@ int main(int argc, char** argv) {
     double t0 = now_s();
     {
         FileReader reader; reader.device_inflate = o.device_inflate; reader.device = o.device; reader.verbose = o.verbose;
-        R.truth = read_input_file(reader, o.truth, o.bcf_direct != 0);
-        R.call = read_input_file(reader, o.call, o.bcf_direct != 0);
+        int64_t left = o.resident_max;                                 // the truth file first; the call file gets what is left
+        if (o.resident) { read_input_resident(reader, o, o.truth, left, R.truth); read_input_resident(reader, o, o.call, left, R.call); }
+        else { read_input_file(reader, o.truth, o.bcf_direct != 0, R.truth); read_input_file(reader, o.call, o.bcf_direct != 0, R.call); }
     }
     R.out_fp = fopen(o.out.c_str(), "w");
     if (!R.out_fp) die("Could not open output file %s for writing", o.out.c_str());
@@ -586,7 +739,7 @@ int main(int argc, char** argv) {
             if (r.c_nal > 5) { snprintf(msg, sizeof msg, "The call record at position %lld has %d alleles: -doGQ 8 reads PL for at most 5.", (long long)C.pos, r.c_nal); R.stop = msg; break; }
         }
         p.tside = bcf_side(R.truth, ti, r.t_nal, r.t_map); p.cside = bcf_side(R.call, ci, r.c_nal, r.c_map);
-        R.n_direct[0] += p.tside.have != 0; R.n_direct[1] += p.cside.have != 0;
+        R.n_direct[0] += R.truth.vectors(ti); R.n_direct[1] += R.call.vectors(ci);      // (not a resident record whose line stands as text: its side never fits)
         R.pairs.push_back(p);
     }
     const long nsites2 = (long)R.pairs.size();
@@ -615,8 +768,13 @@ int main(int argc, char** argv) {
         fprintf(stderr, "[bcf] bcf-direct 1: records judged from their vectors: truth %ld, call %ld; redone on the host %ld; vector bytes sent up %lld, text bytes sent up %lld; "
                         "device stage %.3f ms over %ld batches (hipEvent pairs), of which k_gtd_bcf_decode %.3f ms\n",
                 R.n_direct[0], R.n_direct[1], R.n_host, (long long)R.vec_up, (long long)R.text_up, R.ms_stage, R.n_batches, R.ms_decode);
+    if (o.verbose && o.resident)
+        fprintf(stderr, "[resident] truth %d, call %d: device stage %.3f ms over %ld batches (hipEvent pairs), of which %s %.3f ms\n",
+                R.truth.rf ? 1 : 0, R.call.rf ? 1 : 0, R.ms_stage, R.n_timed, (R.truth.direct || R.call.direct) ? "k_gtd_bcf_decode" : "k_gtd_parse", R.ms_decode);
     fprintf(stderr, "\n\nFinished running gtDiscordance\n\t-> Output file: %s\n", o.out.c_str());
     if (R.dev) gtd_dev_destroy(R.dev);
+    if (R.truth.rf) rf_destroy(R.truth.rf);
+    if (R.call.rf) rf_destroy(R.call.rf);
     fclose(R.out_fp);
     fflush(stdout);
     return 0;

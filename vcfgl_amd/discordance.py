@@ -115,13 +115,17 @@ GTDISC_PROGRAM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin",
 
 
 def compare_files(truth, call, out, do_gq=0, per_site=False, on_device=True, device=None, batch_records=None, verbose=False,
-                  timeout=None, env=None, device_inflate=None, bcf_direct=None):
+                  timeout=None, env=None, device_inflate=None, bcf_direct=None, resident=None, resident_max_bytes=None):
     """Runs gtdiscordance_hip -t `truth` -i `call` -o `out` -doGQ `do_gq` [-perSite 1] as a fresh child process and returns
     (returncode, stdout, stderr) as text; stdout holds the -perSite lines, `out` the table or the -doGQ 1 / 2 listing.
     on_device=False compares on the host and touches no GPU; on_device=True without a GPU fails (returncode 1): there is no
     fallback.  device_inflate=True inflates the BGZF members of both files on the GPU (--device-inflate 1; any other file is read by
     zlib as without it), also under on_device=False.  bcf_direct=True judges a BCF file of the pair from its typed GT / GQ / PL vectors
-    (--bcf-direct 1) and writes the same bytes as without it.  A missing program is an error (build the package first)."""
+    (--bcf-direct 1) and writes the same bytes as without it.  resident=True (--resident 1, with device_inflate and on_device) leaves
+    each BGZF file of the pair in GPU memory once inflated -- VCF text, or BCF under bcf_direct -- so that only the records' heads
+    come down and the batches read the files where they lie; resident_max_bytes bounds the inflated and compressed bytes of both
+    files together (--resident-max-bytes; default: the GPU's free memory less 1 GiB).  A file that cannot be resident is read as
+    without the flag; the bytes written are the same.  A missing program is an error (build the package first)."""
     if not os.path.exists(GTDISC_PROGRAM):
         raise FileNotFoundError("%s is not built (make -C vcfgl_amd/csrc all)" % GTDISC_PROGRAM)
     cmd = [GTDISC_PROGRAM, "-t", str(truth), "-i", str(call), "-o", str(out), "-doGQ", str(int(do_gq)), "-perSite", "1" if per_site else "0",
@@ -134,6 +138,10 @@ def compare_files(truth, call, out, do_gq=0, per_site=False, on_device=True, dev
         cmd += ["--device-inflate", "1" if device_inflate else "0"]
     if bcf_direct is not None:
         cmd += ["--bcf-direct", "1" if bcf_direct else "0"]
+    if resident is not None:
+        cmd += ["--resident", "1" if resident else "0"]
+    if resident_max_bytes is not None:
+        cmd += ["--resident-max-bytes", str(int(resident_max_bytes))]
     if verbose:
         cmd += ["--verbose", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
